@@ -21,11 +21,13 @@
 #include <cstdio>
 #include <cstring>
 #include <thread>
+#include <limits>
 #include <set>
 #include <vector>
 
 #include "../wave_tracer_amd/csrc/wt/bdpt.h"
 #include "../wave_tracer_amd/csrc/wt/path.h"
+#include "../wave_tracer_amd/csrc/wt/diffraction_probe.h"
 
 using namespace wt;
 
@@ -698,6 +700,43 @@ int oracle_query_regions(const void* scene_host, const float* cones, uint32_t n,
             if (k < edge_cap) out_edges_slab[(size_t)i * edge_cap + k++] = e;
         out_flux[2 * i] = (float)fl;
         out_flux[2 * i + 1] = (float)fs;
+    }
+    return 0;
+}
+
+// The sequential Fraunhofer aperture per query (wt/diffraction_probe.h: probe_fsd_sequential, the semantics of bdpt_walk_step) with the
+// layouts of wtgpu_test_fsd_apertures: hdr n x kFsdProbeWords words, segs n x pool_cap segment records (each query its own pool).
+int oracle_fsd_apertures(const void* scene_host, const float* cones, const float* sk, const uint32_t* ids, const uint32_t* n_ids, uint32_t n, uint32_t id_cap,
+                         uint32_t pool_cap, uint32_t* hdr, float* segs) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    for (uint32_t q = 0; q < n; ++q) {
+        uint32_t edge_counter = 0;
+        const fsd_pool_t pool{nullptr, reinterpret_cast<fsd_edge_t*>(segs) + (size_t)q * pool_cap, nullptr, 1u, &edge_counter, pool_cap};
+        const cone_t beam = probe_cone(cones + (size_t)q * 10);
+        const uint32_t m = n_ids[q] < id_cap ? n_ids[q] : id_cap;
+        fsd_aperture_t ap;
+        const bool ok = probe_fsd_sequential(sc, beam, sk[3 * q + 2], vec2{sk[3 * q], sk[3 * q + 1]}, ids + (size_t)q * id_cap, m, pool, 0u, ap);
+        probe_fsd_header(ok, ap, hdr + (size_t)q * kFsdProbeWords);
+    }
+    return 0;
+}
+// The UTD aperture and path_do_fsd per query with the layouts of wtgpu_test_utd_sums; the header words of the cooperative sums (4..6) are NaN
+// (there is no wavefront here).
+int oracle_utd_sums(const void* scene_host, const float* queries, const uint32_t* ids, const uint32_t* n_ids, uint32_t n, uint32_t id_cap, uint32_t utd_cap,
+                    uint32_t* recs, uint32_t* hdr, uint32_t* edges) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    std::vector<stack_entry_t> st(kOracleStack);
+    const stack_ref_t stack = make_flat_stack(st.data(), kOracleStack);
+    for (uint32_t q = 0; q < n; ++q) {
+        const utd_probe_query_t Q = utd_probe_query(queries + (size_t)q * kUtdProbeQueryFloats);
+        const uint32_t m = n_ids[q] < id_cap ? n_ids[q] : id_cap;
+        utd_edge_rec_t* r = reinterpret_cast<utd_edge_rec_t*>(recs) + (size_t)q * utd_cap;
+        utd_aperture_t ap;
+        probe_utd_build(sc, Q, ids + (size_t)q * id_cap, m, utd_cap, r, ap);
+        uint32_t* h = hdr + (size_t)q * kUtdProbeWords;
+        probe_utd_terms(sc, Q, ap, r, stack, h, edges + (size_t)q * utd_cap * kUtdProbeEdgeWords);
+        h[4] = h[5] = h[6] = probe_bits(std::numeric_limits<float>::quiet_NaN());
+        h[7] = probe_bits(probe_utd_sequential(sc, Q, ap, r, stack));
     }
     return 0;
 }

@@ -109,6 +109,9 @@ def load_library():
     lib.wtgpu_trace_rays.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp]
     lib.wtgpu_traverse_cones.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
     lib.wtgpu_query_regions.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.wtgpu_test_fsd_apertures.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp, vp]
+    lib.wtgpu_test_utd_sums.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
+    lib.wtgpu_test_profile_counters.argtypes = [vp, vp, u32]
     lib.wtgpu_calibrate_copy.argtypes = [u64, i32]
     lib.wtgpu_get_counters.argtypes = [vp, C.POINTER(Counters)]
     lib.wtgpu_reset_counters.argtypes = [vp]
@@ -333,6 +336,57 @@ class Scene:
         u = lambda t: t.cpu().numpy().view(np.uint32)
         return {"dist": dist.cpu().numpy(), "flags": u(flags), "primary": u(primary), "ntris": u(ntris), "nedges": u(nedges), "edges": u(edges),
                 "flux": flux.cpu().numpy()}
+
+    def fsd_apertures(self, cones, sk, ids, n_ids, pool_cap=4096, mode=0):
+        """Test hook (wtgpu_test_hooks.h): one Fraunhofer aperture per query.  cones [n,10], sk [n,3] = (sigma.x, sigma.y, k), ids [n,id_cap] edge ids,
+        n_ids [n]; mode 0 = coop_build_aperture, 1 = the sequential build.  -> (hdr [n,8] u32, segs [n,pool_cap,7] f32); layouts: wt/diffraction_probe.h."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.device)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        n, id_cap = ids.shape
+        n_ids = np.ascontiguousarray(n_ids, dtype=np.uint32)
+        assert len(cones) == n and len(sk) == n and len(n_ids) == n and (n_ids <= id_cap).all()
+        n_edges = self.info.n_edges
+        assert all((ids[i, :n_ids[i]] < n_edges).all() for i in range(n)), "edge id out of range"
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        d_cones, d_sk = t(cones, np.float32), t(sk, np.float32)
+        d_ids, d_nids = t(ids.view(np.int32), np.int32), t(n_ids.view(np.int32), np.int32)
+        hdr = torch.zeros((n, 8), dtype=torch.int32, device=dev)
+        segs = torch.zeros((n, pool_cap, 7), dtype=torch.float32, device=dev)
+        _check(load_library().wtgpu_test_fsd_apertures(self._h, None, d_cones.data_ptr(), d_sk.data_ptr(), d_ids.data_ptr(), d_nids.data_ptr(), n, id_cap,
+                                                       pool_cap, mode, hdr.data_ptr(), segs.data_ptr()))
+        torch.cuda.synchronize(dev)
+        return hdr.cpu().numpy().view(np.uint32), segs.cpu().numpy()
+
+    def utd_sums(self, queries, ids, n_ids, utd_cap=48):
+        """Test hook (wtgpu_test_hooks.h): one UTD aperture per query [n,32] (wt/diffraction_probe.h) from ids [n,id_cap] / n_ids [n], its per-wedge
+        terms and the coherent sums of coop_do_fsd<1,8,64> and path_do_fsd.  -> (hdr [n,8] u32, edges [n,utd_cap,8] u32, recs [n,utd_cap,3] u32)."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.device)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        n, id_cap = ids.shape
+        n_ids = np.ascontiguousarray(n_ids, dtype=np.uint32)
+        assert len(queries) == n and len(n_ids) == n and (n_ids <= id_cap).all()
+        n_edges = self.info.n_edges
+        assert all((ids[i, :n_ids[i]] < n_edges).all() for i in range(n)), "edge id out of range"
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        d_q, d_ids, d_nids = t(queries, np.float32), t(ids.view(np.int32), np.int32), t(n_ids.view(np.int32), np.int32)
+        hdr = torch.zeros((n, 8), dtype=torch.int32, device=dev)
+        edges = torch.zeros((n, utd_cap, 8), dtype=torch.int32, device=dev)
+        recs = torch.zeros((n, utd_cap, 3), dtype=torch.int32, device=dev)
+        _check(load_library().wtgpu_test_utd_sums(self._h, None, d_q.data_ptr(), d_ids.data_ptr(), d_nids.data_ptr(), n, id_cap, utd_cap, recs.data_ptr(),
+                                                  hdr.data_ptr(), edges.data_ptr()))
+        torch.cuda.synchronize(dev)
+        u = lambda x: x.cpu().numpy().view(np.uint32)
+        return u(hdr), u(edges), u(recs)
+
+    def profile_counters(self, n=8):
+        """Test hook (wtgpu_test_hooks.h): the first n WTGPU_PROFILE scratch counters, accumulated since upload."""
+        out = (C.c_uint64 * n)()
+        _check(load_library().wtgpu_test_profile_counters(self._h, out, n))
+        return [int(v) for v in out]
 
     def counters(self):
         c = Counters()

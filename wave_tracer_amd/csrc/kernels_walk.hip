@@ -333,6 +333,7 @@ __global__ void __launch_bounds__(64, 3) k_edges(launch_args_t a) {
             if (a.profile) {
                 atomicAdd(a.st.counters + kNumCounters + 5, 1ull);
                 atomicAdd(a.st.counters + kNumCounters + 6, (unsigned long long)n_edges);
+                if (marker == kApertureMarker) atomicAdd(a.st.counters + kNumCounters + 3, 1ull);   // apertures with segments built here, by the wavefront
             }
         }
         __syncthreads();

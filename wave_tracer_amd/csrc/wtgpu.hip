@@ -444,9 +444,9 @@ int wtgpu_scene_upload(wtgpu_scene* s, int device, uint64_t max_batch) {
 }
 
 static void read_knobs(wtgpu_scene* s) {
-    auto u = [](const char* name, uint32_t dflt) {
+    auto u = [](const char* name, uint32_t dflt) {   // negative -> 0; the whole uint32 range (atoi turned 4294967295 into -1, i.e. 0)
         const char* e = getenv(name);
-        return e ? (uint32_t)std::max(0, atoi(e)) : dflt;
+        return e ? (uint32_t)std::min<long long>(std::max<long long>(0, strtoll(e, nullptr, 10)), 0xFFFFFFFFll) : dflt;
     };
     wtgpu_scene::knobs_t& k = s->knobs;
     k.cone_budget = u("WTGPU_CONE_BUDGET", kConeBudget);
@@ -1349,7 +1349,7 @@ int wtgpu_get_counters(wtgpu_scene* s, wtgpu_counters* out) {
     if (s->knobs.profile == 1) {
         unsigned long long p[8];
         HIP_CHECK(hipMemcpy(p, s->slices[0].counters + kNumCounters, sizeof(p), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[wtgpu profile] flux tasks: %llu, candidates %llu (max %llu per task), exact-tested %llu; k_edges: %llu walks, %llu edges\n", p[0], p[1], p[4], p[2], p[5], p[6]);
+        fprintf(stderr, "[wtgpu profile] flux tasks: %llu, candidates %llu (max %llu per task), exact-tested %llu; k_edges: %llu walks, %llu edges, %llu apertures built\n", p[0], p[1], p[4], p[2], p[5], p[6], p[3]);
     }
     if (s->knobs.profile == 3) {
         unsigned long long p[kProfSlots];
@@ -1436,6 +1436,31 @@ int wtgpu_query_regions(wtgpu_scene* s, void* stream_, const float* d_cones, uin
     hipLaunchKernelGGL(k_query_regions, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream_), s->dev, d_cones, n, edge_cap, d_dist, d_flags, d_primary,
                        d_ntris, d_nedges, d_edges, d_flux, s->slices[0].counters + kDroppedSlot);
     HIP_CHECK(hipGetLastError());
+    return WTGPU_OK;
+}
+
+int wtgpu_test_profile_counters(wtgpu_scene* s, unsigned long long* out, uint32_t n) {
+    if (!s || !out || !s->uploaded || n > kProfSlots) return fail(WTGPU_ERR_INVALID, "wtgpu_test_profile_counters: uploaded scene, n <= kProfSlots");
+    {
+        const int rc = drain_all(s);
+        if (rc) return rc;
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, s->slices[0].counters + kNumCounters, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return WTGPU_OK;
+}
+int wtgpu_test_fsd_apertures(wtgpu_scene* s, void* stream, const float* d_cones, const float* d_sk, const uint32_t* d_ids, const uint32_t* d_n_ids,
+                             uint32_t n, uint32_t id_cap, uint32_t pool_cap, uint32_t mode, uint32_t* d_hdr, float* d_segs) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    if (mode > 1 || id_cap == 0 || pool_cap == 0) return fail(WTGPU_ERR_INVALID, "wtgpu_test_fsd_apertures: mode 0 / 1, id_cap and pool_cap > 0");
+    HIP_CHECK((hipError_t)test_fsd_apertures(s->dev, static_cast<hipStream_t>(stream), d_cones, d_sk, d_ids, d_n_ids, n, id_cap, pool_cap, mode, d_hdr, d_segs));
+    return WTGPU_OK;
+}
+int wtgpu_test_utd_sums(wtgpu_scene* s, void* stream, const float* d_queries, const uint32_t* d_ids, const uint32_t* d_n_ids, uint32_t n, uint32_t id_cap,
+                        uint32_t utd_cap, uint32_t* d_recs, uint32_t* d_hdr, uint32_t* d_edges) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    if (id_cap == 0 || utd_cap == 0) return fail(WTGPU_ERR_INVALID, "wtgpu_test_utd_sums: id_cap and utd_cap > 0");
+    HIP_CHECK((hipError_t)test_utd_sums(s->dev, static_cast<hipStream_t>(stream), d_queries, d_ids, d_n_ids, n, id_cap, utd_cap, d_recs, d_hdr, d_edges));
     return WTGPU_OK;
 }
 

@@ -5,6 +5,7 @@
 //   kernels_fsd.hip     k_flux_split, k_flux_tasks, k_interact_c, k_interact_c_hard (Fraunhofer interactions: power sums, rejection sampling)
 //   kernels_path.hip    k_path_* (plt_path)
 //   kernels_connect.hip k_connect_* (strategy buckets, connections, MIS, film splat)
+//   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms (wtgpu_test_hooks.h)
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -19,6 +20,7 @@
 #include "wt/bdpt.h"
 #include "wt/coop.h"
 #include "wt/coop_fsd.h"
+#include "wt/coop_utd.h"
 #include "wt/path.h"
 
 using namespace wt;
@@ -395,6 +397,11 @@ __global__ void k_traverse_cones(scene_t sc, const float* cones, uint32_t n, uin
                                  uint32_t* scratch_tris);
 __global__ void k_query_regions(scene_t sc, const float* cones, uint32_t n, uint32_t edge_cap, float* dist, uint32_t* flags, uint32_t* primary, uint32_t* ntris,
                                 uint32_t* nedges, uint32_t* edges, float* flux, unsigned long long* dropped);
+// kernels_test.hip: launches of the test entry points (wtgpu_test_hooks.h); return a hipError_t
+int test_fsd_apertures(const scene_t& sc, hipStream_t stream, const float* d_cones, const float* d_sk, const uint32_t* d_ids, const uint32_t* d_n_ids,
+                       uint32_t n, uint32_t id_cap, uint32_t pool_cap, uint32_t mode, uint32_t* d_hdr, float* d_segs);
+int test_utd_sums(const scene_t& sc, hipStream_t stream, const float* d_queries, const uint32_t* d_ids, const uint32_t* d_n_ids, uint32_t n, uint32_t id_cap,
+                  uint32_t utd_cap, uint32_t* d_recs, uint32_t* d_hdr, uint32_t* d_edges);
 
 }   // namespace wtk
 using namespace wtk;

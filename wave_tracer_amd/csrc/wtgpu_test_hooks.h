@@ -18,6 +18,21 @@ int wtgpu_scene_compare_part(const wtgpu_scene* a, const wtgpu_scene* b, const c
  * pipeline continues from the second one's output).  Accumulated since upload: event-timed milliseconds of each kernel, words of their outputs
  * (traversal records, triangle lists, heavy-queue checksums) that differ, walks and rounds replayed. */
 int wtgpu_trace_ab_stats(wtgpu_scene* s, double* ms_refill, double* ms_sm, uint64_t* differing_words, uint64_t* walks, uint64_t* rounds);
+/* The WTGPU_PROFILE scratch counters (accumulated since upload; n <= 128).  WTGPU_PROFILE=1: [3] apertures with segments built by k_edges'
+ * wavefront (coop_build_aperture), [5] walks k_edges gathered, [6] edge ids they gathered. */
+int wtgpu_test_profile_counters(wtgpu_scene* s, unsigned long long* out, uint32_t n);
+/* Per-query entry points of the diffraction kernels (kernels_test.hip; layouts: wt/diffraction_probe.h).  Device pointers, asynchronous on `stream`;
+ * the edge ids must be < the scene's edge count (not checked).  The CPU checker has the same entry points (oracle/oracle.cpp: oracle_fsd_apertures,
+ * oracle_utd_sums).
+ * wtgpu_test_fsd_apertures: one Fraunhofer aperture per query from an explicit edge-id list (n x id_cap, the first n_ids[q] used), built by
+ *   coop_build_aperture (mode 0) or by the sequential form after the sizing of bdpt_walk_step (mode 1), each query in a segment pool of its own
+ *   of pool_cap records (a smaller pool forces fsd_pool_alloc_edges to fail).  hdr: n x 8 words; segs: n x pool_cap segment records (7 floats).
+ * wtgpu_test_utd_sums: one UTD aperture per query (utd_build_aperture into n x utd_cap records `recs`) and its coherent sum by coop_do_fsd<1>,
+ *   <8>, <64> and path_do_fsd.  hdr: n x 8 words; edges: n x utd_cap x 8 words. */
+int wtgpu_test_fsd_apertures(wtgpu_scene* s, void* stream, const float* d_cones, const float* d_sk, const uint32_t* d_ids, const uint32_t* d_n_ids,
+                             uint32_t n, uint32_t id_cap, uint32_t pool_cap, uint32_t mode, uint32_t* d_hdr, float* d_segs);
+int wtgpu_test_utd_sums(wtgpu_scene* s, void* stream, const float* d_queries, const uint32_t* d_ids, const uint32_t* d_n_ids, uint32_t n, uint32_t id_cap,
+                        uint32_t utd_cap, uint32_t* d_recs, uint32_t* d_hdr, uint32_t* d_edges);
 #ifdef __cplusplus
 }
 #endif

@@ -6,3 +6,4 @@
 #include "kernels_fsd.hip"
 #include "kernels_path.hip"
 #include "kernels_connect.hip"
+#include "kernels_test.hip"
