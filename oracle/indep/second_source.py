@@ -184,3 +184,343 @@ def polygon_fourier_integral(P, xi, n=40):
         Y = a[1] + S * (b[1] - a[1]) + T * (c[1] - a[1])
         tot += J * np.sum(W * np.exp(-1j * (xi[0] * X + xi[1] * Y)))
     return tot
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# The material layer in f64 (tests/bsdf_probe.py): diffuse, dielectric and surface_spm with the Dirac, gaussian and fractal profiles, restated
+# from the reference's formulas (scalar Python floats / complex: IEEE double and double complex).  It follows the reference, not ideal
+# physics, including its asymmetries: f() evaluates Fresnel with Re(eta) and alpha(wi, wo), sample() with the complex eta and alpha(wi, wi),
+# pdf() always applies the reflection / transmission split with Re(eta) and alpha(wi, wi) (src/bsdf/surface_spm.cpp:40-201).
+# Directions are in the local shading frame (z: the normal); a `leaf` is a dict: type ("diffuse" | "dielectric" | "spm"), eta (complex,
+# exterior / interior), refl (diffuse reflectance), profile ("dirac" | "fractal" | "gaussian"), roughness, gamma, sigma (gaussian, [1/mm],
+# 0: roughness-parametrised), refl_scale, trans_scale.
+import cmath as _cm
+import math as _m
+
+_MEANK = 2 * _m.pi / 550e-6                  # fractal.hpp:80: wavelen_to_wavenum(550 nm) [1/mm]
+_MAX_GGX_ALPHA, _MAX_T = 0.75, 70.0 ** 2     # fractal.hpp:26-27
+_F32_EPS = 2.0 ** -23
+
+
+def spm_fresnel(eta, w, n=(0.0, 0.0, 1.0)):
+    """fresnel.hpp:74-117: the coefficients of an interface of relative index eta (complex) seen from w; the refraction and every coefficient
+    use the REAL index refract() returns.  -> dict t, eta (real), Z, rs, rp, ts, tp, Ts, Tp"""
+    if eta == 1:
+        return dict(t=(-w[0], -w[1], -w[2]), eta=1.0, Z=1.0, rs=0j, rp=0j, ts=1 + 0j, tp=1 + 0j, Ts=1.0, Tp=1.0)
+    wn = w[0] * n[0] + w[1] * n[1] + w[2] * n[2]
+    abs_cosi = abs(wn)
+    # refract about n: express w in a frame where n is z (the callers use n = z or a half vector m)
+    wt = (w[0] - wn * n[0], w[1] - wn * n[1], w[2] - wn * n[2])
+    e = eta.real if wn > 0 else 1 / eta.real
+    cost2 = 1 - e * e * (1 - wn * wn)
+    if abs_cosi == 0 or cost2 < 0:
+        return dict(t=(0.0, 0.0, 1.0), eta=e, Z=1.0, rs=1 + 0j, rp=1 + 0j, ts=0j, tp=0j, Ts=0.0, Tp=0.0)
+    cost = _m.sqrt(cost2)
+    s = 1.0 if wn >= 0 else -1.0
+    t = tuple(-e * wt[i] - cost * s * n[i] for i in range(3))
+    lt = _m.sqrt(sum(x * x for x in t))
+    t = tuple(x / lt for x in t)
+    rs = (e * abs_cosi - cost) / (e * abs_cosi + cost)
+    rp = (abs_cosi - e * cost) / (abs_cosi + e * cost)
+    ts, tp = rs + 1, (rp + 1) * e
+    Z = abs(cost / (e * abs_cosi))
+    return dict(t=t, eta=e, Z=Z, rs=complex(rs), rp=complex(rp), ts=complex(ts), tp=complex(tp), Ts=min(1.0, Z * ts * ts), Tp=min(1.0, Z * tp * tp))
+
+
+def spm_fresnel_reflection(eta, w, n=(0.0, 0.0, 1.0)):
+    """fresnel.hpp:128-144: the (conductor) reflection amplitudes with the complex index; 0 from below the normal"""
+    wn = w[0] * n[0] + w[1] * n[1] + w[2] * n[2]
+    if eta == 1 or wn < 0:
+        return 0j, 0j
+    t = _cm.sqrt(1 - (1 - wn * wn) * eta * eta)
+    return (eta * wn - t) / (eta * wn + t), (wn - eta * t) / (wn + eta * t)
+
+
+def mueller_from_jones(fs, fp):
+    """The Mueller matrix of the diagonal Jones matrix diag(fs, fp) (mueller.hpp:294-316), row-major 4 x 4"""
+    Rs, Rp = abs(fs) ** 2, abs(fp) ** 2
+    x = fp * fs.conjugate()
+    M = np.zeros(16)
+    M[0] = M[5] = (Rs + Rp) / 2
+    M[1] = M[4] = (Rs - Rp) / 2
+    M[10] = M[15] = x.real
+    M[11], M[14] = x.imag, -x.imag
+    return M
+
+
+def mueller_fresnel_rt(eta, reflection, w, n=(0.0, 0.0, 1.0)):
+    """mueller.hpp:318-347: reflection -> the conductor amplitudes, transmission -> Z x the dielectric transmission amplitudes"""
+    if reflection:
+        return mueller_from_jones(*spm_fresnel_reflection(eta, w, n))
+    f = spm_fresnel(eta, w, n)
+    return f["Z"] * mueller_from_jones(f["ts"], f["tp"])
+
+
+def _roughness_T(r):
+    """fractal.hpp:29-34 (roughness_to_T) at 550 nm, and roughness_to_alpha (fractal.hpp:45-47)"""
+    a2 = min(max(r, 0.0), _MAX_GGX_ALPHA) ** 2
+    T = _MAX_T if a2 == 0 else min(_MAX_T, (1 - a2) / (4 * _MEANK ** 2 * a2))
+    return T, (r / 9) ** 2
+
+
+def profile_params(leaf, k):
+    """fractal.hpp:76-103 / gaussian.hpp:94-117: (T or sigma2, sigma2_norm, alpha); the normalisations with expm1 / log1p (exact in f64)"""
+    if leaf["profile"] == "fractal":
+        T, alpha = _roughness_T(leaf["roughness"])
+        s = (leaf["gamma"] - 1) / 2
+        return T, 1 / -_m.expm1(-s * _m.log1p(k * k * T)), alpha
+    if leaf["sigma"] > 0:
+        sigma2 = leaf["sigma"] ** 2
+        alpha = sigma2
+    else:
+        T, alpha = _roughness_T(leaf["roughness"])
+        sigma2 = 1 / T
+    return sigma2, 1 / -_m.expm1(-(k * k / 2 / sigma2)), alpha
+
+
+def profile_alpha(leaf, wiz, woz, k):
+    """the specular fraction exp(-((|wi.z| + |wo.z|) k)^2 alpha) (fractal.hpp:137-145, gaussian.hpp:156-163); 1 for Dirac"""
+    if leaf["profile"] == "dirac":
+        return 1.0
+    return _m.exp(-((abs(wiz) + abs(woz)) * k) ** 2 * profile_params(leaf, k)[2])
+
+
+def profile_delta_only(leaf):
+    """is_delta_only (fractal.hpp:166-177, gaussian.hpp:165-169): a textured roughness has no mean value, so only Dirac is delta-only then"""
+    if leaf.get("delta_only_by_mean"):
+        return leaf["profile"] == "dirac"
+    return leaf["profile"] == "dirac" or (leaf["roughness"] == 0 and not (leaf["profile"] == "gaussian" and leaf["sigma"] > 0))
+
+
+def profile_psd_z(leaf, zx, zy, k):
+    """the PSD at spatial frequency z [1/mm] (fractal.hpp:105-113, gaussian.hpp:120-128)"""
+    P, norm, _ = profile_params(leaf, k)
+    z2 = zx * zx + zy * zy
+    if leaf["profile"] == "fractal":
+        g = leaf["gamma"]
+        return norm * (k * k * (g - 1) * P / (2 * _m.pi)) / (1 + P * z2) ** ((g + 1) / 2)
+    e = _m.exp(-z2 / 2 / P)
+    return 0.0 if e <= _F32_EPS else norm * (k * k * e / (2 * _m.pi * P))
+
+
+def _gauss_max_phi(r, l):
+    if r < _F32_EPS or l < _F32_EPS:
+        return _m.pi
+    return max(1e-2, _m.acos(min(1.0, max(-1.0, (r * r + l * l - 1) / (2 * r * l)))))
+
+
+def profile_pdf(leaf, wi, wo, k):
+    """the profile's sampling density of wo (fractal.hpp:209-229; gaussian.hpp:55-75 detail::boxmueller_truncated_pdf); 0 for Dirac"""
+    if leaf["profile"] == "dirac":
+        return 0.0
+    if leaf["profile"] == "gaussian":
+        s2 = profile_params(leaf, k)[0] / (k * k)
+        mx, my = -wi[0], -wi[1]
+        d2 = mx * mx + my * my
+        l, coso = _m.sqrt(min(1.0, d2)), _m.sqrt(max(0.0, 1 - d2))
+        r2 = (wo[0] - mx) ** 2 + (wo[1] - my) ** 2
+        return .5 * _m.exp(-.5 * r2 / s2) / (_gauss_max_phi(_m.sqrt(r2), l) * s2) * coso
+    zx, zy = wi[0] + wo[0], wi[1] + wo[1]
+    fk = _m.hypot(zx, zy)
+    s = _m.sqrt(max(0.0, 1 - wi[2] ** 2))
+    phi_max = _m.pi if fk == 0 or s == 0 else _m.acos(min(1.0, max(-1.0, (fk * fk + s * s - 1) / (2 * fk * s))))
+    w = phi_max / _m.pi
+    return abs(wo[2]) * profile_psd_z(leaf, zx * k, zy * k, k) / w if w > 1e-2 else 0.0
+
+
+def profile_sample(leaf, wi, k, u0, u1):
+    """the profiles' sample maps from two uniforms: fractal.cpp:27-69 (Holzschuch & Pacanowski), gaussian.hpp:205-228 + 26-53 (truncated
+    Box-Muller); the truncation masses with expm1 / log1p.  -> (wo, pdf, psd)"""
+    if leaf["profile"] == "gaussian":
+        P = profile_params(leaf, k)[0]
+        s2 = P / (k * k)
+        mx, my = -wi[0], -wi[1]
+        d2 = mx * mx + my * my
+        l, coso = _m.sqrt(min(1.0, d2)), _m.sqrt(max(0.0, 1 - d2))
+        phi_i = _m.atan2(my, mx) if (mx != 0 or my != 0) else 0.0
+        om = -_m.expm1(-.5 * (1 + l) ** 2 / s2) * (1 - max(_F32_EPS, u0))      # 1 - x
+        x = 1 - om
+        r = _m.sqrt(-2 * s2 * _m.log1p(-om))
+        mp = _gauss_max_phi(r, l)
+        phi = phi_i + _m.pi + mp * (2 * u1 - 1)
+        wx, wy = r * _m.cos(phi) + mx, r * _m.sin(phi) + my
+        pdf = .5 * x / (mp * s2) * coso
+        psd = profile_psd_z(leaf, k * (wx - mx), k * (wy - my), k)
+    else:
+        T = profile_params(leaf, k)[0]
+        g = leaf["gamma"]
+        s = _m.sqrt(max(0.0, 1 - wi[2] ** 2))
+        phi_i = _m.atan2(wi[1], wi[0]) if s > 0 else 0.0
+        M = -_m.expm1(-(g - 1) / 2 * _m.log1p(k * k * T * (1 + s) ** 2))
+        f = _m.sqrt(_m.expm1(-2 / (g - 1) * _m.log1p(-M * u0))) / _m.sqrt(T)
+        fk = f / k
+        phi_max = _m.pi if f == 0 or s == 0 else _m.acos(min(1.0, max(-1.0, (fk * fk + s * s - 1) / (2 * fk * s))))
+        phf = phi_i + (2 * u1 - 1) * phi_max
+        zx, zy = f * _m.cos(phf), f * _m.sin(phf)
+        wx, wy = zx / k - wi[0], zy / k - wi[1]
+        psd = profile_psd_z(leaf, zx, zy, k)
+        w = phi_max / _m.pi
+        z0 = _m.sqrt(max(0.0, 1 - wx * wx - wy * wy))
+        pdf = z0 * psd / w if w > 1e-2 else 0.0
+    z = _m.sqrt(max(0.0, 1 - wx * wx - wy * wy))
+    return (wx, wy, z if wi[2] >= 0 else -z), pdf, psd
+
+
+def spm_flip_wo(wo, eta):
+    """surface_spm.cpp:28-36"""
+    sc = eta if wo[2] > 0 else 1 / eta
+    x, y = wo[0] * sc, wo[1] * sc
+    l2 = x * x + y * y
+    return (1.0, 0.0, 0.0) if l2 > 1 else (x, y, (-1.0 if wo[2] > 0 else 1.0) * _m.sqrt(max(0.0, 1 - l2)))
+
+
+def spm_has_transmission(eta, leaf=None):
+    """surface_spm.cpp:39: |Im eta|^2 / |eta|^2 <= 1e-2 (a leaf's `has_tr`, where given, decides instead: the caller's choice of side for an
+    eta on the threshold itself)"""
+    if leaf is not None and "has_tr" in leaf:
+        return leaf["has_tr"]
+    return abs(eta.imag) ** 2 / abs(eta) ** 2 <= 1e-2
+
+
+def _half(wi, wo):
+    h = [wi[i] + wo[i] for i in range(3)]
+    if wi[2] < 0:
+        h = [-x for x in h]
+    l = _m.sqrt(sum(x * x for x in h))
+    return tuple(x / l for x in h) if l > 0 else (float("nan"),) * 3
+
+
+def leaf_f(leaf, wi, wo, k, backward):
+    """bsdf f with the cosine foreshortening (diffuse.cpp:23-35, surface_spm.cpp:40-73); the dielectric is delta only: 0"""
+    if leaf["type"] == "diffuse":
+        M = np.zeros(16)
+        M[0] = wo[2] / _m.pi * leaf["refl"] if (wi[2] > 0 and wo[2] > 0) else 0.0
+        return M
+    if leaf["type"] == "dielectric":
+        return np.zeros(16)
+    eta = leaf["eta"]
+    refl = wi[2] * wo[2] >= 0
+    if wi[2] == 0 or wo[2] == 0 or profile_delta_only(leaf) or (not refl and not spm_has_transmission(eta, leaf)):
+        return np.zeros(16)
+    awo = wo if refl else spm_flip_wo(wo, eta.real)
+    alpha = profile_alpha(leaf, wi[2], awo[2], k)
+    J = (1 / eta.real if wi[2] < 0 else eta.real) ** 2 if (not refl and backward) else 1.0
+    F = mueller_fresnel_rt(complex(eta.real, 0), refl, wi, _half(wi, awo))
+    psd = profile_psd_z(leaf, k * (wi[0] + awo[0]), k * (wi[1] + awo[1]), k) if leaf["profile"] != "dirac" else 0.0
+    return (1 - alpha) * J * abs(wo[2]) * psd * (leaf["refl_scale"] if refl else leaf["trans_scale"]) * F
+
+
+def leaf_pdf(leaf, wi, wo, k):
+    """diffuse.cpp:63-71, dielectric (delta only: 0), surface_spm.cpp:165-196"""
+    if leaf["type"] == "dielectric":
+        return 0.0
+    if leaf["type"] == "diffuse":
+        return wo[2] / _m.pi if (wi[2] > 0 and wo[2] > 0) else 0.0
+    eta = leaf["eta"]
+    refl = wi[2] * wo[2] >= 0
+    if wi[2] == 0 or wo[2] == 0 or (not refl and not spm_has_transmission(eta, leaf)):
+        return 0.0
+    awo = wo if refl else spm_flip_wo(wo, eta.real)
+    alpha = profile_alpha(leaf, wi[2], wi[2], k)
+    f = spm_fresnel(complex(eta.real, 0), wi)
+    pt = (f["Ts"] + f["Tp"]) / 2
+    return (1 - alpha) * profile_pdf(leaf, wi, awo, k) * ((1 - pt) if refl else pt)
+
+
+def _cosine_hemisphere(u0, u1):
+    """sampler.hpp:171-190 (Shirley-Chiu concentric map) and the cosine lift"""
+    ox, oy = 2 * u0 - 1, 2 * u1 - 1
+    if ox == 0 and oy == 0:
+        r, th = 0.0, 0.0
+    elif abs(ox) > abs(oy):
+        r, th = ox, _m.pi / 4 * (oy / ox)
+    else:
+        r, th = oy, _m.pi / 2 - _m.pi / 4 * (ox / oy)
+    x, y = r * _m.cos(th), r * _m.sin(th)
+    return (x, y, _m.sqrt(max(0.0, 1 - x * x - y * y)))
+
+
+def leaf_sample(leaf, wi, k, backward, u):
+    """the leaf's sample from the uniforms u[...] in their order of use (diffuse.cpp:37-61, dielectric.cpp:26-72, surface_spm.cpp:75-157).
+    -> dict valid, wo, dpd (tagged: a discrete mass negated), discrete, eta, M (the weighted bsdf), lobe ("specular" | "scatter"),
+    reflection, used (uniforms consumed), and per decision (uniform index, f64 threshold) in `decisions`"""
+    r = dict(valid=False, wo=(0.0, 0.0, 1.0), dpd=0.0, discrete=False, eta=1.0, M=np.zeros(16), lobe=None, reflection=None, used=0, decisions=[])
+    i = 0
+    if leaf["type"] == "diffuse":
+        if wi[2] <= 0:
+            return r
+        wo = _cosine_hemisphere(u[0], u[1])
+        M = np.zeros(16)
+        M[0] = leaf["refl"]
+        r.update(valid=True, wo=wo, dpd=wo[2] / _m.pi, M=M, lobe="scatter", reflection=True, used=2)
+        return r
+    if leaf["type"] == "dielectric":
+        f = spm_fresnel(complex(leaf["eta"].real, 0), wi)
+        T = (f["Ts"] + f["Tp"]) / 2
+        refl = u[0] >= T
+        r["decisions"].append((0, T))
+        r["used"] = 1
+        pdf = 1 - T if refl else T
+        sc = leaf["refl_scale"] if refl else leaf["trans_scale"]
+        if sc == 0:
+            return r
+        if refl:
+            M = sc * mueller_from_jones(f["rs"], f["rp"])
+            wo = (-wi[0], -wi[1], wi[2])
+        else:
+            M = f["Z"] * sc * mueller_from_jones(f["ts"], f["tp"]) * (f["eta"] ** 2 if backward else 1.0)
+            wo = f["t"]
+        r.update(valid=True, wo=wo, dpd=-1.0, discrete=True, eta=f["eta"], M=M / pdf, lobe="specular", reflection=refl)
+        return r
+    eta = leaf["eta"]
+    alpha = profile_alpha(leaf, wi[2], wi[2], k)
+    # the reference's alpha is an f_t = float: exp(-a) is 0 below the f32 range and 1 within half an ulp of 1, which decides whether
+    # the specular resp. the scattered lobe exists; near those limits the f32 evaluation may go either way (decision index -1: the band)
+    if alpha < 2.0 ** -149 or 1 - alpha < 2.0 ** -25:
+        alpha = 0.0 if alpha < .5 else 1.0
+    elif alpha < 2.0 ** -120 or 1 - alpha < 2.0 ** -22:
+        r["decisions"].append((-1, alpha))
+    has_spec, has_scat = alpha > 0, alpha < 1
+    has_tr = spm_has_transmission(eta, leaf)
+    if wi[2] == 0 or (not has_spec and not has_scat):
+        return r
+    pdf, spec = 1.0, has_spec
+    if has_spec and has_scat:
+        if alpha == 1:
+            spec = True
+        else:
+            spec = u[i] < alpha
+            r["decisions"].append((i, alpha))
+            i += 1
+        pdf = alpha if spec else 1 - alpha
+    f = spm_fresnel(eta, wi)
+    pt = (f["Ts"] + f["Tp"]) / 2
+    refl = True
+    if has_tr:
+        refl = u[i] >= pt
+        r["decisions"].append((i, pt))
+        i += 1
+        pdf *= (1 - pt) if refl else pt
+    J = f["eta"] ** 2 if (not refl and backward) else 1.0
+    sc = leaf["refl_scale"] if refl else leaf["trans_scale"]
+    r["used"] = i
+    if sc == 0 or (not refl and not has_tr):
+        return r
+    if spec:
+        wo = (-wi[0], -wi[1], wi[2]) if refl else f["t"]
+        F = mueller_fresnel_rt(eta, refl, wi)
+        r.update(valid=True, wo=wo, dpd=-pdf, discrete=True, eta=1.0 if refl else f["eta"], M=F * (alpha * J * sc / pdf), lobe="specular",
+                 reflection=refl)
+        return r
+    pwo, ppdf, psd = profile_sample(leaf, wi, k, u[i], u[i + 1])
+    r["used"] = i + 2
+    F = mueller_fresnel_rt(eta, refl, wi, _half(wi, pwo))
+    wo = pwo if refl else spm_flip_wo(pwo, eta.real)
+    if not refl:   # spm_flip_wo's l2 > 1 (no refracted direction: wo = (1,0,0)) decided within rounding
+        sc_ = eta.real if pwo[2] > 0 else 1 / eta.real
+        if abs((pwo[0] * sc_) ** 2 + (pwo[1] * sc_) ** 2 - 1) < 1e-5:
+            r["decisions"].append((-1, 1.0))
+    pdf *= ppdf
+    r.update(valid=True, wo=wo, dpd=pdf, eta=1.0 if refl else f["eta"], M=F * ((1 - alpha) * J * abs(wo[2]) * psd * sc / pdf) if pdf != 0 else np.full(16, np.inf),
+             lobe="scatter", reflection=refl)
+    return r

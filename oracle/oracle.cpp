@@ -28,6 +28,7 @@
 #include "../wave_tracer_amd/csrc/wt/bdpt.h"
 #include "../wave_tracer_amd/csrc/wt/path.h"
 #include "../wave_tracer_amd/csrc/wt/diffraction_probe.h"
+#include "../wave_tracer_amd/csrc/wt/bsdf_probe.h"
 
 using namespace wt;
 
@@ -738,6 +739,37 @@ int oracle_utd_sums(const void* scene_host, const float* queries, const uint32_t
         h[4] = h[5] = h[6] = probe_bits(std::numeric_limits<float>::quiet_NaN());
         h[7] = probe_bits(probe_utd_sequential(sc, Q, ap, r, stack));
     }
+    return 0;
+}
+
+// The material layer per query (wt/bsdf_probe.h: probe_bsdf, generic form) with the layouts of wtgpu_test_bsdf_queries: n x kBsdfProbeQueryWords
+// query words, n x kBsdfProbeWords output words.
+int oracle_bsdf_queries(const void* scene_host, const uint32_t* queries, uint32_t n, uint32_t* out) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    for (uint32_t q = 0; q < n; ++q) {
+        if (queries[(size_t)q * kBsdfProbeQueryWords] >= sc.n_materials) return 1;
+        probe_bsdf<-1>(sc, queries + (size_t)q * kBsdfProbeQueryWords, out + (size_t)q * kBsdfProbeWords);
+    }
+    return 0;
+}
+// The raw texture record (texture_t, sizeof bytes) of a texture id and n floats of the texture data from `offset`: the f64 restatement's
+// texel lookups (tests/bsdf_probe.py).
+int oracle_texture_record(const void* scene_host, uint32_t id, void* out, uint32_t size) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (id >= sc.n_textures || size != sizeof(texture_t)) return 1;
+    memcpy(out, &sc.textures[id], sizeof(texture_t));
+    return 0;
+}
+int oracle_texture_data(const void* scene_host, uint32_t offset, uint32_t n, float* out) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    memcpy(out, sc.texture_data + offset, (size_t)n * sizeof(float));
+    return 0;
+}
+// The raw material record (material_t, sizeof bytes) of a material id: the f64 restatement's parameters (tests/bsdf_probe.py).
+int oracle_material_record(const void* scene_host, uint32_t mat, void* out, uint32_t size) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (mat >= sc.n_materials || size != sizeof(material_t)) return 1;
+    memcpy(out, &sc.materials[mat], sizeof(material_t));
     return 0;
 }
 

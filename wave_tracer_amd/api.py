@@ -112,6 +112,7 @@ def load_library():
     lib.wtgpu_test_fsd_apertures.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, vp, vp]
     lib.wtgpu_test_utd_sums.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
     lib.wtgpu_test_profile_counters.argtypes = [vp, vp, u32]
+    lib.wtgpu_test_bsdf_queries.argtypes = [vp, vp, vp, u32, i32, vp]
     lib.wtgpu_calibrate_copy.argtypes = [u64, i32]
     lib.wtgpu_get_counters.argtypes = [vp, C.POINTER(Counters)]
     lib.wtgpu_reset_counters.argtypes = [vp]
@@ -381,6 +382,21 @@ class Scene:
         torch.cuda.synchronize(dev)
         u = lambda x: x.cpu().numpy().view(np.uint32)
         return u(hdr), u(edges), u(recs)
+
+    def bsdf_queries(self, queries, form=-1):
+        """Test hook (wtgpu_test_hooks.h): the material layer per query.  queries [n,18] u32 (wt/bsdf_probe.h); form -1 = generic, 0 / 1 / 2 = the
+        class form of diffuse / dielectric / surface_spm.  -> out [n,48] u32 (f32 bits except flags and the draw count)."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.device)
+        q = np.ascontiguousarray(queries, dtype=np.uint32)
+        n = q.shape[0]
+        assert q.shape == (n, 18) and (q[:, 0] < self.info.n_materials).all(), "material id out of range"
+        d_q = torch.from_numpy(q.view(np.int32)).to(dev)
+        out = torch.zeros((n, 48), dtype=torch.int32, device=dev)
+        _check(load_library().wtgpu_test_bsdf_queries(self._h, None, d_q.data_ptr(), n, int(form), out.data_ptr()))
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy().view(np.uint32)
 
     def profile_counters(self, n=8):
         """Test hook (wtgpu_test_hooks.h): the first n WTGPU_PROFILE scratch counters, accumulated since upload."""

@@ -1,6 +1,8 @@
 // wave_tracer_amd — test entry points of the wave-cooperative diffraction kernels (wtgpu_test_hooks.h; see wtgpu_kernels.h for the list of kernel
 // translation units).  Each runs the cooperative form and the sequential form it replaces on the same explicit queries (wt/diffraction_probe.h:
-// layouts), one query at a time; no render kernel is compiled here.
+// layouts), one query at a time; the material layer's queries run in the generic or the class form (wt/bsdf_probe.h).  No render kernel is
+// compiled here.
+#include "wt/bsdf_probe.h"
 #include "wt/diffraction_probe.h"
 #include "wtgpu_kernels.h"
 
@@ -76,6 +78,14 @@ __global__ void __launch_bounds__(64) k_test_utd_coop(scene_t sc, const float* q
     if (have && (threadIdx.x & (G - 1)) == 0) hdr[(size_t)q * kUtdProbeWords + word] = probe_bits(f);
 }
 
+// One lane per material query (wt/bsdf_probe.h); `form`: -1 generic, else the class form of that leaf type.
+template <int CLS>
+__global__ void __launch_bounds__(64) k_test_bsdf(scene_t sc, const uint32_t* queries, uint32_t n, uint32_t* out) {
+    const uint32_t q = blockIdx.x * 64 + threadIdx.x;
+    if (q >= n) return;
+    probe_bsdf<CLS>(sc, queries + (size_t)q * kBsdfProbeQueryWords, out + (size_t)q * kBsdfProbeWords);
+}
+
 int test_fsd_apertures(const scene_t& sc, hipStream_t stream, const float* d_cones, const float* d_sk, const uint32_t* d_ids, const uint32_t* d_n_ids,
                        uint32_t n, uint32_t id_cap, uint32_t pool_cap, uint32_t mode, uint32_t* d_hdr, float* d_segs) {
     if (n == 0) return 0;
@@ -92,6 +102,18 @@ int test_utd_sums(const scene_t& sc, hipStream_t stream, const float* d_queries,
     hipLaunchKernelGGL(k_test_utd_coop<1>, dim3((n + 63) / 64), dim3(64), 0, stream, sc, d_queries, n, utd_cap, recs, d_hdr, 4u);
     hipLaunchKernelGGL(k_test_utd_coop<8>, dim3((n + 7) / 8), dim3(64), 0, stream, sc, d_queries, n, utd_cap, recs, d_hdr, 5u);
     hipLaunchKernelGGL(k_test_utd_coop<64>, dim3(n), dim3(64), 0, stream, sc, d_queries, n, utd_cap, recs, d_hdr, 6u);
+    return (int)hipGetLastError();
+}
+
+int test_bsdf_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_queries, uint32_t n, int form, uint32_t* d_out) {
+    if (n == 0) return 0;
+    const dim3 grid((n + 63) / 64), block(64);
+    switch (form) {
+        case MAT_DIFFUSE: hipLaunchKernelGGL(k_test_bsdf<MAT_DIFFUSE>, grid, block, 0, stream, sc, d_queries, n, d_out); break;
+        case MAT_DIELECTRIC: hipLaunchKernelGGL(k_test_bsdf<MAT_DIELECTRIC>, grid, block, 0, stream, sc, d_queries, n, d_out); break;
+        case MAT_SURFACE_SPM: hipLaunchKernelGGL(k_test_bsdf<MAT_SURFACE_SPM>, grid, block, 0, stream, sc, d_queries, n, d_out); break;
+        default: hipLaunchKernelGGL(k_test_bsdf<-1>, grid, block, 0, stream, sc, d_queries, n, d_out); break;
+    }
     return (int)hipGetLastError();
 }
 

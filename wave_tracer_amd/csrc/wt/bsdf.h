@@ -32,6 +32,11 @@ struct bsdf_sample_t {
 };
 
 // ---- fractal surface profile ---------------------------------------------------------------------
+// The profiles' normalisations 1 / (1 - e^-x) (gaussian) and 1 / (1 - (1 + y)^-s) (fractal), and the truncation masses of their samplers,
+// cancel in f32 when the argument is small: at radio wavelengths (k ~ 0.2 / mm) the reference's expressions give 1 / 0 = inf.  Below
+// kProfileSmallArg they are computed as -expm1f(-x) resp. -expm1f(-s log1pf(y)); above it (every bundled scene: the smallest argument, the
+// double_slits screen at 50 um, is k^2 T = 3.1e-4) the reference's expressions are kept bit for bit.
+constexpr float kProfileSmallArg = 1e-4f;
 struct fractal_params_t {
     float T;   // [mm^2]
     float sigma2_norm;
@@ -42,7 +47,10 @@ WT_HD fractal_params_t fractal_params(const material_t& m, float k) {
     const float max_GGX_alpha = .75f, maxT = sqr(70.f);
     const float alpha2 = sqr(clampf(m.roughness, 0.f, max_GGX_alpha));
     const float T = fminf_(maxT, (1.f - alpha2) / (4.f * sqr(meank) * alpha2));
-    const float x = 1.f + k * k * T;
+    const float y = k * k * T;
+    if (y < kProfileSmallArg)   // 1 - (1 + y)^-(gamma-1)/2 without the cancellation (deviations)
+        return {T, 1.f / -expm1f(-(m.gamma - 1.f) / 2.f * log1pf(y)), sqr(m.roughness / 9.f)};
+    const float x = 1.f + y;
     const float p = m.gamma == 3.f ? x : powf(x, (m.gamma - 1.f) / 2.f);
     return {T, 1.f / (1.f - 1.f / p), sqr(m.roughness / 9.f)};
 }
@@ -72,7 +80,8 @@ WT_HD gaussian_params_t gaussian_params(const material_t& m, float k) {
         r.sigma2 = 1.f / T;
         r.alpha = sqr(m.roughness / 9.f);
     }
-    r.sigma2_norm = 1.f / (1.f - expf(-(k * k / 2.f / r.sigma2)));
+    const float x = k * k / 2.f / r.sigma2;
+    r.sigma2_norm = 1.f / (x < kProfileSmallArg ? -expm1f(-x) : 1.f - expf(-x));
     return r;
 }
 WT_HD float gaussian_psd(const gaussian_params_t& pr, vec2 z, float k) {
@@ -142,9 +151,17 @@ WT_HD profile_sample_t profile_sample(const material_t& m, vec3 wi, float k, sam
         const float l = sqrtf(fminf_(1.f, dot(mean, mean)));
         const float coso = sqrtf(fmaxf_(0.f, 1.f - dot(mean, mean)));
         const float phi_i = (mean.x != 0.f || mean.y != 0.f) ? atan2f(mean.y, mean.x) : 0.f;
-        const float sm = expf(-.5f * sqr(1.f + l) / s2);
-        const float x = (1.f - sm) * fmaxf_(FLT_EPSILON, u.x) + sm;
-        const float r = sqrtf(-2.f * s2 * logf(x));
+        const float a = .5f * sqr(1.f + l) / s2;
+        float x, r;
+        if (a < kProfileSmallArg) {   // x = 1 - (1 - e^-a)(1 - u): log x without the cancellation
+            const float om = -expm1f(-a) * (1.f - fmaxf_(FLT_EPSILON, u.x));
+            x = 1.f - om;
+            r = sqrtf(-2.f * s2 * log1pf(-om));
+        } else {
+            const float sm = expf(-a);
+            x = (1.f - sm) * fmaxf_(FLT_EPSILON, u.x) + sm;
+            r = sqrtf(-2.f * s2 * logf(x));
+        }
         const float max_phi = gaussian_max_phi(r, l);
         const float phi = phi_i + kPi + max_phi * (2.f * u.y - 1.f);
         const vec2 wo2 = r * vec2{cosf(phi), sinf(phi)} + mean;
@@ -160,8 +177,15 @@ WT_HD profile_sample_t profile_sample(const material_t& m, vec3 wi, float k, sam
     const vec2 u2 = sampler_r2(sampler);
     const float k2T = sqr(k) * pr.T;
     const float g = m.gamma;
-    const float M = 1.f - powf(1.f + k2T * sqr(1.f + s), -(g - 1.f) / 2.f);
-    const float f = sqrtf(powf(1.f - M * u2.x, -2.f / (g - 1.f)) - 1.f) / sqrtT;   // [1/mm]
+    const float y = k2T * sqr(1.f + s);
+    float f;   // [1/mm]
+    if (y < kProfileSmallArg) {   // M = 1 - (1 + y)^-(g-1)/2, (1 - M u)^(-2/(g-1)) - 1 without the cancellations
+        const float M = -expm1f(-(g - 1.f) / 2.f * log1pf(y));
+        f = sqrtf(expm1f(-2.f / (g - 1.f) * log1pf(-M * u2.x))) / sqrtT;
+    } else {
+        const float M = 1.f - powf(1.f + y, -(g - 1.f) / 2.f);
+        f = sqrtf(powf(1.f - M * u2.x, -2.f / (g - 1.f)) - 1.f) / sqrtT;
+    }
     const float f_k = f / k;
     const float phi_max = (f == 0.f || s == 0.f) ? kPi : acosf(clampf((sqr(f_k) + sqr(s) - 1.f) / (2.f * f_k * s), -1.f, 1.f));
     const float phi_f = phi_i + (2.f * u2.y - 1.f) * phi_max;

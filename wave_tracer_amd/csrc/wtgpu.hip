@@ -1464,6 +1464,13 @@ int wtgpu_test_utd_sums(wtgpu_scene* s, void* stream, const float* d_queries, co
     return WTGPU_OK;
 }
 
+int wtgpu_test_bsdf_queries(wtgpu_scene* s, void* stream, const uint32_t* d_queries, uint32_t n, int form, uint32_t* d_out) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    if (form < -1 || form > (int)MAT_SURFACE_SPM) return fail(WTGPU_ERR_INVALID, "wtgpu_test_bsdf_queries: form -1, 0, 1 or 2");
+    HIP_CHECK((hipError_t)test_bsdf_queries(s->dev, static_cast<hipStream_t>(stream), d_queries, n, form, d_out));
+    return WTGPU_OK;
+}
+
 int wtgpu_calibrate_copy(uint64_t n_dwords, int repeats) {
     uint32_t *in = nullptr, *out = nullptr;
     HIP_CHECK(hipMalloc((void**)&in, n_dwords * 4));

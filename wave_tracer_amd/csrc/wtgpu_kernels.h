@@ -5,7 +5,7 @@
 //   kernels_fsd.hip     k_flux_split, k_flux_tasks, k_interact_c, k_interact_c_hard (Fraunhofer interactions: power sums, rejection sampling)
 //   kernels_path.hip    k_path_* (plt_path)
 //   kernels_connect.hip k_connect_* (strategy buckets, connections, MIS, film splat)
-//   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms (wtgpu_test_hooks.h)
+//   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -402,6 +402,7 @@ int test_fsd_apertures(const scene_t& sc, hipStream_t stream, const float* d_con
                        uint32_t n, uint32_t id_cap, uint32_t pool_cap, uint32_t mode, uint32_t* d_hdr, float* d_segs);
 int test_utd_sums(const scene_t& sc, hipStream_t stream, const float* d_queries, const uint32_t* d_ids, const uint32_t* d_n_ids, uint32_t n, uint32_t id_cap,
                   uint32_t utd_cap, uint32_t* d_recs, uint32_t* d_hdr, uint32_t* d_edges);
+int test_bsdf_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_queries, uint32_t n, int form, uint32_t* d_out);
 
 }   // namespace wtk
 using namespace wtk;

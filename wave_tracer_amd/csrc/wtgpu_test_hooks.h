@@ -33,6 +33,11 @@ int wtgpu_test_fsd_apertures(wtgpu_scene* s, void* stream, const float* d_cones,
                              uint32_t n, uint32_t id_cap, uint32_t pool_cap, uint32_t mode, uint32_t* d_hdr, float* d_segs);
 int wtgpu_test_utd_sums(wtgpu_scene* s, void* stream, const float* d_queries, const uint32_t* d_ids, const uint32_t* d_n_ids, uint32_t n, uint32_t id_cap,
                         uint32_t utd_cap, uint32_t* d_recs, uint32_t* d_hdr, uint32_t* d_edges);
+/* Per-query entry point of the material layer (kernels_test.hip: k_test_bsdf; layouts: wt/bsdf_probe.h): n queries of 18 words, n x 48 output
+ * words, device pointers, asynchronous on `stream`.  form -1: the generic material_f / material_pdf / material_sample; 0, 1, 2 (diffuse,
+ * dielectric, surface_spm): the class forms of the material-sorted interaction pass.  Material ids must be < the scene's material count (not
+ * checked).  The CPU checker's counterpart (generic form only): oracle/oracle.cpp: oracle_bsdf_queries. */
+int wtgpu_test_bsdf_queries(wtgpu_scene* s, void* stream, const uint32_t* d_queries, uint32_t n, int form, uint32_t* d_out);
 #ifdef __cplusplus
 }
 #endif
