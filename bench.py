@@ -11,6 +11,11 @@ reduce of the film afterwards (outside the timed region it would be <2 ms; it is
 
 Prints ONE JSON line (rank 0).  --dump-outputs DIR: after the timed steps, rank 0 writes the films the timed path accumulated (what a caller of
 render_async_into receives after the last step) as DIR/<name>.npy, so that two builds can be compared output for output.
+
+A plain run sets up, warms up, times the steps and reports; its roofline comes from the run's own counters and HIP-event times, with
+`traffic` taken from the newest measurement committed under profiles/.  --full adds what takes runs of its own (one GPU only): the live
+HBM traffic of the dominant kernel (two rocprofv3 --pmc child passes over one step; --no-traffic skips them) and the CPU checker's
+baseline on the same film (~15 s; --no-cpu-baseline skips it).
 """
 import argparse
 import json
@@ -157,8 +162,10 @@ def main():
                     "etoile / bidir_room = C4's ~560 seeded buildings, C5's ~50 objects and 34 materials)")
     ap.add_argument("--polarimetric", type=int, default=-1, help="Stokes film (default: on for bidir_room = BASELINE.json configs[4])")
     ap.add_argument("--ray-tracing", action="store_true", help="diagnostic: --ray-tracing of the reference CLI (wt_context.hpp:43), no cones / diffraction")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the live PMC measurement of roofline.traffic (two rocprofv3 passes over one step, ~20 s)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the live PMC traffic of roofline.traffic and "
+                    "the CPU baseline (one GPU only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the live PMC measurement of roofline.traffic (two rocprofv3 passes over one step, ~20 s)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="film reduce: nccl = RCCL over xGMI (one GPU per rank); gloo: host reduce, ranks may share a GPU (launcher tests on 1-GPU boxes)")
@@ -320,11 +327,12 @@ def main():
         achieved = alg_bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
         # whole path: all algorithmic bytes of a step over the wall time of a step
         whole = bytes_per_sample * npix * s_rank / (dt / K) / 1e9
-        # HBM traffic of that kernel, per launch like `achieved`: measured live (measure_traffic: two rocprofv3 --pmc passes over one step of this
-        # workload, on this box, in child processes after the timed region); if rocprofv3 is unavailable, the summary committed under profiles/
+        # HBM traffic of that kernel, per launch like `achieved`: with --full measured live (measure_traffic: two rocprofv3 --pmc passes over one
+        # step of this workload, on the same GPU, in child processes after the timed region); in a plain run, or if rocprofv3 is unavailable, the
+        # summary committed under profiles/
         traffic, traffic_src = None, None
         integ, max_depth, n_tris_scene, emitters = int(sc.info.integrator), int(sc.info.max_depth), int(sc.info.n_tris), sc.emitter_summary()
-        if world == 1 and not args.no_traffic:
+        if args.full and world == 1 and not args.no_traffic:
             # the child processes size their batches from the FREE device memory (wtgpu_scene_upload): give this process's state and films back
             # first, or the child splits the step into smaller batches than the timed region ran and `traffic` is per a different launch
             del value, weight, light
@@ -428,7 +436,7 @@ def main():
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if film_sums is not None:
             out["film_sums"] = {"value": film_sums[0], "weight": film_sums[1], "light": film_sums[2]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.scene, args.res, args.cpu_seconds, md, pol)
         print(json.dumps(out))
     if distributed:

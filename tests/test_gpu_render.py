@@ -640,6 +640,31 @@ def test_bench_launches_its_own_ranks(built):
     assert "roofline" in d and "whole_path" in d["roofline"]
 
 
+def test_bench_full_adds_the_cpu_baseline(built):
+    """A plain `bench.py` run reports the headline and the roofline of its own counters only; `--full` adds the legs that take runs of
+    their own (here the CPU baseline; the live PMC passes are skipped with --no-traffic)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    common = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--scene", "furnace", "--res", "64", "--spp-per-step", "1"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-traffic", "--cpu-seconds", "1"])):
+        out = subprocess.check_output(common + extra, env=env, stderr=subprocess.DEVNULL, timeout=300).decode()
+        ls = [l for l in out.splitlines() if l.startswith("{")]
+        assert len(ls) == 1, out
+        lines[name] = json.loads(ls[0])
+    for d in lines.values():
+        assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["unit"] == "Msamples/s" and d["higher_is_better"]
+        assert d["config"]["samples_per_step"] == 64 * 64 and "whole_path" in d["roofline"]
+    assert "cpu_baseline" not in lines["plain"]
+    assert (lines["plain"]["roofline"]["traffic_source"] or {}).get("measured") is None
+    cb = lines["full"]["cpu_baseline"]
+    assert cb["value"] > 0 and cb["unit"] == "Msamples/s" and cb["cores"] >= 1
+
+
 def test_pause_resume_and_capture_intermediate(built):
     """The renderer's remaining interrupts (include/wt/scene/interrupts.hpp; src/scene/render.cpp:306-368) at the C-ABI: a pause requested from
     the progress callback holds the render at the chunk boundary while another thread asks for an intermediate capture (served WHILE paused, with

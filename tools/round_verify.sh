@@ -6,9 +6,9 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; O=$R/gpurun_out/${TAG}final; mkdir -p $
 export HSA_KERNARG_POOL_SIZE=16777216
 ( time python -m pytest tests -m gpu -q --timeout 600 ) > $O/tests.log 2>&1; echo "tests rc=$?"; tail -6 $O/tests.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -4 $O/smoke.log
-timeout 500 python bench.py > $O/bench_line_1440.json 2> $O/bench_line_1440.err; cut -c1-300 $O/bench_line_1440.json
-timeout 400 python bench.py --scene etoile --res 720 > $O/bench_etoile.json 2>/dev/null; cut -c1-200 $O/bench_etoile.json
-timeout 400 python bench.py --scene bidir_room --res 1920 > $O/bench_bidir_room.json 2>/dev/null; cut -c1-200 $O/bench_bidir_room.json
+timeout 500 python bench.py --full > $O/bench_line_1440.json 2> $O/bench_line_1440.err; cut -c1-300 $O/bench_line_1440.json
+timeout 400 python bench.py --full --scene etoile --res 720 > $O/bench_etoile.json 2>/dev/null; cut -c1-200 $O/bench_etoile.json
+timeout 400 python bench.py --full --scene bidir_room --res 1920 > $O/bench_bidir_room.json 2>/dev/null; cut -c1-200 $O/bench_bidir_room.json
 bash tools/profile_round.sh $TAG > $O/profile_round.log 2>&1; tail -2 $O/profile_round.log
 # lane utilisation, L1 / L2 / texture-address passes (one step each)
 bash tools/pmc_pass.sh ${TAG}_pmc_SQ_lane_utilisation "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY"
