@@ -186,6 +186,33 @@ int wtgpu_traverse_cones(wtgpu_scene* scene, void* stream, const float* d_cones,
 int wtgpu_query_regions(wtgpu_scene* scene, void* stream, const float* d_cones, uint32_t n, uint32_t edge_cap, float* d_dist, uint32_t* d_flags,
                         uint32_t* d_primary, uint32_t* d_ntris, uint32_t* d_nedges, uint32_t* d_edges, float* d_flux);
 
+/* By-geometry sensor masks (include/wt/sensor/mask/mask.hpp, src/sensor/mask.cpp:28-108), what the reference's CLI writes as the alpha channel
+ * of `<sensor>_tonemapped_masked` (src/main.cpp:315-326).  A scene file's perspective sensor may hold <sensor_mask type="by-geometry"> with a
+ * mask_id_regex (src/sensor/perspective.cpp:98); it is kept beside the flattened scene, which it does not change.
+ *
+ * The element id of shape `shape` (the scene's shape order = tri_meta_t::shape_idx): the element's `id`, "__unnamed_$<n>" for unnamed enabled
+ * top-level elements (src/scene/loader/loader.cpp:131-133); "" for bundled scenes and wtgpu_scene_create_from_desc.  Valid while the handle lives. */
+int wtgpu_scene_shape_id(const wtgpu_scene* scene, uint32_t shape, const char** id);
+/* The scene file's mask (mask_t::load, src/sensor/mask.cpp:76-108).  `samples` is always 32: the loader reads a `samples` attribute but never
+ * passes it to the mask (mask.hpp:44-52).  shape_flags[i] = 1 if std::regex_match(id of shape i, regex) (ECMAScript, the whole id). */
+typedef struct wtgpu_sensor_mask_spec {
+    int32_t present;              /* 0: no <sensor_mask> (the other fields are empty) */
+    uint32_t samples;
+    const char* regex;
+    const uint8_t* shape_flags;   /* n_shapes bytes, valid while the handle lives */
+    uint32_t n_shapes;
+} wtgpu_sensor_mask_spec;
+int wtgpu_scene_sensor_mask_spec(const wtgpu_scene* scene, wtgpu_sensor_mask_spec* out);
+/* mask_t::create_mask (src/sensor/mask.cpp:28-66) on the device, into the caller's DEVICE buffer d_out [height][width] f32, on `stream`: per pixel
+ * `samples` rays of the sensor's own pixel sampling (perspective.hpp:229-262, k = 0), each traced to its closest hit (ads_t::intersect); a hit on a
+ * shape whose flag is 0 adds 1 / float(samples), in sequence (a miss adds nothing).  shape_flags: n_shapes bytes on the host, 1 = "matches the
+ * regex", copied before the call returns; NULL = the scene file's flags.  RNG: sample s of pixel p draws from the stream (seed, p * samples + s).
+ * Needs an uploaded scene with a perspective sensor (WTGPU_ERR_INVALID otherwise); touches neither films nor counters. */
+int wtgpu_sensor_mask(wtgpu_scene* scene, void* stream, const uint8_t* shape_flags, uint32_t samples, uint64_t seed, float* d_out);
+/* The same computation on `n_threads` host threads (0: all cores) from the host description, into HOST memory out [height][width]: the
+ * reference's own CPU job, bit for bit what wtgpu_sensor_mask computes.  No device needed. */
+int wtgpu_sensor_mask_host(const wtgpu_scene* scene, const uint8_t* shape_flags, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out);
+
 /* Profiling aid: `repeats` launches of a streaming copy of n_dwords 32-bit words (one dword per lane, coalesced: the access width
  * of the SoA path state) with a known byte count, used to calibrate rocprofv3's FETCH_SIZE / WRITE_SIZE (tools/profile_round.sh). */
 int wtgpu_calibrate_copy(uint64_t n_dwords, int repeats);

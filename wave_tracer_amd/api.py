@@ -31,6 +31,11 @@ class TestHooks(C.Structure):      # wave_tracer_amd/csrc/wtgpu_test_hooks.h (no
     _fields_ = [("only_s", C.c_uint32), ("only_t", C.c_uint32), ("crop_of", C.c_uint32)]
 
 
+class SensorMaskSpec(C.Structure):   # wtgpu_sensor_mask_spec
+    _fields_ = [("present", C.c_int32), ("samples", C.c_uint32), ("regex", C.c_char_p), ("shape_flags", C.POINTER(C.c_uint8)),
+                ("n_shapes", C.c_uint32)]
+
+
 class SceneInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32), ("n_tris", C.c_uint32), ("n_edges", C.c_uint32),
                 ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("n_shapes", C.c_uint32), ("n_emitters", C.c_uint32),
@@ -55,7 +60,8 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_scene_upload", "wtgpu_render", "wtgpu_trace_rays", "wtgpu_traverse_cones", "wtgpu_get_counters",
            "wtgpu_reset_counters", "wtgpu_last_render_timings", "wtgpu_develop", "wtgpu_scene_destroy", "wtgpu_last_error",
            "wtgpu_scene_stats_json", "wtgpu_calibrate_copy", "wtgpu_render_async", "wtgpu_join", "wtgpu_query_regions", "wtgpu_render_progressive",
-           "wtgpu_cancel", "wtgpu_pause", "wtgpu_resume", "wtgpu_capture_intermediate", "wtgpu_comm_unique_id", "wtgpu_comm_create", "wtgpu_film_reduce", "wtgpu_comm_destroy", "wtgpu_scene_create_from_xml"]
+           "wtgpu_cancel", "wtgpu_pause", "wtgpu_resume", "wtgpu_capture_intermediate", "wtgpu_comm_unique_id", "wtgpu_comm_create", "wtgpu_film_reduce", "wtgpu_comm_destroy", "wtgpu_scene_create_from_xml",
+           "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
 CAPTURE_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_void_p)
 
@@ -113,6 +119,10 @@ def load_library():
     lib.wtgpu_test_utd_sums.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
     lib.wtgpu_test_profile_counters.argtypes = [vp, vp, u32]
     lib.wtgpu_test_bsdf_queries.argtypes = [vp, vp, vp, u32, i32, vp]
+    lib.wtgpu_scene_shape_id.argtypes = [vp, u32, C.POINTER(C.c_char_p)]
+    lib.wtgpu_scene_sensor_mask_spec.argtypes = [vp, C.POINTER(SensorMaskSpec)]
+    lib.wtgpu_sensor_mask.argtypes = [vp, vp, vp, u32, u64, vp]
+    lib.wtgpu_sensor_mask_host.argtypes = [vp, vp, u32, u64, u32, vp]
     lib.wtgpu_calibrate_copy.argtypes = [u64, i32]
     lib.wtgpu_get_counters.argtypes = [vp, C.POINTER(Counters)]
     lib.wtgpu_reset_counters.argtypes = [vp]
@@ -397,6 +407,64 @@ class Scene:
         _check(load_library().wtgpu_test_bsdf_queries(self._h, None, d_q.data_ptr(), n, int(form), out.data_ptr()))
         torch.cuda.synchronize(dev)
         return out.cpu().numpy().view(np.uint32)
+
+    @property
+    def shape_ids(self):
+        """The element id of every shape, in shape order (scene files: the element's `id`, "__unnamed_$<n>" for unnamed enabled top-level
+        elements, src/scene/loader/loader.cpp:131-133; bundled scenes and descriptions: empty strings)."""
+        lib, out = load_library(), []
+        for i in range(self.info.n_shapes):
+            p = C.c_char_p()
+            _check(lib.wtgpu_scene_shape_id(self._h, i, C.byref(p)))
+            out.append(p.value.decode())
+        return out
+
+    @property
+    def sensor_mask_spec(self):
+        """The scene file's <sensor_mask type="by-geometry"> (src/sensor/mask.cpp:76-108): None, or {"regex", "samples" (always 32: the
+        reference's loader drops the attribute), "shapes": uint8 numpy array, 1 where the shape's id matches the regex}."""
+        import numpy as np
+        s = SensorMaskSpec()
+        _check(load_library().wtgpu_scene_sensor_mask_spec(self._h, C.byref(s)))
+        if not s.present:
+            return None
+        flags = np.ctypeslib.as_array(s.shape_flags, (s.n_shapes,)).copy() if s.n_shapes else np.zeros(0, np.uint8)
+        return {"regex": s.regex.decode(), "samples": int(s.samples), "shapes": flags}
+
+    def _mask_args(self, samples, shapes):
+        import numpy as np
+        if samples is None:
+            spec = self.sensor_mask_spec
+            samples = spec["samples"] if spec else 32
+        if shapes is None:
+            return int(samples), None
+        flags = np.ascontiguousarray(np.asarray(shapes) != 0, dtype=np.uint8)
+        if flags.shape != (self.info.n_shapes,):
+            raise ValueError(f"shapes: one flag per shape expected ({self.info.n_shapes}), got shape {flags.shape}")
+        return int(samples), flags
+
+    def sensor_mask(self, samples=None, seed=1, shapes=None, stream=None):
+        """mask_t::create_mask on the scene's device (wtgpu_sensor_mask): an H x W float32 torch tensor, per pixel the share of `samples`
+        primary rays whose first hit is on a shape that does NOT match the mask.  samples: None = the scene file's (32).  shapes: None = the
+        scene file's flags, else one flag per shape (true = matches the regex: not counted).  Enqueued on `stream` (default: torch's current)."""
+        import torch
+        if self.device is None:
+            raise WtgpuError("sensor_mask: upload(device) first")
+        dev = torch.device("cuda", self.device)
+        n, flags = self._mask_args(samples, shapes)
+        out = torch.empty((self.height, self.width), dtype=torch.float32, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _check(load_library().wtgpu_sensor_mask(self._h, C.c_void_p(st) if st else None, None if flags is None else flags.ctypes.data, n, int(seed),
+                                                out.data_ptr()))
+        return out
+
+    def sensor_mask_host(self, samples=None, seed=1, shapes=None, threads=0):
+        """The same mask on host threads (wtgpu_sensor_mask_host; threads 0 = all cores), as numpy: bit for bit the device's."""
+        import numpy as np
+        n, flags = self._mask_args(samples, shapes)
+        out = np.zeros((self.height, self.width), np.float32)
+        _check(load_library().wtgpu_sensor_mask_host(self._h, None if flags is None else flags.ctypes.data, n, int(seed), int(threads), out.ctypes.data))
+        return out
 
     def profile_counters(self, n=8):
         """Test hook (wtgpu_test_hooks.h): the first n WTGPU_PROFILE scratch counters, accumulated since upload."""

@@ -222,7 +222,18 @@ void apply_opts(const scene_params_t& p, wt::integrator_opts_t& o);
 // Procedural stand-ins for the reference's Git-LFS assets that are absent from its checkout: `file` as written
 // in scenes/cornell-box/box.xml.  The stand-in comes with its own to_world (the asset's model units are unknown).  FALSE: no stand-in.
 bool asset_standin_mesh(const std::string& file, int mesh_detail, mesh_t& mesh, xform_t& to_world, bool& face_normals);
+// What a scene file says beyond the flattened scene: host-side state of the scene handle, NOT part of wt::scene_t (a file with a sensor mask
+// bakes to the same flattened scene as the same file without it)
+struct scene_file_extras_t {
+    std::vector<std::string> shape_ids;   // per shape: its element id; unnamed enabled top-level elements are "__unnamed_$<n>" (loader.cpp:131-133)
+    // <sensor_mask type="by-geometry"> of the perspective sensor (src/sensor/mask.cpp:76-108, src/sensor/perspective.cpp:98)
+    bool has_mask = false;
+    std::string mask_regex;               // mask_id_regex
+    uint32_t mask_samples = 32;           // always 32: the loader reads `samples` but never passes it on (mask.cpp:93,105-107)
+    std::vector<uint8_t> mask_flags;      // per shape: 1 = std::regex_match(id, mask_regex) (ECMAScript, whole id)
+};
 // minimal reader of the reference's XML scene format (host/xml_scene.cpp): `defines` = "name=value" (-D of the reference's CLI)
-void build_scene_from_xml(const std::string& path, const std::vector<std::string>& defines, const scene_params_t& p, scene_builder_t& b);
+void build_scene_from_xml(const std::string& path, const std::vector<std::string>& defines, const scene_params_t& p, scene_builder_t& b,
+                          scene_file_extras_t* extras = nullptr);
 
 }   // namespace wth

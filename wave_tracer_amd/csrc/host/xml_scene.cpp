@@ -23,7 +23,9 @@
 //     texture (constant, checkerboard, scale, transform, bitmap from PNG / PFM with filter, wrap modes and colour encoding);
 //     shape (rectangle, cube, sphere, cylinder, prism, lens, ply / obj: host/ply_loader.cpp, host/obj_loader.cpp) with general to_world
 //     transforms (matrix / rotate / scale / translate / lookat).
-//   Not handled: spatially varying emitter radiance textures (constant ones are), sensor masks.
+//   sensor_mask (by-geometry, in a perspective sensor; ignored with a warning in a virtual-plane one) and every shape's element id are kept
+//     beside the flattened scene (scene_file_extras_t): the mask does not change what the scene bakes to.
+//   Not handled: spatially varying emitter radiance textures (constant ones are).
 // Spectral resolution at bake time (as in host/scenes.cpp): composite BSDFs / spectra take the bin that contains the sensor's
 // sensitivity range; an emitter whose spectrum has no line-for-line overlap with the sensor's (a continuous spectrum against a
 // monochromatic sensor: the reference integrates it over a 2e-6 relative band, scene_build_sensor_sampling_data.cpp:55-60, ~1e-9
@@ -36,6 +38,7 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <regex>
 #include <sstream>
 #include <stdexcept>
 
@@ -643,8 +646,38 @@ struct loader_t {
     std::map<std::string, int> materials;
     std::string base_dir;   // directory of the scene file: relative asset paths resolve against it
     int mesh_detail = 1;    // tessellation of the procedural stand-ins for Git-LFS assets (scene_params_t::mesh_detail)
+    scene_file_extras_t extras;   // shape ids and the sensor mask: host state beside the flattened scene
 
     explicit loader_t(scene_builder_t& bb) : b(bb) {}
+
+    // mask_t::load (src/sensor/mask.cpp:76-108): type by-geometry, a non-empty mask_id_regex; `samples` is read but never reaches the mask
+    void read_sensor_mask(const xnode_t& m) {
+        if (m.get("type") != "by-geometry") throw std::runtime_error("(sensor mask loader) Unrecognized 'type'");
+        std::string regex;
+        for (auto& k : m.kids) {
+            const std::string name = k.get("name");
+            if (k.name == "string" && name == "mask_id_regex")
+                regex = k.get("value");
+            else if (k.name == "integer" && name == "samples")
+                (void)eval_number(k.get("value"));
+            else
+                std::fprintf(stderr, "wtgpu: (sensor mask loader) Unqueried node type %s (\"%s\")\n", k.name.c_str(), name.c_str());
+        }
+        if (regex.empty()) throw std::runtime_error("(sensor mask loader) expected 'mask_id_regex' regex expression to be provided");
+        extras.has_mask = true;
+        extras.mask_regex = regex;
+    }
+    // the regex is compiled once (std::regex: ECMAScript) and matched against every shape's whole id (mask.cpp:39,56)
+    void flag_masked_shapes() {
+        std::regex re;
+        try {
+            re = std::regex(extras.mask_regex);
+        } catch (const std::regex_error& e) {
+            throw std::runtime_error("(sensor mask loader) invalid 'mask_id_regex' \"" + extras.mask_regex + "\": " + e.what());
+        }
+        extras.mask_flags.clear();
+        for (const std::string& id : extras.shape_ids) extras.mask_flags.push_back(std::regex_match(id, re) ? 1 : 0);
+    }
 
     std::string subst(const std::string& v) const {
         std::string o;
@@ -1275,6 +1308,8 @@ struct loader_t {
             float tan_alpha = -1.f;
             if (const xnode_t* a = sensor->named("alpha")) tan_alpha = (float)std::tan(parse_dim(a->get("value"), DIM_ANGLE, "alpha"));
             b.set_sensor_virtual_plane(to_world(*sensor, {0, 1, 0}), parse_dim(e2[0], DIM_LENGTH, "extent"), parse_dim(e2[1], DIM_LENGTH, "extent"), W, H, tan_alpha);
+            // the virtual-plane loader reads no mask: the reference warns about the node and goes on without it
+            if (sensor->child("sensor_mask")) std::fprintf(stderr, "wtgpu: (virtual plane sensor loader) unqueried node type sensor_mask: ignored\n");
         } else if (stype == "perspective") {
             const xnode_t* fov = sensor->named("fov");
             if (!fov) throw std::runtime_error("perspective sensor: fov expected");
@@ -1290,6 +1325,7 @@ struct loader_t {
                 if (v == "x") fov_y = 2.0 * std::atan(std::tan(fov_y / 2) / (double(W) / double(H)));
             }
             b.set_sensor_perspective(to_world(*sensor, {0, 1, 0}), fov_y, W, H, pse, rto);
+            if (const xnode_t* m = sensor->child("sensor_mask")) read_sensor_mask(*m);
         } else
             throw std::runtime_error("sensor type \"" + stype + "\" is not supported");
         if (const xnode_t* r = film->named("rfilter_scale")) b.set_film_rfilter_scale((float)eval_number(r->get("value")));
@@ -1487,6 +1523,8 @@ struct loader_t {
                 } else
                     throw std::runtime_error("shape type \"" + type + "\" is not supported by the minimal reader");
                 const int shape = b.add_shape(mesh, M, mat, face_normals);
+                extras.shape_ids.resize(std::max(extras.shape_ids.size(), (size_t)shape + 1));
+                extras.shape_ids[shape] = element_id;
                 if (const xnode_t* em = n.child("emitter")) {   // area emitter on this shape (src/scene/shape.cpp:150-168)
                     if (em->get("type") != "area") throw std::runtime_error("(shape loader) emitter must be an area emitter");
                     const xnode_t* sp = em->named("radiance");
@@ -1533,6 +1571,7 @@ struct loader_t {
                 }
             }
         }
+        if (extras.has_mask) flag_masked_shapes();
         if (!n_emitters) throw std::runtime_error("(scene) no emitters overlap the sensor's sensitivity");
         std::stable_sort(emitter_keys.begin(), emitter_keys.end(), [](const emitter_key_t& x, const emitter_key_t& y) {
             return x.cls != y.cls ? x.cls < y.cls : x.cls == 0 ? x.id < y.id : x.index < y.index;
@@ -1551,7 +1590,8 @@ struct loader_t {
 
 // `defines`: "name=value" strings (the reference's -D command-line defines).  prm: res (if non-zero) becomes the define "res" unless
 // given explicitly; max_depth / fsd / mis / rr / force_ray_tracing override the integrator element; lut_*: table resolution.
-void build_scene_from_xml(const std::string& path, const std::vector<std::string>& defines, const scene_params_t& prm, scene_builder_t& b) {
+void build_scene_from_xml(const std::string& path, const std::vector<std::string>& defines, const scene_params_t& prm, scene_builder_t& b,
+                          scene_file_extras_t* extras) {
     loader_t L(b);
     for (auto& d : defines) {
         const size_t e = d.find('=');
@@ -1561,6 +1601,7 @@ void build_scene_from_xml(const std::string& path, const std::vector<std::string
     if (prm.res && !L.defs.count("res")) L.defs["res"] = std::to_string(prm.res);
     L.load(path, prm);
     b.finalize();
+    if (extras) *extras = std::move(L.extras);
 }
 
 }   // namespace wth

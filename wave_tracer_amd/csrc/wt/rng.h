@@ -50,6 +50,7 @@ enum rng_stream_e : uint32_t {
     STREAM_SENSOR_WALK = 1,   // sensor subpath
     STREAM_EMITTER_WALK = 2,  // emitter subpath
     STREAM_CONNECT = 16,      // + t*32 + s : one stream per (s,t) connection
+    STREAM_MASK = 0x80000000u,   // sensor masks (wtgpu_sensor_mask); far above every connection stream (bdpt.h: connect_stream)
 };
 
 struct sampler_t {

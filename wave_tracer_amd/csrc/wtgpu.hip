@@ -114,6 +114,10 @@ struct wtgpu_scene {
     void* capture_user = nullptr;
     uint32_t* query_scratch = nullptr;   // wtgpu_traverse_cones
     size_t query_scratch_bytes = 0;
+    wth::scene_file_extras_t file;       // shape ids and the sensor mask of a scene file: host state only, not part of the flattened scene
+    uint8_t* d_mask_flags = nullptr;     // wtgpu_sensor_mask: the shape flags of the last call on the device, and their pinned staging copy;
+    uint8_t* h_mask_flags = nullptr;     // both are reused once ev_mask (recorded behind that call's kernel) has passed
+    hipEvent_t ev_mask = nullptr;
     // WTGPU_TRACE_AB (diagnostic, tests/test_gpu_traversal.py): accumulated over the replayed rounds — milliseconds of k_trace_refill / k_trace_sm on the
     // same queue, words of their outputs that differ (traversal records + triangle lists + heavy-queue checksums), walks replayed
     double ab_ms[2] = {0, 0};
@@ -278,7 +282,7 @@ int wtgpu_scene_create_from_xml(const char* path, const char* const* defines, ui
             if (!defines[i]) return fail(WTGPU_ERR_INVALID, "null define");
             defs.emplace_back(defines[i]);
         }
-        wth::build_scene_from_xml(path, defs, p, *s->builder);
+        wth::build_scene_from_xml(path, defs, p, *s->builder, &s->file);
         finish_built_scene(s.get());
         *out = s.release();
         return WTGPU_OK;
@@ -1439,6 +1443,66 @@ int wtgpu_query_regions(wtgpu_scene* s, void* stream_, const float* d_cones, uin
     return WTGPU_OK;
 }
 
+// ---- sensor masks (include/wt/sensor/mask/mask.hpp, src/sensor/mask.cpp:28-108) ----------------------------------------------------------
+int wtgpu_scene_shape_id(const wtgpu_scene* s, uint32_t shape, const char** id) {
+    if (!s || !id) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (shape >= s->host.n_shapes) return fail(WTGPU_ERR_INVALID, "shape index out of range");
+    *id = shape < s->file.shape_ids.size() ? s->file.shape_ids[shape].c_str() : "";
+    return WTGPU_OK;
+}
+int wtgpu_scene_sensor_mask_spec(const wtgpu_scene* s, wtgpu_sensor_mask_spec* out) {
+    if (!s || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    out->present = s->file.has_mask ? 1 : 0;
+    out->samples = s->file.mask_samples;
+    out->regex = s->file.mask_regex.c_str();
+    out->shape_flags = s->file.has_mask && !s->file.mask_flags.empty() ? s->file.mask_flags.data() : nullptr;
+    out->n_shapes = s->host.n_shapes;
+    return WTGPU_OK;
+}
+// the flags a mask call uses (NULL: the scene file's), after the checks both forms share
+static int mask_flags_for(const wtgpu_scene* s, const uint8_t* shape_flags, uint32_t samples, const uint8_t** flags) {
+    if (s->host.sensor.type != SENSOR_PERSPECTIVE)
+        return fail(WTGPU_ERR_INVALID, "sensor masks need a perspective sensor (only the perspective loader reads a <sensor_mask>: src/sensor/perspective.cpp:98)");
+    if (samples == 0 || samples > 65536) return fail(WTGPU_ERR_INVALID, "sensor mask: 1 .. 65536 samples per pixel expected");
+    if (!shape_flags && !s->file.has_mask) return fail(WTGPU_ERR_INVALID, "the scene has no <sensor_mask>: pass one flag per shape");
+    *flags = shape_flags ? shape_flags : s->file.mask_flags.data();
+    return WTGPU_OK;
+}
+int wtgpu_sensor_mask(wtgpu_scene* s, void* stream_, const uint8_t* shape_flags, uint32_t samples, uint64_t seed, float* d_out) {
+    if (!s || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const uint8_t* flags = nullptr;
+    if (const int rc = mask_flags_for(s, shape_flags, samples, &flags)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    device_guard_t guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const size_t n = std::max<size_t>(1, s->host.n_shapes);
+    if (!s->ev_mask) {
+        uint8_t* d = nullptr;
+        if (const int rc = dmalloc(s, &d, n)) return rc;
+        HIP_CHECK(hipHostMalloc((void**)&s->h_mask_flags, n, hipHostMallocDefault));
+        HIP_CHECK(hipEventCreateWithFlags(&s->ev_mask, hipEventDisableTiming));
+        s->d_mask_flags = d;
+    } else
+        HIP_CHECK(hipEventSynchronize(s->ev_mask));   // the previous call's kernel has read the buffers
+    if (s->host.n_shapes) std::memcpy(s->h_mask_flags, flags, s->host.n_shapes);
+    HIP_CHECK(hipMemcpyAsync(s->d_mask_flags, s->h_mask_flags, n, hipMemcpyHostToDevice, stream));
+    const int e = sensor_mask_launch(s->dev, stream, s->d_mask_flags, samples, seed, d_out);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_sensor_mask: ") + hipGetErrorString((hipError_t)e));
+    HIP_CHECK(hipEventRecord(s->ev_mask, stream));
+    return WTGPU_OK;
+}
+int wtgpu_sensor_mask_host(const wtgpu_scene* s, const uint8_t* shape_flags, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out) {
+    if (!s || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const uint8_t* flags = nullptr;
+    if (const int rc = mask_flags_for(s, shape_flags, samples, &flags)) return rc;
+    try {
+        sensor_mask_host(s->host, flags, samples, seed, n_threads, out);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+
 int wtgpu_test_profile_counters(wtgpu_scene* s, unsigned long long* out, uint32_t n) {
     if (!s || !out || !s->uploaded || n > kProfSlots) return fail(WTGPU_ERR_INVALID, "wtgpu_test_profile_counters: uploaded scene, n <= kProfSlots");
     {
@@ -1525,6 +1589,11 @@ static void release_device(wtgpu_scene* s) {
     s->d_path_slices.clear();
     s->d_tri_class = nullptr;
     s->pend_cap = s->n_chunks = 0;
+    s->d_mask_flags = nullptr;   // (freed with dev_allocs)
+    if (s->h_mask_flags) (void)hipHostFree(s->h_mask_flags);
+    s->h_mask_flags = nullptr;
+    if (s->ev_mask) (void)hipEventDestroy(s->ev_mask);
+    s->ev_mask = nullptr;
     s->uploaded = false;
 }
 

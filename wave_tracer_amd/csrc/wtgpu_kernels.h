@@ -6,6 +6,7 @@
 //   kernels_path.hip    k_path_* (plt_path)
 //   kernels_connect.hip k_connect_* (strategy buckets, connections, MIS, film splat)
 //   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
+//   kernels_mask.hip    k_sensor_mask_wave / k_sensor_mask_lane: by-geometry sensor masks (not part of a render)
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -403,6 +404,10 @@ int test_fsd_apertures(const scene_t& sc, hipStream_t stream, const float* d_con
 int test_utd_sums(const scene_t& sc, hipStream_t stream, const float* d_queries, const uint32_t* d_ids, const uint32_t* d_n_ids, uint32_t n, uint32_t id_cap,
                   uint32_t utd_cap, uint32_t* d_recs, uint32_t* d_hdr, uint32_t* d_edges);
 int test_bsdf_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_queries, uint32_t n, int form, uint32_t* d_out);
+// kernels_mask.hip: by-geometry sensor masks (wtgpu_sensor_mask / wtgpu_sensor_mask_host).  shape_matches: one byte per shape, 1 = the id matches
+// the mask's regex.  The launch returns a hipError_t.
+int sensor_mask_launch(const scene_t& sc, hipStream_t stream, const uint8_t* d_shape_matches, uint32_t samples, uint64_t seed, float* d_out);
+void sensor_mask_host(const scene_t& sc, const uint8_t* shape_matches, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out);
 
 }   // namespace wtk
 using namespace wtk;

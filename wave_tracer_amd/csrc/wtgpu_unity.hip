@@ -7,3 +7,4 @@
 #include "kernels_path.hip"
 #include "kernels_connect.hip"
 #include "kernels_test.hip"
+#include "kernels_mask.hip"

@@ -194,3 +194,25 @@ def write_developed(out_dir, sensor_name, scene_name, developed, spe, stokes=1, 
             paths.append(os.path.join(out_dir, f"{sensor_name}_{suffix}.exr"))
             write_exr(paths[-1], planes[..., s], attrs)
     return paths
+
+
+def write_masked(out_dir, sensor_name, scene_name, tonemapped, mask, spe, renderer="wave_tracer_amd"):
+    """The masked copy of a TONEMAPPED film the reference's CLI writes for a sensor with a <sensor_mask> (src/main.cpp:315-326):
+    `<sensor>_tonemapped_masked.exr`, the tonemapped colour as it was before any watermark plus the mask (Scene.sensor_mask) as alpha —
+    a 1-component film becomes LA (channels Y, A), a colour film RGBA.  Attributes as write_developed's, `sensor` = `<sensor>_tonemapped`.
+    Returns the path."""
+    import os
+    a = np.asarray(tonemapped, dtype=np.float32)
+    if a.ndim == 2:
+        a = a[..., None]
+    H, W, C = a.shape
+    if C not in (1, 3):
+        raise ValueError("single-channel or RGB film expected")
+    m = np.asarray(mask, dtype=np.float32)
+    if m.shape != (H, W):
+        raise ValueError(f"mask: {H} x {W} expected, got {m.shape}")
+    film = sensor_name + "_tonemapped"
+    attrs = {"renderer": renderer, "scene": scene_name, "sensor": film, "samples": str(int(spe))}
+    path = os.path.join(out_dir, film + "_masked.exr")
+    write_exr(path, np.concatenate([a, m[..., None]], axis=-1), attrs, ["Y", "A"] if C == 1 else ["R", "G", "B", "A"])
+    return path

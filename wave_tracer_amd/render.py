@@ -43,6 +43,19 @@ def render(scene, spp, seed=1, device=0, sample_begin=0):
     return value.cpu().numpy(), weight.cpu().numpy(), light.cpu().numpy()
 
 
+def sensor_mask(scene, samples=None, seed=1, shapes=None, device=0):
+    """The scene's by-geometry sensor mask (mask_t::create_mask, src/sensor/mask.cpp:28-66) computed on one GPU, as an H x W float32 numpy
+    array — the alpha channel of imageio.write_masked.  Uploads the scene like render()."""
+    import torch
+    if scene.device is None:
+        scene.upload(device)
+    dev = torch.device("cuda", scene.device)
+    with torch.cuda.device(dev):
+        mask = scene.sensor_mask(samples, seed, shapes)
+        torch.cuda.synchronize(dev)
+    return mask.cpu().numpy()
+
+
 def shard_samples(spp, rank, world):
     """Sample-index sharding: rank r renders [r*spp/world, (r+1)*spp/world)."""
     b = (spp * rank) // world
