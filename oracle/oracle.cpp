@@ -528,7 +528,7 @@ int oracle_trace_rays(const void* scene_host, const float* rays, uint32_t n, flo
     return 0;
 }
 // The same queries through the device's 128-BYTE NODES (wt/bvh.h: bvh8_qnode_t, child boxes on a 16-bit grid over the scene, rounded outwards), built here
-// from the scene's nodes exactly as wtgpu.hip builds them at upload: what a closest-hit ray query / a cone query finds must not depend on the node source.
+// from the scene's nodes exactly as wtgpu_upload.hip builds them at upload: what a closest-hit ray query / a cone query finds must not depend on the node source.
 struct grid_scene_t {
     std::vector<bvh8_qnode_t> nodes;
     qgrid_t grid;

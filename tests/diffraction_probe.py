@@ -19,7 +19,7 @@ from oracle_util import load_oracle  # noqa: E402
 K_FSD_P0_SIGMA = np.float32(0.288675134594813 / 4)
 K_FSD_DEAD_RATIO = 1e-10
 K_FSD_MAX_EDGES = 4096
-UTD_CAP = 48                 # records per aperture in the UTD tests: the per-walk share of the device's wedge pool (wtgpu.hip: 48 per walk)
+UTD_CAP = 48                 # records per aperture in the UTD tests: the per-walk share of the device's wedge pool (wtgpu_upload.hip: 48 per walk)
 _INV_SQRT2 = 0.70710678118654752440
 PROBE_DIRS = np.array([[-_INV_SQRT2, -_INV_SQRT2], [-1, 0], [-_INV_SQRT2, _INV_SQRT2], [0, 1], [_INV_SQRT2, _INV_SQRT2], [1, 0],
                        [_INV_SQRT2, -_INV_SQRT2], [0, -1]], np.float32)

@@ -108,3 +108,44 @@ def test_minimal_reproducer_of_the_split_persistent_loop(tmp_path):
     a0 = next(i for i, l in enumerate(old) if "global_atomic_add" in l)
     r0 = next(i for i, l in enumerate(old) if "ds_read_b32" in l)
     print(f"k_old with this compiler: atomic in loop {lo[a0]}, load of the shared item in loop {lo[r0]} -> " + ("SPLIT (the round-5 hang)" if lo[a0] != lo[r0] else "one loop"))
+
+
+# ---- environment knobs -------------------------------------------------------------------------------------------------------------------------
+# What is not a knob of the host driver and may still be put into an environment: the library / data locations and the two switches of the
+# runtime-settings check (wtgpu_upload.hip); compile-time switches (-DWTGPU_...) are recognised by their use in the sources' #if lines.
+NOT_KNOBS = {"WTGPU_LIB", "WTGPU_DATA_DIR", "WTGPU_ALLOW_SLOW_RUNTIME", "WTGPU_QUIET"}
+ENV_USE = re.compile(r"""(?<!\w)(WTGPU_[A-Z0-9_]+)=(?!=)|["'](WTGPU_[A-Z0-9_]+)["']""")
+
+
+def _knob_names():
+    table = open(os.path.join(CSRC, "wtgpu_knobs.hip")).read()
+    names = set(re.findall(r'^\s*\{"(WTGPU_[A-Z0-9_]+)", K\(', table, re.M))          # the table's records
+    names |= set(re.findall(r'getenv\("(WTGPU_[A-Z0-9_]+)"\)', table))                 # the special cases beside it
+    return names
+
+
+def test_every_knob_a_tool_or_test_sets_is_in_the_knob_table():
+    """A WTGPU_* name that tests/, tools/, bench.py or the Python package put into an environment is a name read_knobs reads (wtgpu_knobs.hip: the
+    table and the special cases beside it), or one of the documented non-knobs: a tool that sets a knob nobody reads would measure nothing."""
+    knobs = _knob_names()
+    assert len(knobs) >= 40 and "WTGPU_GRID_CLS" in knobs and "WTGPU_STREAMS" in knobs, "the pattern no longer matches the knob table: update this test"
+    compile_time = set()
+    for path in glob.glob(os.path.join(CSRC, "**", "*.*"), recursive=True):
+        if path.endswith((".hip", ".h", ".cpp", ".c")):
+            for line in open(path, errors="replace"):
+                if line.lstrip().startswith("#") and re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                    compile_time |= set(re.findall(r"WTGPU_[A-Z0-9_]+", line))
+    files = [os.path.join(ROOT, "bench.py")] + glob.glob(os.path.join(ROOT, "wave_tracer_amd", "*.py"))
+    for d in ("tests", "tools"):
+        for ext in ("py", "sh"):
+            files += glob.glob(os.path.join(ROOT, d, "**", "*." + ext), recursive=True)
+    used, unknown = set(), []
+    for path in sorted(files):
+        for i, line in enumerate(open(path, errors="replace")):
+            for m in ENV_USE.finditer(line):
+                name = m.group(1) or m.group(2)
+                used.add(name)
+                if name not in knobs and name not in NOT_KNOBS and name not in compile_time:
+                    unknown.append(f"{os.path.relpath(path, ROOT)}:{i + 1}: {name}")
+    assert len(used & knobs) >= 10, "the pattern no longer finds the knobs the tests set: update this test"
+    assert not unknown, "set into an environment, read by nothing:\n" + "\n".join(unknown)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A/B micro-benchmark of the ADS query kernels (per-lane vs 8-lane-group): Mqueries/s on the bench geometry + parity vs the CPU
-checker.  usage (GPU box): python tools/bench_queries.py [n_rays]   — run twice, with and without WTGPU_RAYS_PER_LANE=1"""
+"""Micro-benchmark of the ADS ray-query kernel: Mqueries/s on the bench geometry + parity vs the CPU checker.
+usage (GPU box): python tools/bench_queries.py [n_rays]"""
 import os
 import sys
 import time
@@ -34,7 +34,7 @@ for rep in range(3):
     _check(lib.wtgpu_trace_rays(sc.handle, None, d_rays.data_ptr(), n, dist.data_ptr(), tuid.data_ptr(), bary.data_ptr(), front.data_ptr()))
     torch.cuda.synchronize()
     dt = time.time() - t
-    print(f"mode={'per-lane' if os.environ.get('WTGPU_RAYS_PER_LANE') else 'g8'} rep {rep}: {n / dt / 1e6:.1f} Mrays/s ({dt * 1e3:.1f} ms)")
+    print(f"rep {rep}: {n / dt / 1e6:.1f} Mrays/s ({dt * 1e3:.1f} ms)")
 m = 20000
 od, ot, ob, of = oracle_trace(sc, rays[:m])
 gd, gt = dist[:m].cpu().numpy(), tuid[:m].cpu().numpy().view(np.uint32)

@@ -359,7 +359,7 @@ constexpr uint32_t kLightMaxWalks = WTGPU_LIGHT_MAX_WALKS;
 // runs exactly those three stage bodies, round after round, with a block barrier where the stream order stood, until the queue is empty, `max_rounds`
 // are done, or a walk needs a stage this kernel does not hold — the wave-cooperative traversal (heavy queue), the whole-region edge walk (k_edges),
 // the Fraunhofer sampling passes: then it stops BEFORE that stage, says which (CTL_LIGHT_STOP), and the host continues that round with the ordinary
-// kernels (wtgpu.hip: render_finish_part).  Same stage code, same order per walk: the same results as rounds.
+// kernels (wtgpu.hip: finish_look).  Same stage code, same order per walk: the same results as rounds.
 // Between two stages of a light round: what the lanes of this block wrote must be read by the lanes of this block — ONE block, one CU, one XCD.
 // The block barrier orders the stores (written through to the XCD's L2) and an agent-scope ACQUIRE drops the CU's L1 lines that queue counters updated
 // by L2 atomics would otherwise be read from; the RELEASE half of __threadfence() — a write-back of the XCD's whole L2 (buffer_wbl2: microseconds,

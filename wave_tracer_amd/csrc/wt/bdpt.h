@@ -32,7 +32,7 @@ constexpr uint32_t kMaxVerts = 18;
 // loop is not what they lack) and the 32 more empty rounds per batch cost 2-4 % of a pass.  Kept at 96.
 // Round 6: no walk is dropped at 96 any more.  kMaxWalkIters is what the device driver launches WITHOUT LOOKING at most (and what its per-round
 // timing events are sized for); a batch whose round queue is not empty after that keeps getting rounds, eight at a time, until it is
-// (wtgpu.hip: render_finish_part), and the checker's loops run to kWalkIterLimit — a bound against a walk that never ends, 43 x the old cap, counted
+// (wtgpu.hip: finish_look), and the checker's loops run to kWalkIterLimit — a bound against a walk that never ends, 43 x the old cap, counted
 // like before if it is ever reached (walk_iteration_cap_hits; the full-size tests assert zero).
 #ifndef WT_MAX_WALK_ITERS
 #define WT_MAX_WALK_ITERS 96

@@ -218,7 +218,7 @@ struct grid_nodes_t {   // the 128-byte nodes on the scene grid
     }
 };
 // What a traversal that is not handed a node source reads: on the device the 128-byte nodes — stored BEHIND the scene's nodes in the same allocation,
-// followed by the grid (wtgpu.hip: upload_impl; a scene whose boxes the grid cannot enclose gets cell.x = 0 there, and its kernels the exact
+// followed by the grid (wtgpu_upload.hip: upload_scene_arrays; a scene whose boxes the grid cannot enclose gets cell.x = 0 there, and its kernels the exact
 // nodes: lane_nodes_usable) —, on the host the exact ones.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(WT_NO_QNODES)
 typedef grid_nodes_t lane_nodes_t;

@@ -1,4 +1,4 @@
-// wave_tracer_amd — what the kernel translation units (kernels_*.hip) and the host side (wtgpu.hip) share: the slice state, the launch block,
+// wave_tracer_amd — what the kernel translation units (kernels_*.hip) and the host side (wtgpu*.hip, wtgpu_host.h) share: the slice state, the launch block,
 // the device-side queue helpers and the kernels' declarations.  The kernels of one batch, in launch order:
 //   kernels_walk.hip    k_generate, k_interact (pass A, by material class), k_edges, k_interact_b (pass B)
 //   kernels_trace.hip   k_trace_refill, k_trace_heavy (+ the per-query kernels of the traversal parity tests, the PMC calibration copy)

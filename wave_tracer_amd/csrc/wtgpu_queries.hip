@@ -1,0 +1,151 @@
+// wave_tracer_amd — entry points that are not a render: ray / cone / region queries, by-geometry sensor masks, the probes of the kernel tests
+// (wtgpu_test_hooks.h), the PMC calibration copy, develop.
+#include "wtgpu_host.h"
+
+extern "C" {
+
+int wtgpu_trace_rays(wtgpu_scene* s, void* stream_, const float* d_rays, uint32_t n, float* d_dist, uint32_t* d_tuid, float* d_bary, uint32_t* d_front) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(k_trace_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, s->dev, d_rays, n, d_dist, d_tuid, d_bary, d_front);
+    HIP_CHECK(hipGetLastError());
+    return WTGPU_OK;
+}
+int wtgpu_traverse_cones(wtgpu_scene* s, void* stream_, const float* d_cones, uint32_t n, uint32_t cap, float* d_dist, uint32_t* d_flags,
+                         uint32_t* d_ntris, uint32_t* d_tris) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // scratch for the bounded lists (ids + distances), kept with the scene between calls
+    const size_t need = (size_t)n * kMaxConeTris * 4 * 2;
+    if (need > s->query_scratch_bytes) {
+        device_guard_t guard(s->device);
+        void* p = nullptr;
+        HIP_CHECK(hipMalloc(&p, need));
+        s->dev_allocs.push_back(p);   // (the old block, if any, is released with the scene)
+        s->query_scratch = static_cast<uint32_t*>(p);
+        s->query_scratch_bytes = need;
+    }
+    hipLaunchKernelGGL(k_traverse_cones, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, s->dev, d_cones, n, cap, d_dist, d_flags, d_ntris,
+                       d_tris, s->query_scratch);
+    HIP_CHECK(hipGetLastError());
+    return WTGPU_OK;
+}
+
+int wtgpu_query_regions(wtgpu_scene* s, void* stream_, const float* d_cones, uint32_t n, uint32_t edge_cap, float* d_dist, uint32_t* d_flags,
+                        uint32_t* d_primary, uint32_t* d_ntris, uint32_t* d_nedges, uint32_t* d_edges, float* d_flux) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    if (n == 0) return WTGPU_OK;
+    hipLaunchKernelGGL(k_query_regions, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream_), s->dev, d_cones, n, edge_cap, d_dist, d_flags, d_primary,
+                       d_ntris, d_nedges, d_edges, d_flux, s->slices[0].counters + kDroppedSlot);
+    HIP_CHECK(hipGetLastError());
+    return WTGPU_OK;
+}
+
+// ---- sensor masks (include/wt/sensor/mask/mask.hpp, src/sensor/mask.cpp:28-108) ----------------------------------------------------------
+int wtgpu_scene_shape_id(const wtgpu_scene* s, uint32_t shape, const char** id) {
+    if (!s || !id) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (shape >= s->host.n_shapes) return fail(WTGPU_ERR_INVALID, "shape index out of range");
+    *id = shape < s->file.shape_ids.size() ? s->file.shape_ids[shape].c_str() : "";
+    return WTGPU_OK;
+}
+int wtgpu_scene_sensor_mask_spec(const wtgpu_scene* s, wtgpu_sensor_mask_spec* out) {
+    if (!s || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    out->present = s->file.has_mask ? 1 : 0;
+    out->samples = s->file.mask_samples;
+    out->regex = s->file.mask_regex.c_str();
+    out->shape_flags = s->file.has_mask && !s->file.mask_flags.empty() ? s->file.mask_flags.data() : nullptr;
+    out->n_shapes = s->host.n_shapes;
+    return WTGPU_OK;
+}
+// the flags a mask call uses (NULL: the scene file's), after the checks both forms share
+static int mask_flags_for(const wtgpu_scene* s, const uint8_t* shape_flags, uint32_t samples, const uint8_t** flags) {
+    if (s->host.sensor.type != SENSOR_PERSPECTIVE)
+        return fail(WTGPU_ERR_INVALID, "sensor masks need a perspective sensor (only the perspective loader reads a <sensor_mask>: src/sensor/perspective.cpp:98)");
+    if (samples == 0 || samples > 65536) return fail(WTGPU_ERR_INVALID, "sensor mask: 1 .. 65536 samples per pixel expected");
+    if (!shape_flags && !s->file.has_mask) return fail(WTGPU_ERR_INVALID, "the scene has no <sensor_mask>: pass one flag per shape");
+    *flags = shape_flags ? shape_flags : s->file.mask_flags.data();
+    return WTGPU_OK;
+}
+int wtgpu_sensor_mask(wtgpu_scene* s, void* stream_, const uint8_t* shape_flags, uint32_t samples, uint64_t seed, float* d_out) {
+    if (!s || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const uint8_t* flags = nullptr;
+    if (const int rc = mask_flags_for(s, shape_flags, samples, &flags)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    device_guard_t guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const size_t n = std::max<size_t>(1, s->host.n_shapes);
+    if (!s->ev_mask) {
+        uint8_t* d = nullptr;
+        if (const int rc = dmalloc(s, &d, n)) return rc;
+        HIP_CHECK(hipHostMalloc((void**)&s->h_mask_flags, n, hipHostMallocDefault));
+        HIP_CHECK(hipEventCreateWithFlags(&s->ev_mask, hipEventDisableTiming));
+        s->d_mask_flags = d;
+    } else
+        HIP_CHECK(hipEventSynchronize(s->ev_mask));   // the previous call's kernel has read the buffers
+    if (s->host.n_shapes) std::memcpy(s->h_mask_flags, flags, s->host.n_shapes);
+    HIP_CHECK(hipMemcpyAsync(s->d_mask_flags, s->h_mask_flags, n, hipMemcpyHostToDevice, stream));
+    const int e = sensor_mask_launch(s->dev, stream, s->d_mask_flags, samples, seed, d_out);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_sensor_mask: ") + hipGetErrorString((hipError_t)e));
+    HIP_CHECK(hipEventRecord(s->ev_mask, stream));
+    return WTGPU_OK;
+}
+int wtgpu_sensor_mask_host(const wtgpu_scene* s, const uint8_t* shape_flags, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out) {
+    if (!s || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const uint8_t* flags = nullptr;
+    if (const int rc = mask_flags_for(s, shape_flags, samples, &flags)) return rc;
+    try {
+        sensor_mask_host(s->host, flags, samples, seed, n_threads, out);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+
+int wtgpu_test_fsd_apertures(wtgpu_scene* s, void* stream, const float* d_cones, const float* d_sk, const uint32_t* d_ids, const uint32_t* d_n_ids,
+                             uint32_t n, uint32_t id_cap, uint32_t pool_cap, uint32_t mode, uint32_t* d_hdr, float* d_segs) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    if (mode > 1 || id_cap == 0 || pool_cap == 0) return fail(WTGPU_ERR_INVALID, "wtgpu_test_fsd_apertures: mode 0 / 1, id_cap and pool_cap > 0");
+    HIP_CHECK((hipError_t)test_fsd_apertures(s->dev, static_cast<hipStream_t>(stream), d_cones, d_sk, d_ids, d_n_ids, n, id_cap, pool_cap, mode, d_hdr, d_segs));
+    return WTGPU_OK;
+}
+int wtgpu_test_utd_sums(wtgpu_scene* s, void* stream, const float* d_queries, const uint32_t* d_ids, const uint32_t* d_n_ids, uint32_t n, uint32_t id_cap,
+                        uint32_t utd_cap, uint32_t* d_recs, uint32_t* d_hdr, uint32_t* d_edges) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    if (id_cap == 0 || utd_cap == 0) return fail(WTGPU_ERR_INVALID, "wtgpu_test_utd_sums: id_cap and utd_cap > 0");
+    HIP_CHECK((hipError_t)test_utd_sums(s->dev, static_cast<hipStream_t>(stream), d_queries, d_ids, d_n_ids, n, id_cap, utd_cap, d_recs, d_hdr, d_edges));
+    return WTGPU_OK;
+}
+
+int wtgpu_test_bsdf_queries(wtgpu_scene* s, void* stream, const uint32_t* d_queries, uint32_t n, int form, uint32_t* d_out) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    if (form < -1 || form > (int)MAT_SURFACE_SPM) return fail(WTGPU_ERR_INVALID, "wtgpu_test_bsdf_queries: form -1, 0, 1 or 2");
+    HIP_CHECK((hipError_t)test_bsdf_queries(s->dev, static_cast<hipStream_t>(stream), d_queries, n, form, d_out));
+    return WTGPU_OK;
+}
+
+int wtgpu_calibrate_copy(uint64_t n_dwords, int repeats) {
+    uint32_t *in = nullptr, *out = nullptr;
+    HIP_CHECK(hipMalloc((void**)&in, n_dwords * 4));
+    HIP_CHECK(hipMalloc((void**)&out, n_dwords * 4));
+    HIP_CHECK(hipMemset(in, 1, n_dwords * 4));
+    for (int r = 0; r < repeats; ++r) hipLaunchKernelGGL(k_calib_copy, dim3(256 * 32), dim3(256), 0, 0, in, out, (size_t)n_dwords);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipFree(in));
+    HIP_CHECK(hipFree(out));
+    return WTGPU_OK;
+}
+
+int wtgpu_develop(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, float* out) {
+    if (!s || !value || !weight || !light || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const sensor_t& sn = s->host.sensor;
+    const double sl = spe > 0 ? 1.0 / double(spe) : 0.0;
+    for (size_t p = 0; p < (size_t)sn.width * sn.height; ++p)
+        for (uint32_t c = 0, P = film_planes(sn); c < P; ++c) {
+            const double w = weight[p];
+            const double v = w != 0 ? value[p * P + c] / w : 0.0;
+            out[p * P + c] = (float)(v + light[p * P + c] * sl);
+        }
+    return WTGPU_OK;
+}
+
+}   // extern "C"
