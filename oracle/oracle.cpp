@@ -29,6 +29,7 @@
 #include "../wave_tracer_amd/csrc/wt/path.h"
 #include "../wave_tracer_amd/csrc/wt/diffraction_probe.h"
 #include "../wave_tracer_amd/csrc/wt/bsdf_probe.h"
+#include "../wave_tracer_amd/csrc/wt/sources_probe.h"
 
 using namespace wt;
 
@@ -770,6 +771,88 @@ int oracle_material_record(const void* scene_host, uint32_t mat, void* out, uint
     const scene_t& sc = *static_cast<const scene_t*>(scene_host);
     if (mat >= sc.n_materials || size != sizeof(material_t)) return 1;
     memcpy(out, &sc.materials[mat], sizeof(material_t));
+    return 0;
+}
+
+// The emitter / sensor / wavenumber layer per query (wt/sources_probe.h: probe_source) with the layouts of wtgpu_test_source_queries: n x
+// kSourceProbeQueryWords query words, n x kSourceProbeWords output words.  1: an op, emitter index or tuid out of range (nothing is run).
+int oracle_source_queries(const void* scene_host, const uint32_t* queries, uint32_t n, uint32_t* out) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    for (uint32_t q = 0; q < n; ++q)
+        if (!source_probe_query_ok(sc, queries + (size_t)q * kSourceProbeQueryWords)) return 1;
+    for (uint32_t q = 0; q < n; ++q) probe_source(sc, queries + (size_t)q * kSourceProbeQueryWords, out + (size_t)q * kSourceProbeWords);
+    return 0;
+}
+// The baked records the f64 restatement of the source layer reads (tests/sources_probe.py): an emitter (emitter_t, sizeof bytes), the sensor
+// (sensor_t), an emitter's wavenumber distribution (kdist_t, then n floats of kdist_data from `offset`), the emitter-selection cdf, a shape
+// (shape_t) with its triangle cdf and tuids, a triangle's geometry (tri_geo_t) and shading data (tri_shade_t), the shape triangle index of
+// a tuid.  The words of a textured area emitter's tables come through oracle_texture_data (texture_data[tab ..)).
+// texture_t::f({uv, k}).x of a constant / checkerboard / bitmap texture in the checker's f32 (an input of the source layer: an area emitter's
+// radiance texture)
+float oracle_texture_spectral(const void* scene_host, uint32_t id, float u, float v, float k) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (id >= sc.n_textures) return std::numeric_limits<float>::quiet_NaN();
+    return texture_spectral_leaf(sc, (int)id, vec2{u, v}, k);
+}
+int oracle_emitter_record(const void* scene_host, uint32_t ei, void* out, uint32_t size) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (ei >= sc.n_emitters || size != sizeof(emitter_t)) return 1;
+    memcpy(out, &sc.emitters[ei], sizeof(emitter_t));
+    return 0;
+}
+int oracle_sensor_record(const void* scene_host, void* out, uint32_t size) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (size != sizeof(sensor_t)) return 1;
+    memcpy(out, &sc.sensor, sizeof(sensor_t));
+    return 0;
+}
+int oracle_kdist_record(const void* scene_host, uint32_t ei, void* out, uint32_t size) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (ei >= sc.n_emitters || size != sizeof(kdist_t)) return 1;
+    memcpy(out, &sc.kdists[sc.emitters[ei].k_dist], sizeof(kdist_t));
+    return 0;
+}
+// pdf knots (count), then cdf knots (count) of emitter ei's distribution; 2 * count floats
+int oracle_kdist_table(const void* scene_host, uint32_t ei, uint32_t n, float* out) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (ei >= sc.n_emitters) return 1;
+    const kdist_t& d = sc.kdists[sc.emitters[ei].k_dist];
+    if (d.discrete ? n != 0 : n != 2 * d.count) return 1;
+    memcpy(out, sc.kdist_data + d.offset, (size_t)n * sizeof(float));
+    return 0;
+}
+int oracle_emitter_cdf(const void* scene_host, uint32_t n, float* out) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (n != sc.n_emitters + 1) return 1;
+    memcpy(out, sc.emitter_cdf, (size_t)n * sizeof(float));
+    return 0;
+}
+int oracle_shape_record(const void* scene_host, uint32_t shape, void* out, uint32_t size) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (shape >= sc.n_shapes || size != sizeof(shape_t)) return 1;
+    memcpy(out, &sc.shapes[shape], sizeof(shape_t));
+    return 0;
+}
+// a shape's area cdf (tri_count + 1 floats) and the tuid of each of its triangles (tri_count words)
+int oracle_shape_tables(const void* scene_host, uint32_t shape, float* cdf, uint32_t* tuid) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (shape >= sc.n_shapes) return 1;
+    const shape_t& sh = sc.shapes[shape];
+    memcpy(cdf, sc.shape_tri_cdf + sh.tri_offset + shape, (size_t)(sh.tri_count + 1) * sizeof(float));
+    memcpy(tuid, sc.shape_tri_tuid + sh.tri_offset, (size_t)sh.tri_count * sizeof(uint32_t));
+    return 0;
+}
+// geo: a, b, c, n (12 floats); shade: n0, n1, n2, uv0, uv1, uv2, dpdu, has_uv (19 words); meta: shape_idx, shape_tri_idx
+int oracle_triangle_record(const void* scene_host, uint32_t tuid, float* geo, uint32_t* shade, uint32_t* meta) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    if (tuid >= sc.n_tris) return 1;
+    const tri_geo_t& g = sc.tri_geo[tuid];
+    const float gg[12] = {g.a.x, g.a.y, g.a.z, g.b.x, g.b.y, g.b.z, g.c.x, g.c.y, g.c.z, g.n.x, g.n.y, g.n.z};
+    memcpy(geo, gg, sizeof(gg));
+    static_assert(sizeof(tri_shade_t) == 19 * 4, "tri_shade_t: 19 words");
+    memcpy(shade, &sc.tri_shade[tuid], sizeof(tri_shade_t));
+    meta[0] = sc.tri_meta[tuid].shape_idx;
+    meta[1] = sc.tri_meta[tuid].shape_tri_idx;
     return 0;
 }
 

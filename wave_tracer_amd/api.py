@@ -119,6 +119,7 @@ def load_library():
     lib.wtgpu_test_utd_sums.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
     lib.wtgpu_test_profile_counters.argtypes = [vp, vp, u32]
     lib.wtgpu_test_bsdf_queries.argtypes = [vp, vp, vp, u32, i32, vp]
+    lib.wtgpu_test_source_queries.argtypes = [vp, vp, vp, u32, vp]
     lib.wtgpu_scene_shape_id.argtypes = [vp, u32, C.POINTER(C.c_char_p)]
     lib.wtgpu_scene_sensor_mask_spec.argtypes = [vp, C.POINTER(SensorMaskSpec)]
     lib.wtgpu_sensor_mask.argtypes = [vp, vp, vp, u32, u64, vp]
@@ -405,6 +406,21 @@ class Scene:
         d_q = torch.from_numpy(q.view(np.int32)).to(dev)
         out = torch.zeros((n, 48), dtype=torch.int32, device=dev)
         _check(load_library().wtgpu_test_bsdf_queries(self._h, None, d_q.data_ptr(), n, int(form), out.data_ptr()))
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy().view(np.uint32)
+
+    def source_queries(self, queries):
+        """Test hook (wtgpu_test_hooks.h): the emitter / sensor / wavenumber layer per query.  queries [n,24] u32 (wt/sources_probe.h) -> out
+        [n,80] u32 (f32 bits except the discrete words).  An op, emitter index or tuid out of range raises (WTGPU_ERR_INVALID)."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.device)
+        q = np.ascontiguousarray(queries, dtype=np.uint32)
+        n = q.shape[0]
+        assert q.shape == (n, 24)
+        d_q = torch.from_numpy(q.view(np.int32)).to(dev)
+        out = torch.zeros((n, 80), dtype=torch.int32, device=dev)
+        _check(load_library().wtgpu_test_source_queries(self._h, None, d_q.data_ptr(), n, out.data_ptr()))
         torch.cuda.synchronize(dev)
         return out.cpu().numpy().view(np.uint32)
 

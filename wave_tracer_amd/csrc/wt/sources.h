@@ -337,7 +337,8 @@ WT_HD wavenumber_sample_t kdist_sample(const scene_t& sc, const kdist_t& d, floa
         t = p0 > 0.f ? du / p0 : 0.f;
     else {
         const float disc = fmaxf_(0.f, p0 * p0 + 4.f * a * du);
-        t = 2.f * du / (p0 + sqrtf(disc));
+        const float den = p0 + sqrtf(disc);
+        t = den > 0.f ? 2.f * du / den : 0.f;   // (p0 = 0 and no mass to cover, e.g. u = 0 in a table that starts at density 0: 0 / 0)
     }
     t = clampf(t, 0.f, dk);
     const float k = d.kmin + (float(i) * dk + t);
@@ -481,7 +482,8 @@ WT_HD sensor_direct_sample_t sensor_sample_direct(const scene_t& sc, vec3 wp, fl
         const bool inside = dir_local.z > FLT_EPSILON && fp.x >= 0.f && fp.y >= 0.f && fp.x < float(s.width) && fp.y < float(s.height);
         const uint32_t ex = inside ? (uint32_t)fp.x : 0u, ey = inside ? (uint32_t)fp.y : 0u;
         const vec2 pixel_offset = vec2{fractf(fp.x), fractf(fp.y)} - vec2{.5f, .5f};
-        r.beam = make_backward_beam(s.position, wd, 1.f / recp_sa, k, persp_sourcing_geometry(s, k));
+        // (outside the film the importance is 0, not (1 / recp_sa) x 0: recp_sa = 0 for a point in the sensor's plane, and inf x 0 = NaN)
+        r.beam = make_backward_beam(s.position, wd, inside ? 1.f / recp_sa : 0.f, k, persp_sourcing_geometry(s, k));
         beam_scale(r.beam, recp_dist2 * (inside ? 1.f : 0.f));
         r.dpd = pd_discrete(1.f);
         r.element = {ex, ey, pixel_offset};

@@ -38,6 +38,11 @@ int wtgpu_test_utd_sums(wtgpu_scene* s, void* stream, const float* d_queries, co
  * dielectric, surface_spm): the class forms of the material-sorted interaction pass.  Material ids must be < the scene's material count (not
  * checked).  The CPU checker's counterpart (generic form only): oracle/oracle.cpp: oracle_bsdf_queries. */
 int wtgpu_test_bsdf_queries(wtgpu_scene* s, void* stream, const uint32_t* d_queries, uint32_t n, int form, uint32_t* d_out);
+/* Per-query entry point of the emitter / sensor / wavenumber layer (kernels_test.hip: k_test_sources; layouts: wt/sources_probe.h): n queries
+ * of 24 words, n x 80 output words, device pointers.  The queries are read back and checked first (this call waits for `stream`): an op
+ * outside the table, an emitter index >= the scene's count or a tuid >= its triangle count returns WTGPU_ERR_INVALID and launches nothing.
+ * The CPU checker's counterpart: oracle/oracle.cpp: oracle_source_queries. */
+int wtgpu_test_source_queries(wtgpu_scene* s, void* stream, const uint32_t* d_queries, uint32_t n, uint32_t* d_out);
 #ifdef __cplusplus
 }
 #endif
