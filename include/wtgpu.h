@@ -4,11 +4,13 @@
  *     scene_renderer_t::render()                    src/scene/render.cpp:381-579
  *       -> block_renderer_t -> integrator_t::integrate(ctx, block, pixel, spp)     src/scene/render.cpp:99-113,
  *                                                                                  include/wt/integrator/integrator.hpp:44-57
- * i.e. everything between "scene + ADS are built" and "film storage is developed".  The host keeps scene parsing,
- * film development/tonemapping and image I/O; it hands over a flattened scene description and gets back the
+ * i.e. everything between "scene + ADS are built" and "film storage is developed".  The host keeps scene parsing
+ * and image I/O; it hands over a flattened scene description and gets back the
  * three linear film accumulators  value = sum(w*v), weight = sum(w), light = sum(light-image splats), exactly the
  * quantities film_storage_t holds (include/wt/sensor/film/film_storage.hpp:196-252), from which
  *     pixel = value/weight + light/spe        (film_storage.hpp:256-287, src/scene/render.cpp:245-291).
+ * Development and tonemapping run on either side: on the device, where the films are (wtgpu_develop_device, wtgpu_tonemap_device: the
+ * host downloads a finished picture instead of three f64 accumulators), or on the host (wtgpu_develop, wtgpu_tonemap_host).
  *
  * The integrator is part of the flattened scene: plt_bdpt (src/integrator/plt_bdpt.cpp:43-148) or plt_path in either transport
  * direction (src/integrator/plt_path.cpp:39-50); polarimetric sensors get four Stokes planes per channel.
@@ -233,6 +235,49 @@ int wtgpu_last_render_timings(wtgpu_scene* scene, float out[12]);
 /* Host-side film development (render_context_t::develop, src/scene/render.cpp:245-291):
  * out[h][w][c] = value/weight (0 if weight==0) + light * (1/spe). */
 int wtgpu_develop(const wtgpu_scene* scene, const double* value, const double* weight, const double* light, uint64_t spe, float* out);
+
+/* The same development on the device, on `stream`: d_value / d_weight / d_light as wtgpu_render fills them, d_out [height][width][channels][stokes]
+ * f32 in DEVICE memory — bit for bit what wtgpu_develop computes from the downloaded films.  Needs an uploaded scene (WTGPU_ERR_INVALID
+ * otherwise); touches neither films nor counters. */
+int wtgpu_develop_device(wtgpu_scene* scene, void* stream, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe, float* d_out);
+
+/* Tonemapping (tonemap_t: include/wt/sensor/response/tonemap/tonemap.hpp, src/sensor/response/tonemap.cpp:29-106).
+ *   op    0 linear, 1 gamma: pow(clamp01(x), 1/gamma), 2 sRGB transfer of clamp01(x), 3 dB: clamp01((10 log10 x - db_min) / (db_max - db_min)), 0 for
+ *         x == 0, NaN for x < 0; 4 function (a user expression: read from scene files, refused by the tonemap calls)
+ *   mode  0 select (colour map for a 1-channel film, per channel for RGB), 1 normal (per channel; a single channel is repeated), 2 colourmap
+ *         (the value, or the BT.709 luminance of RGB, through the map)
+ * A colour map is a table of table_n (2 .. 1024) RGB f32 triples, sampled at v (table_n - 1) with linear interpolation.  The reference takes
+ * its maps from tinycolormap, which is absent from its checkout: their tables are not reproduced (the library tabulates `grey` and `turbo`).
+ *
+ * The <tonemap> of the scene file's <response> (tonemap_t::load, tonemap.cpp:127-176), kept beside the flattened scene, which it does not change.
+ * present = 0: the file has none (or there is no file) and op / mode are the response's defaults — sRGB / normal for an RGB film
+ * (src/sensor/response/RGB.cpp:91-93), linear / select for a monochromatic one (monochromatic.cpp:65-66); colourmap is then "Magma"
+ * (tonemap.hpp:80).  The strings are valid while the handle lives. */
+typedef struct wtgpu_tonemap_spec {
+    int32_t present, op, mode;
+    float gamma, db_min, db_max;
+    const char* colourmap;   /* the map's name as the file spells it */
+    const char* function;    /* op 4: the expression's text */
+} wtgpu_tonemap_spec;
+int wtgpu_scene_tonemap_spec(const wtgpu_scene* scene, wtgpu_tonemap_spec* out);
+typedef struct wtgpu_tonemap {
+    int32_t op, mode;
+    float gamma, db_min, db_max;
+    const float* table;      /* HOST pointer, copied before the call returns; may be NULL when the mode sends nothing through a map */
+    uint32_t table_n;
+} wtgpu_tonemap;
+/* Develops the planes of ONE Stokes component (plane index channel * stokes + stokes_component; < stokes of the scene, WTGPU_ERR_INVALID otherwise),
+ * tonemaps them and writes [height][width][3] pixels — [height][width][4] with d_mask (DEVICE, [height][width] f32, e.g. wtgpu_sensor_mask's
+ * result; may be NULL) as the fourth component — in `format`: 0 f32 (the alpha is the mask's bits), 1 8-bit, 2 16-bit codes (uint)(clamp01(x) max + 0.5),
+ * NaN = code 0 (the alpha is quantised the same way).  One kernel on `stream`; the developed values never reach memory.  d_out: DEVICE, aligned to
+ * 16 bytes.  tm = NULL: the scene's own spec; if that needs a colour map which is neither grey nor turbo the call fails and says to pass a
+ * table.  Needs an uploaded scene (WTGPU_ERR_INVALID otherwise); touches neither films nor counters. */
+int wtgpu_tonemap_device(wtgpu_scene* scene, void* stream, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                         const wtgpu_tonemap* tm, uint32_t stokes_component, const float* d_mask, uint32_t format, void* d_out);
+/* The same computation on `n_threads` host threads (0: all cores) from HOST films into HOST memory; mask: HOST, may be NULL.  No device needed.
+ * Bit for bit the device's wherever the operator calls no libm function (linear; the quantisation and the table lookup in every case). */
+int wtgpu_tonemap_host(const wtgpu_scene* scene, const double* value, const double* weight, const double* light, uint64_t spe,
+                       const wtgpu_tonemap* tm, uint32_t stokes_component, const float* mask, uint32_t format, uint32_t n_threads, void* out);
 
 void wtgpu_scene_destroy(wtgpu_scene* scene);
 const char* wtgpu_last_error(void);

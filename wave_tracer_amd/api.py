@@ -36,6 +36,21 @@ class SensorMaskSpec(C.Structure):   # wtgpu_sensor_mask_spec
                 ("n_shapes", C.c_uint32)]
 
 
+class TonemapSpec(C.Structure):      # wtgpu_tonemap_spec
+    _fields_ = [("present", C.c_int32), ("op", C.c_int32), ("mode", C.c_int32), ("gamma", C.c_float), ("db_min", C.c_float), ("db_max", C.c_float),
+                ("colourmap", C.c_char_p), ("function", C.c_char_p)]
+
+
+class Tonemap(C.Structure):          # wtgpu_tonemap
+    _fields_ = [("op", C.c_int32), ("mode", C.c_int32), ("gamma", C.c_float), ("db_min", C.c_float), ("db_max", C.c_float),
+                ("table", C.POINTER(C.c_float)), ("table_n", C.c_uint32)]
+
+
+TONEMAP_OPS = ["linear", "gamma", "sRGB", "dB", "function"]       # tonemap_e
+TONEMAP_MODES = ["select", "normal", "colourmap"]                 # tonemap_mode_e
+TONEMAP_FORMATS = {"f32": 0, "u8": 1, "u16": 2}
+
+
 class SceneInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32), ("n_tris", C.c_uint32), ("n_edges", C.c_uint32),
                 ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("n_shapes", C.c_uint32), ("n_emitters", C.c_uint32),
@@ -61,7 +76,8 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_reset_counters", "wtgpu_last_render_timings", "wtgpu_develop", "wtgpu_scene_destroy", "wtgpu_last_error",
            "wtgpu_scene_stats_json", "wtgpu_calibrate_copy", "wtgpu_render_async", "wtgpu_join", "wtgpu_query_regions", "wtgpu_render_progressive",
            "wtgpu_cancel", "wtgpu_pause", "wtgpu_resume", "wtgpu_capture_intermediate", "wtgpu_comm_unique_id", "wtgpu_comm_create", "wtgpu_film_reduce", "wtgpu_comm_destroy", "wtgpu_scene_create_from_xml",
-           "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host"]
+           "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host",
+           "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
 CAPTURE_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_void_p)
 
@@ -124,6 +140,10 @@ def load_library():
     lib.wtgpu_scene_sensor_mask_spec.argtypes = [vp, C.POINTER(SensorMaskSpec)]
     lib.wtgpu_sensor_mask.argtypes = [vp, vp, vp, u32, u64, vp]
     lib.wtgpu_sensor_mask_host.argtypes = [vp, vp, u32, u64, u32, vp]
+    lib.wtgpu_scene_tonemap_spec.argtypes = [vp, C.POINTER(TonemapSpec)]
+    lib.wtgpu_develop_device.argtypes = [vp, vp, vp, vp, vp, u64, vp]
+    lib.wtgpu_tonemap_device.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(Tonemap), u32, vp, u32, vp]
+    lib.wtgpu_tonemap_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(Tonemap), u32, vp, u32, u32, vp]
     lib.wtgpu_calibrate_copy.argtypes = [u64, i32]
     lib.wtgpu_get_counters.argtypes = [vp, C.POINTER(Counters)]
     lib.wtgpu_reset_counters.argtypes = [vp]
@@ -480,6 +500,91 @@ class Scene:
         n, flags = self._mask_args(samples, shapes)
         out = np.zeros((self.height, self.width), np.float32)
         _check(load_library().wtgpu_sensor_mask_host(self._h, None if flags is None else flags.ctypes.data, n, int(seed), int(threads), out.ctypes.data))
+        return out
+
+    @property
+    def tonemap_spec(self):
+        """The <tonemap> of the scene file's <response> (tonemap_t::load, src/sensor/response/tonemap.cpp:127-176) as a dict: present, op (linear |
+        gamma | sRGB | dB | function), mode (select | normal | colourmap), gamma, db_range, colourmap (the map's name), function.  present =
+        False (no node, or no file): the response's default — sRGB / normal for an RGB film, linear / select for a monochromatic one, map Magma."""
+        s = TonemapSpec()
+        _check(load_library().wtgpu_scene_tonemap_spec(self._h, C.byref(s)))
+        return {"present": bool(s.present), "op": TONEMAP_OPS[s.op], "mode": TONEMAP_MODES[s.mode], "gamma": float(s.gamma),
+                "db_range": (float(s.db_min), float(s.db_max)), "colourmap": s.colourmap.decode(), "function": s.function.decode()}
+
+    @staticmethod
+    def _tonemap_struct(tm):
+        """tm: None (the scene's own spec) or a dict like tonemap_spec's with an optional "table" ([n,3] f32) -> (wtgpu_tonemap or None, keepalive)."""
+        import numpy as np
+        if tm is None:
+            return None, None
+        table = tm.get("table")
+        tab = None if table is None else np.ascontiguousarray(table, dtype=np.float32)
+        if tab is not None and (tab.ndim != 2 or tab.shape[1] != 3):
+            raise ValueError(f"table: [n, 3] expected, got shape {tab.shape}")
+        db = tm.get("db_range", (0.0, 0.0))
+        st = Tonemap(TONEMAP_OPS.index(tm.get("op", "linear")), TONEMAP_MODES.index(tm.get("mode", "select")), float(tm.get("gamma", 2.2)),
+                     float(db[0]), float(db[1]), None if tab is None else tab.ctypes.data_as(C.POINTER(C.c_float)), 0 if tab is None else len(tab))
+        return st, tab
+
+    def _device_films(self, what, value, weight, light, mask=None):
+        """The device entry points read the films by their sizes: refuse tensors of another size, type or device before a kernel does."""
+        import torch
+        if self.device is None:
+            raise WtgpuError(f"{what}: upload(device) first")
+        n = self.width * self.height
+        for t, name, numel, dtype in ((value, "value", n * self.channels, torch.float64), (weight, "weight", n, torch.float64),
+                                      (light, "light", n * self.channels, torch.float64), (mask, "mask", n, torch.float32)):
+            if t is None and name == "mask":
+                continue
+            if not (t.is_cuda and t.device.index == self.device and t.dtype == dtype and t.numel() == numel and t.is_contiguous()):
+                raise ValueError(f"{what}: {name}: a contiguous {dtype} tensor of {numel} elements on cuda:{self.device} expected")
+        return torch.device("cuda", self.device)
+
+    def develop_device(self, value, weight, light, spe, stream=None):
+        """wtgpu_develop on the scene's device (wtgpu_develop_device): value / weight / light are the torch f64 films there; returns the developed
+        film as a torch f32 tensor shaped like `value`, bit for bit render.develop's.  Enqueued on `stream` (default: torch's current)."""
+        import torch
+        dev = self._device_films("develop_device", value, weight, light)
+        out = torch.empty(tuple(value.shape), dtype=torch.float32, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _check(load_library().wtgpu_develop_device(self._h, C.c_void_p(st) if st else None, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
+                                                   out.data_ptr()))
+        return out
+
+    def tonemap_device(self, value, weight, light, spe, tm=None, stokes_component=0, mask=None, fmt="f32", stream=None):
+        """Develops and tonemaps one Stokes component of the films on the scene's device in one kernel (wtgpu_tonemap_device).  tm: None = the
+        scene's own tonemap_spec, else a dict {op, mode, gamma, db_range, table} (table: [n,3] f32 colour map, imageio.colour_table).  mask: an
+        H x W f32 torch tensor on the device (sensor_mask) that becomes the alpha.  fmt: f32 | u8 | u16.  Returns a torch tensor H x W x 3 (x 4
+        with a mask) of float32 / uint8 / int16 (the 16-bit codes: view them as unsigned)."""
+        import torch
+        dev = self._device_films("tonemap_device", value, weight, light, mask)
+        st_tm, keep = self._tonemap_struct(tm)
+        dtype = {"f32": torch.float32, "u8": torch.uint8, "u16": torch.int16}[fmt]
+        out = torch.empty((self.height, self.width, 4 if mask is not None else 3), dtype=dtype, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _check(load_library().wtgpu_tonemap_device(self._h, C.c_void_p(st) if st else None, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
+                                                   None if st_tm is None else C.byref(st_tm), int(stokes_component),
+                                                   None if mask is None else mask.data_ptr(), TONEMAP_FORMATS[fmt], out.data_ptr()))
+        del keep
+        return out
+
+    def tonemap_host(self, value, weight, light, spe, tm=None, stokes_component=0, mask=None, fmt="f32", threads=0):
+        """The same computation on host threads from numpy films (wtgpu_tonemap_host; threads 0 = all cores): a numpy array H x W x 3 (x 4 with
+        a mask) of float32 / uint8 / uint16.  No device needed."""
+        import numpy as np
+        v = np.ascontiguousarray(value, dtype=np.float64)
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        l = np.ascontiguousarray(light, dtype=np.float64)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+        n = self.width * self.height
+        if v.size != n * self.channels or l.size != v.size or w.size != n or (m is not None and m.size != n):
+            raise ValueError("tonemap_host: films of the scene's size expected")
+        st_tm, keep = self._tonemap_struct(tm)
+        out = np.zeros((self.height, self.width, 4 if m is not None else 3), {"f32": np.float32, "u8": np.uint8, "u16": np.uint16}[fmt])
+        _check(load_library().wtgpu_tonemap_host(self._h, v.ctypes.data, w.ctypes.data, l.ctypes.data, int(spe), None if st_tm is None else C.byref(st_tm),
+                                                 int(stokes_component), None if m is None else m.ctypes.data, TONEMAP_FORMATS[fmt], int(threads), out.ctypes.data))
+        del keep
         return out
 
     def profile_counters(self, n=8):

@@ -231,6 +231,13 @@ struct scene_file_extras_t {
     std::string mask_regex;               // mask_id_regex
     uint32_t mask_samples = 32;           // always 32: the loader reads `samples` but never passes it on (mask.cpp:93,105-107)
     std::vector<uint8_t> mask_flags;      // per shape: 1 = std::regex_match(id, mask_regex) (ECMAScript, whole id)
+    // <tonemap> of the film's <response> (tonemap_t::load, src/sensor/response/tonemap.cpp:127-176); absent: the response's default
+    // (RGB: sRGB / normal, src/sensor/response/RGB.cpp:91-93; monochromatic: linear / select, monochromatic.cpp:65-66)
+    bool has_tonemap = false;
+    int32_t tonemap_op = 0, tonemap_mode = 0;          // wt/tonemap.h: tonemap_op_e, tonemap_mode_e
+    float tonemap_gamma = 2.2f, tonemap_db_min = 0.f, tonemap_db_max = 0.f;
+    std::string tonemap_colourmap = "Magma";           // tonemap_t::default_colourmap (tonemap.hpp:80); the name as the file spells it
+    std::string tonemap_function;                      // the `function` operator's expression (read, not evaluated)
 };
 // minimal reader of the reference's XML scene format (host/xml_scene.cpp): `defines` = "name=value" (-D of the reference's CLI)
 void build_scene_from_xml(const std::string& path, const std::vector<std::string>& defines, const scene_params_t& p, scene_builder_t& b,

@@ -23,8 +23,9 @@
 //     texture (constant, checkerboard, scale, transform, bitmap from PNG / PFM with filter, wrap modes and colour encoding);
 //     shape (rectangle, cube, sphere, cylinder, prism, lens, ply / obj: host/ply_loader.cpp, host/obj_loader.cpp) with general to_world
 //     transforms (matrix / rotate / scale / translate / lookat).
-//   sensor_mask (by-geometry, in a perspective sensor; ignored with a warning in a virtual-plane one) and every shape's element id are kept
-//     beside the flattened scene (scene_file_extras_t): the mask does not change what the scene bakes to.
+//   sensor_mask (by-geometry, in a perspective sensor; ignored with a warning in a virtual-plane one), every shape's element id and the
+//     response's <tonemap> (linear / gamma / sRGB / dB / function, mode, colourmap name, range, gamma) are kept beside the flattened scene
+//     (scene_file_extras_t): they do not change what the scene bakes to.
 //   Not handled: spatially varying emitter radiance textures (constant ones are).
 // Spectral resolution at bake time (as in host/scenes.cpp): composite BSDFs / spectra take the bin that contains the sensor's
 // sensitivity range; an emitter whose spectrum has no line-for-line overlap with the sensor's (a continuous spectrum against a
@@ -667,6 +668,58 @@ struct loader_t {
         extras.has_mask = true;
         extras.mask_regex = regex;
     }
+    // tonemap_t::load (src/sensor/response/tonemap.cpp:127-176): the operator, its mode, the colour map's name, the dB range, gamma and the
+    // user function's text, with the reference's messages; kept beside the flattened scene, which it does not change
+    void read_tonemap(const xnode_t& n) {
+        static const char* const ops[] = {"linear", "gamma", "sRGB", "dB", "function"};
+        static const char* const modes[] = {"select", "normal", "colourmap"};
+        const std::string type = n.get("type");
+        int op = -1;
+        for (int i = 0; i < 5; ++i)
+            if (type == ops[i]) op = i;
+        if (op < 0) throw std::runtime_error("(tonemap operator loader) Unrecognized 'type'");
+        int mode = 0;
+        std::string colourmap = "Magma", function;
+        bool have_range = false, have_function = false;
+        double db_min = 0, db_max = 0, gamma = 2.2;
+        for (auto& k : n.kids) {
+            const std::string name = k.get("name");
+            if (k.name == "string" && name == "mode") {
+                mode = -1;
+                for (int i = 0; i < 3; ++i)
+                    if (k.get("value") == modes[i]) mode = i;
+                if (mode < 0) throw std::runtime_error("(tonemap operator loader) Unrecognized value in node \"mode\"");
+            } else if (k.name == "string" && name == "colourmap")
+                colourmap = k.get("value");
+            else if (k.name == "range") {
+                if (have_range) throw std::runtime_error("(tonemap operator loader) Range already provided");
+                const std::string v = k.get("value");
+                const size_t sep = v.find("..");
+                if (sep == std::string::npos) throw std::runtime_error("(tonemap operator loader) (parse_range) malformed range expression, expected '<min>..<max>'");
+                db_min = eval_number(v.substr(0, sep));
+                db_max = eval_number(v.substr(sep + 2));
+                have_range = true;
+            } else if (k.name == "function") {
+                if (have_function) throw std::runtime_error("(tonemap operator loader) Function already provided");
+                function = k.get("value");
+                have_function = true;
+            } else if (k.name == "float" && name == "gamma")
+                gamma = eval_number(k.get("value"));
+            else
+                std::fprintf(stderr, "wtgpu: (tonemap operator loader) Unqueried node type %s (\"%s\")\n", k.name.c_str(), name.c_str());
+        }
+        if (op == 4 && !have_function) throw std::runtime_error("(tonemap operator loader) expected 'function' to be provided");
+        if (op == 3 && (!have_range || !((float)db_max - (float)db_min > 0.f))) throw std::runtime_error("(tonemap operator loader) expected valid 'db' range to be provided");
+        if (op == 1 && !(gamma > 0)) throw std::runtime_error("(tonemap operator loader) 'gamma' must be positive");
+        extras.has_tonemap = true;
+        extras.tonemap_op = op;
+        extras.tonemap_mode = mode;
+        extras.tonemap_gamma = (float)gamma;
+        extras.tonemap_db_min = (float)db_min;
+        extras.tonemap_db_max = (float)db_max;
+        extras.tonemap_colourmap = colourmap;
+        extras.tonemap_function = function;
+    }
     // the regex is compiled once (std::regex: ECMAScript) and matched against every shape's whole id (mask.cpp:39,56)
     void flag_masked_shapes() {
         std::regex re;
@@ -1299,6 +1352,7 @@ struct loader_t {
             band_hi = 720e-9;
         } else
             throw std::runtime_error("response type \"" + resp->get("type") + "\" is not supported");
+        if (const xnode_t* tm = resp->child("tonemap")) read_tonemap(*tm);
         const std::string stype = sensor->get("type");
         if (stype == "virtual_plane") {
             const xnode_t* ext = sensor->named("extent");

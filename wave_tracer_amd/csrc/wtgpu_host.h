@@ -6,7 +6,7 @@
 //   wtgpu_knobs.hip      the environment knobs: one table, read_knobs (wtgpu_knobs.h; plain C++)
 //   wtgpu_trace_ab.hip   WTGPU_TRACE_AB replay harness, the alternative forms of the per-lane traversal
 //   wtgpu_counters.hip   wtgpu_get_counters and its profile printers, reset
-//   wtgpu_queries.hip    ray / cone / region queries, sensor masks, the test probes, develop
+//   wtgpu_queries.hip    ray / cone / region queries, sensor masks, the test probes, develop and tonemap
 //   wtgpu_control.hip    cancel / pause / resume / capture / progressive render; the RCCL film reduction
 #pragma once
 #include <hip/hip_runtime.h>
@@ -104,6 +104,9 @@ struct wtgpu_scene {
     uint8_t* d_mask_flags = nullptr;     // wtgpu_sensor_mask: the shape flags of the last call on the device, and their pinned staging copy;
     uint8_t* h_mask_flags = nullptr;     // both are reused once ev_mask (recorded behind that call's kernel) has passed
     hipEvent_t ev_mask = nullptr;
+    float* d_tm_table = nullptr;         // wtgpu_tonemap_device: the colour table of the last call (kMaxTonemapTable entries), staged the same way
+    float* h_tm_table = nullptr;
+    hipEvent_t ev_tm = nullptr;
     // WTGPU_TRACE_AB (diagnostic, tests/test_gpu_traversal.py): accumulated over the replayed rounds — milliseconds of k_trace_refill / k_trace_sm on the
     // same queue, words of their outputs that differ (traversal records + triangle lists + heavy-queue checksums), walks replayed
     double ab_ms[2] = {0, 0};

@@ -7,6 +7,7 @@
 //   kernels_connect.hip k_connect_* (strategy buckets, connections, MIS, film splat)
 //   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
 //   kernels_mask.hip    k_sensor_mask_wave / k_sensor_mask_lane: by-geometry sensor masks (not part of a render)
+//   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -25,6 +26,9 @@
 #include "wt/path.h"
 
 using namespace wt;
+namespace wt {
+struct tonemap_args_t;   // wt/tonemap.h (kernels_develop.hip and the entry points that launch it)
+}
 
 namespace wtk {
 
@@ -409,6 +413,17 @@ int test_source_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d
 // the mask's regex.  The launch returns a hipError_t.
 int sensor_mask_launch(const scene_t& sc, hipStream_t stream, const uint8_t* d_shape_matches, uint32_t samples, uint64_t seed, float* d_out);
 void sensor_mask_host(const scene_t& sc, const uint8_t* shape_matches, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out);
+// kernels_develop.hip: film development and tonemapping (wtgpu_develop_device / wtgpu_tonemap_device / wtgpu_tonemap_host).  Films as wtgpu_render
+// fills them; `t.table` is a DEVICE pointer for the launch and a host pointer for the host twin; s: the Stokes component; d_mask: null, or one
+// f32 per pixel that becomes the fourth component.  per_pixel / lds_table: the measured alternatives (WTGPU_DEVELOP_PER_PIXEL, WTGPU_TONEMAP_LDS_TABLE).
+// The launches return a hipError_t.
+constexpr uint32_t kMaxTonemapTable = 1024;   // entries of a colour table
+int develop_launch(const sensor_t& sn, hipStream_t stream, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                   uint32_t per_pixel, float* d_out);
+int develop_tonemap_launch(const sensor_t& sn, hipStream_t stream, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                           const tonemap_args_t& t, uint32_t s, const float* d_mask, uint32_t format, uint32_t lds_table, void* d_out);
+void develop_tonemap_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, const tonemap_args_t& t, uint32_t s,
+                          const float* mask, uint32_t format, uint32_t n_threads, void* out);
 
 }   // namespace wtk
 using namespace wtk;

@@ -1,7 +1,8 @@
 // wave_tracer_amd — entry points that are not a render: ray / cone / region queries, by-geometry sensor masks, the probes of the kernel tests
-// (wtgpu_test_hooks.h), the PMC calibration copy, develop.
+// (wtgpu_test_hooks.h), the PMC calibration copy, develop and tonemap.
 #include "wtgpu_host.h"
 #include "wt/sources_probe.h"
+#include "wt/tonemap.h"
 
 extern "C" {
 
@@ -155,13 +156,139 @@ int wtgpu_calibrate_copy(uint64_t n_dwords, int repeats) {
 int wtgpu_develop(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, float* out) {
     if (!s || !value || !weight || !light || !out) return fail(WTGPU_ERR_INVALID, "null argument");
     const sensor_t& sn = s->host.sensor;
-    const double sl = spe > 0 ? 1.0 / double(spe) : 0.0;
+    const double sl = develop_scale(spe);
     for (size_t p = 0; p < (size_t)sn.width * sn.height; ++p)
-        for (uint32_t c = 0, P = film_planes(sn); c < P; ++c) {
-            const double w = weight[p];
-            const double v = w != 0 ? value[p * P + c] / w : 0.0;
-            out[p * P + c] = (float)(v + light[p * P + c] * sl);
+        for (uint32_t c = 0, P = film_planes(sn); c < P; ++c) out[p * P + c] = develop_plane(value[p * P + c], weight[p], light[p * P + c], sl);
+    return WTGPU_OK;
+}
+
+// ---- development and tonemapping where the films are (kernels_develop.hip; wt/tonemap.h) ---------------------------------------------------
+int wtgpu_scene_tonemap_spec(const wtgpu_scene* s, wtgpu_tonemap_spec* out) {
+    if (!s || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const wth::scene_file_extras_t& f = s->file;
+    const bool rgb = s->host.sensor.channels == 3;
+    out->present = f.has_tonemap ? 1 : 0;
+    // absent: sRGB / normal for an RGB response (RGB.cpp:91-93: create_sRGB), linear / select for a monochromatic one (monochromatic.cpp:65-66)
+    out->op = f.has_tonemap ? f.tonemap_op : rgb ? TM_SRGB : TM_LINEAR;
+    out->mode = f.has_tonemap ? f.tonemap_mode : rgb ? TM_NORMAL : TM_SELECT;
+    out->gamma = f.tonemap_gamma;
+    out->db_min = f.tonemap_db_min;
+    out->db_max = f.tonemap_db_max;
+    out->colourmap = f.tonemap_colourmap.c_str();
+    out->function = f.tonemap_function.c_str();
+    return WTGPU_OK;
+}
+
+// the polynomial fit of the Turbo map imageio.colourmap evaluates, and the identity: the two maps the library can tabulate itself
+static void builtin_table(bool turbo, std::vector<float>& tab) {
+    const uint32_t n = 256;
+    tab.resize(3 * n);
+    static const double c4[3][4] = {{.13572138, 4.61539260, -42.66032258, 132.13108234}, {.09140261, 2.19418839, 4.84296658, -14.18503333}, {.10667330, 12.64194608, -60.58204836, 110.36276771}};
+    static const double c2[3][2] = {{-152.94239396, 59.28637943}, {4.27729857, 2.82956604}, {-89.90310912, 27.34824973}};
+    for (uint32_t i = 0; i < n; ++i) {
+        const double v = double(i) / double(n - 1), v2 = v * v, v3 = v2 * v;
+        for (int k = 0; k < 3; ++k) {
+            const double x = c4[k][0] + c4[k][1] * v + c4[k][2] * v2 + c4[k][3] * v3 + c2[k][0] * (v2 * v2) + c2[k][1] * (v3 * v2);
+            tab[3 * i + k] = turbo ? (float)std::min(1.0, std::max(0.0, x)) : (float)v;
         }
+    }
+}
+static bool same_name(const std::string& a, const char* b) {
+    if (a.size() != std::strlen(b)) return false;
+    for (size_t i = 0; i < a.size(); ++i)
+        if (std::tolower((unsigned char)a[i]) != b[i]) return false;
+    return true;
+}
+// The operator a tonemap call uses after the checks both forms share: `tm` (NULL: the scene's own spec, whose map must be one the library can
+// tabulate), the Stokes component, the format.  args.table points at the caller's table or into `own` (host memory), or is null when the mode
+// sends nothing through a map.
+static int tonemap_args_for(const wtgpu_scene* s, const wtgpu_tonemap* tm, uint32_t stokes_component, uint32_t format, tonemap_args_t& args, std::vector<float>& own) {
+    const sensor_t& sn = s->host.sensor;
+    if (sn.channels != 1 && sn.channels != 3) return fail(WTGPU_ERR_INVALID, "tonemap: a film of 1 or 3 channels expected");
+    if (stokes_component >= film_stokes(sn))
+        return fail(WTGPU_ERR_INVALID, "tonemap: stokes_component " + std::to_string(stokes_component) + " out of range (the film has " + std::to_string(film_stokes(sn)) + ")");
+    if (format > TM_U16) return fail(WTGPU_ERR_INVALID, "tonemap: format 0 (f32), 1 (u8) or 2 (u16) expected");
+    wtgpu_tonemap_spec spec{};
+    (void)wtgpu_scene_tonemap_spec(s, &spec);
+    const int32_t op = tm ? tm->op : spec.op, mode = tm ? tm->mode : spec.mode;
+    const float gamma = tm ? tm->gamma : spec.gamma, db_min = tm ? tm->db_min : spec.db_min, db_max = tm ? tm->db_max : spec.db_max;
+    if (op == TM_FUNCTION) return fail(WTGPU_ERR_INVALID, "tonemap: the 'function' operator is not supported (the expression is read from the scene file, not evaluated)");
+    if (op < TM_LINEAR || op > TM_FUNCTION) return fail(WTGPU_ERR_INVALID, "tonemap: operator 0 (linear), 1 (gamma), 2 (sRGB) or 3 (dB) expected");
+    if (mode < TM_SELECT || mode > TM_COLOURMAP) return fail(WTGPU_ERR_INVALID, "tonemap: mode 0 (select), 1 (normal) or 2 (colourmap) expected");
+    if (op == TM_GAMMA && !(gamma > 0.f)) return fail(WTGPU_ERR_INVALID, "(tonemap operator loader) 'gamma' must be positive");
+    if (op == TM_DB && !(db_max - db_min > 0.f)) return fail(WTGPU_ERR_INVALID, "(tonemap operator loader) expected valid 'db' range to be provided");
+    args.op = op;
+    args.mode = mode;
+    args.inv_gamma = 1.f / gamma;
+    args.db_min = db_min;
+    args.db_len = db_max - db_min;
+    args.table = nullptr;
+    args.table_n = 0;
+    if (!tm_uses_map(mode, sn.channels)) return WTGPU_OK;
+    if (tm && tm->table) {
+        if (tm->table_n < 2 || tm->table_n > kMaxTonemapTable) return fail(WTGPU_ERR_INVALID, "tonemap: a colour table of 2 .. " + std::to_string(kMaxTonemapTable) + " RGB entries expected");
+        args.table = tm->table;
+        args.table_n = tm->table_n;
+        return WTGPU_OK;
+    }
+    if (tm) return fail(WTGPU_ERR_INVALID, "tonemap: this mode maps the film through a colour table: pass one");
+    const bool turbo = same_name(s->file.tonemap_colourmap, "turbo");
+    if (!turbo && !same_name(s->file.tonemap_colourmap, "grey"))
+        return fail(WTGPU_ERR_INVALID, "tonemap: the scene's colour map \"" + s->file.tonemap_colourmap + "\" is not one the library tabulates (grey, turbo): pass a table");
+    builtin_table(turbo, own);
+    args.table = own.data();
+    args.table_n = (uint32_t)(own.size() / 3);
+    return WTGPU_OK;
+}
+
+int wtgpu_develop_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe, float* d_out) {
+    if (!s || !d_value || !d_weight || !d_light || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    device_guard_t guard(s->device);
+    const int e = develop_launch(s->host.sensor, static_cast<hipStream_t>(stream_), d_value, d_weight, d_light, spe, s->knobs.develop_per_pixel, d_out);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_develop: ") + hipGetErrorString((hipError_t)e));
+    return WTGPU_OK;
+}
+int wtgpu_tonemap_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe, const wtgpu_tonemap* tm,
+                         uint32_t stokes_component, const float* d_mask, uint32_t format, void* d_out) {
+    if (!s || !d_value || !d_weight || !d_light || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    tonemap_args_t args{};
+    std::vector<float> own;
+    if (const int rc = tonemap_args_for(s, tm, stokes_component, format, args, own)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    if ((uintptr_t)d_out % 16) return fail(WTGPU_ERR_INVALID, "tonemap: d_out must be aligned to 16 bytes");
+    device_guard_t guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (args.table) {   // the table goes to the device behind everything already on `stream`, through a pinned copy made before the call returns
+        const size_t bytes = (size_t)kMaxTonemapTable * 3 * sizeof(float);
+        if (!s->ev_tm) {
+            float* d = nullptr;
+            if (const int rc = dmalloc(s, &d, (size_t)kMaxTonemapTable * 3)) return rc;
+            HIP_CHECK(hipHostMalloc((void**)&s->h_tm_table, bytes, hipHostMallocDefault));
+            HIP_CHECK(hipEventCreateWithFlags(&s->ev_tm, hipEventDisableTiming));
+            s->d_tm_table = d;
+        } else
+            HIP_CHECK(hipEventSynchronize(s->ev_tm));   // the previous call's kernel has read the buffers
+        std::memcpy(s->h_tm_table, args.table, (size_t)args.table_n * 3 * sizeof(float));
+        HIP_CHECK(hipMemcpyAsync(s->d_tm_table, s->h_tm_table, (size_t)args.table_n * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        args.table = s->d_tm_table;
+    }
+    const int e = develop_tonemap_launch(s->host.sensor, stream, d_value, d_weight, d_light, spe, args, stokes_component, d_mask, format, s->knobs.tonemap_lds_table, d_out);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_develop_tonemap: ") + hipGetErrorString((hipError_t)e));
+    if (args.table) HIP_CHECK(hipEventRecord(s->ev_tm, stream));
+    return WTGPU_OK;
+}
+int wtgpu_tonemap_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_tonemap* tm,
+                       uint32_t stokes_component, const float* mask, uint32_t format, uint32_t n_threads, void* out) {
+    if (!s || !value || !weight || !light || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    tonemap_args_t args{};
+    std::vector<float> own;
+    if (const int rc = tonemap_args_for(s, tm, stokes_component, format, args, own)) return rc;
+    try {
+        develop_tonemap_host(s->host.sensor, value, weight, light, spe, args, stokes_component, mask, format, n_threads, out);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
     return WTGPU_OK;
 }
 

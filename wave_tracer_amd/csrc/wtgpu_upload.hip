@@ -310,6 +310,11 @@ void release_device(wtgpu_scene* s) {
     s->h_mask_flags = nullptr;
     if (s->ev_mask) (void)hipEventDestroy(s->ev_mask);
     s->ev_mask = nullptr;
+    s->d_tm_table = nullptr;     // (freed with dev_allocs)
+    if (s->h_tm_table) (void)hipHostFree(s->h_tm_table);
+    s->h_tm_table = nullptr;
+    if (s->ev_tm) (void)hipEventDestroy(s->ev_tm);
+    s->ev_tm = nullptr;
     s->uploaded = false;
 }
 

@@ -52,6 +52,14 @@ def colourmap(v, name="turbo"):
     return np.clip(np.stack(rgb, axis=-1), 0.0, 1.0)
 
 
+def colour_table(name, n=256):
+    """A colour map as the table Scene.tonemap_device / tonemap_host take: n x 3 float32, entry i = colourmap(i / (n - 1), name).
+    'grey' or 'turbo' (the polynomial fit above; tinycolormap's tables are not reproduced)."""
+    if n < 2:
+        raise ValueError("a colour table needs at least 2 entries")
+    return colourmap(np.arange(n, dtype=np.float64) / (n - 1), name.lower()).astype(np.float32)
+
+
 def tonemap(img, op="sRGB", mode="select", gamma=2.2, db_range=(-60.0, 0.0), cmap="turbo"):
     """tonemap_t::operator() on a developed film [H,W,1] or [H,W,3] -> RGB in [0,1].
     op: linear | gamma | sRGB | dB;  mode: select (colour map for monochrome, per channel for RGB) | normal | colourmap."""

@@ -105,7 +105,7 @@ def render_with_preview(scene, spp, preview, seed=1, chunk_spp=8, preview_id="se
     """Renders `spp` samples per element in chunks (wtgpu_render_progressive) and pushes the developed partial film to `preview` as the
     render advances (src/scene/render.cpp:306-368).  Needs a GPU.  Returns (value, weight, light) numpy films."""
     import torch
-    from .render import alloc_films, develop
+    from .render import alloc_films, develop_device
     if scene.device is None:
         scene.upload(device)
     dev = torch.device("cuda", device)
@@ -114,10 +114,8 @@ def render_with_preview(scene, spp, preview, seed=1, chunk_spp=8, preview_id="se
 
     def on_progress(done, total):
         if preview.available(preview_id) or done == total:
-            torch.cuda.synchronize(dev)
-            v, w, l = (t.cpu().numpy() for t in films)
             per_elem = max(1, done // (scene.width * scene.height))
-            img = develop(scene, v, w, l, per_elem)
+            img = develop_device(scene, *films, per_elem, stream)   # developed on the device: only the f32 film is downloaded
             stokes = int(scene.info.stokes)
             # polarimetric films are [H][W][channels][4 Stokes components]: the viewer shows the intensity plane, like the reference's preview
             img = img.reshape(scene.height, scene.width, -1, stokes)[..., 0] if stokes > 1 else img.reshape(scene.height, scene.width, -1)

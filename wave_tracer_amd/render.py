@@ -29,6 +29,15 @@ def develop(scene, value, weight, light, spe):
     return out
 
 
+def develop_device(scene, value, weight, light, spe, stream=None):
+    """develop() where the films are: value / weight / light are the torch f64 films on the scene's device (alloc_films); returns the developed
+    film as a numpy f32 array, bit for bit develop()'s.  Only the f32 result crosses to the host: half the bytes of one of the two f64 plane films."""
+    import torch
+    out = scene.develop_device(value, weight, light, spe, stream)
+    torch.cuda.synchronize(out.device)
+    return out.cpu().numpy()
+
+
 def render(scene, spp, seed=1, device=0, sample_begin=0):
     """Renders `spp` samples per element on one GPU; returns (value, weight, light) as numpy f64 arrays."""
     import torch
