@@ -279,6 +279,41 @@ int wtgpu_tonemap_device(wtgpu_scene* scene, void* stream, const double* d_value
 int wtgpu_tonemap_host(const wtgpu_scene* scene, const double* value, const double* weight, const double* light, uint64_t spe,
                        const wtgpu_tonemap* tm, uint32_t stokes_component, const float* mask, uint32_t format, uint32_t n_threads, void* out);
 
+/* Film statistics: range, histogram and sum of the developed planes of ONE Stokes component — what choosing a dB range or an exposure needs,
+ * and the distribution of received power over a coverage map — without the developed film leaving the device.
+ *   planes   the film's channels (plane c: the developed value of film plane c * stokes + stokes_component, bit for bit wtgpu_develop's), plus one
+ *            with flag 2 LUMINANCE (3-channel films only): the BT.709 luminance max(0, .2126 r + .7152 g + .0722 b) of the three, as the tonemap's
+ *            colourmap mode computes it.  Flag 1 ABS: every element is |x| (the signed Stokes components Q / U / V).
+ *   members  all elements, or with a mask ([height][width] f32, e.g. wtgpu_sensor_mask's result) those of the pixels where mask > 0.
+ *   classes  a member is exactly one of: NaN; x < 0; x == 0; 0 < x < edge[0] (below); x >= edge[bins] (above); bin i with edge[i] <= x < edge[i+1].
+ *   edges    bins + 1 strictly increasing f32 thresholds in x's own scale, computed once in f64 and rounded: scale 0 linear
+ *            lo + i (hi - lo) / bins, scale 1 dB 10^((lo + i (hi - lo) / bins) / 10) with lo / hi in dB.  bins = 0: the one edge of lo.
+ *   record   n members; min / max / min_positive over the members that are not NaN (NaN if there is none; -0 sorts below +0); sum in f64 over the
+ *            same members in one fixed order (chunks of 256 in row-major order, each reduced pairwise at distances 128, 64 .. 1, the chunk
+ *            sums reduced the same way), so device and host agree on every field bit for bit.
+ * Errors (WTGPU_ERR_INVALID with a message): stokes_component >= the film's stokes, bins > 4096, lo >= hi with bins > 0 (or a value that is not
+ * finite), LUMINANCE on a film that is not 3-channel, unknown scale or flags, edges that rounding made equal. */
+typedef struct wtgpu_film_stats_spec {
+    uint32_t stokes_component, scale /* 0 linear, 1 dB */, bins /* 0 .. 4096 */, flags /* 1 ABS, 2 LUMINANCE */;
+    float lo, hi;
+} wtgpu_film_stats_spec;
+typedef struct wtgpu_film_stats {
+    uint64_t n, n_nan, n_negative, n_zero, n_below, n_above;
+    float min, max, min_positive, pad;
+    double sum;
+} wtgpu_film_stats;
+/* the edge table of a spec: edges[bins + 1] (needs no scene; checks what it can of the spec) */
+int wtgpu_film_stats_edges(const wtgpu_film_stats_spec* spec, float* edges);
+/* On the device, on `stream`: one pass over d_value / d_weight / d_light (as wtgpu_render fills them) that develops in registers, then a small
+ * kernel and the copy of the result, for which the call waits: out[planes] and hist[planes][bins] are HOST memory (hist may be NULL if bins == 0).
+ * d_mask: DEVICE, may be NULL.  Needs an uploaded scene (WTGPU_ERR_INVALID otherwise); its scratch memory is allocated at the first call and
+ * freed with the scene; touches neither films nor counters. */
+int wtgpu_film_stats_device(wtgpu_scene* scene, void* stream, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                            const wtgpu_film_stats_spec* spec, const float* d_mask, wtgpu_film_stats* out, uint64_t* hist);
+/* The same on `n_threads` host threads (0: all cores) from HOST films; the result does not depend on n_threads.  No device needed. */
+int wtgpu_film_stats_host(const wtgpu_scene* scene, const double* value, const double* weight, const double* light, uint64_t spe,
+                          const wtgpu_film_stats_spec* spec, const float* mask, uint32_t n_threads, wtgpu_film_stats* out, uint64_t* hist);
+
 void wtgpu_scene_destroy(wtgpu_scene* scene);
 const char* wtgpu_last_error(void);
 const char* wtgpu_scene_stats_json(const wtgpu_scene* scene);

@@ -1,6 +1,7 @@
 """ctypes binding of the C-ABI in include/wtgpu.h (libwtgpu.so).  No compute happens in Python."""
 import ctypes as C
 import json
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,6 +47,18 @@ class Tonemap(C.Structure):          # wtgpu_tonemap
                 ("table", C.POINTER(C.c_float)), ("table_n", C.c_uint32)]
 
 
+class FilmStatsSpec(C.Structure):    # wtgpu_film_stats_spec
+    _fields_ = [("stokes_component", C.c_uint32), ("scale", C.c_uint32), ("bins", C.c_uint32), ("flags", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class FilmStats(C.Structure):        # wtgpu_film_stats
+    _fields_ = [("n", C.c_uint64), ("n_nan", C.c_uint64), ("n_negative", C.c_uint64), ("n_zero", C.c_uint64), ("n_below", C.c_uint64), ("n_above", C.c_uint64),
+                ("min", C.c_float), ("max", C.c_float), ("min_positive", C.c_float), ("pad", C.c_float), ("sum", C.c_double)]
+
+
+FILM_STATS_SCALES = ["linear", "dB"]
+FILM_STATS_ABS, FILM_STATS_LUMINANCE = 1, 2
+FILM_STATS_MAX_BINS = 4096
 TONEMAP_OPS = ["linear", "gamma", "sRGB", "dB", "function"]       # tonemap_e
 TONEMAP_MODES = ["select", "normal", "colourmap"]                 # tonemap_mode_e
 TONEMAP_FORMATS = {"f32": 0, "u8": 1, "u16": 2}
@@ -77,7 +90,8 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_scene_stats_json", "wtgpu_calibrate_copy", "wtgpu_render_async", "wtgpu_join", "wtgpu_query_regions", "wtgpu_render_progressive",
            "wtgpu_cancel", "wtgpu_pause", "wtgpu_resume", "wtgpu_capture_intermediate", "wtgpu_comm_unique_id", "wtgpu_comm_create", "wtgpu_film_reduce", "wtgpu_comm_destroy", "wtgpu_scene_create_from_xml",
            "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host",
-           "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host"]
+           "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host",
+           "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
 CAPTURE_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_void_p)
 
@@ -144,6 +158,9 @@ def load_library():
     lib.wtgpu_develop_device.argtypes = [vp, vp, vp, vp, vp, u64, vp]
     lib.wtgpu_tonemap_device.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(Tonemap), u32, vp, u32, vp]
     lib.wtgpu_tonemap_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(Tonemap), u32, vp, u32, u32, vp]
+    lib.wtgpu_film_stats_edges.argtypes = [C.POINTER(FilmStatsSpec), vp]
+    lib.wtgpu_film_stats_device.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(FilmStatsSpec), vp, vp, vp]
+    lib.wtgpu_film_stats_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(FilmStatsSpec), vp, u32, vp, vp]
     lib.wtgpu_calibrate_copy.argtypes = [u64, i32]
     lib.wtgpu_get_counters.argtypes = [vp, C.POINTER(Counters)]
     lib.wtgpu_reset_counters.argtypes = [vp]
@@ -586,6 +603,84 @@ class Scene:
                                                  int(stokes_component), None if m is None else m.ctypes.data, TONEMAP_FORMATS[fmt], int(threads), out.ctypes.data))
         del keep
         return out
+
+    # ---- film statistics (wtgpu_film_stats_*; csrc/wt/film_stats.h) ----
+    def _film_stats(self, what, call, stokes_component, scale, range, bins, abs, luminance):
+        """The one or two passes of film_stats_device / film_stats_host.  call(spec, records, hist_pointer_or_None) runs one pass."""
+        import numpy as np
+        if scale not in FILM_STATS_SCALES:
+            raise ValueError(f"{what}: scale 'dB' or 'linear' expected, got {scale!r}")
+        planes = self.spectral_channels + (1 if luminance else 0)
+        flags = (FILM_STATS_ABS if abs else 0) | (FILM_STATS_LUMINANCE if luminance else 0)
+
+        def one_pass(lo, hi, nbins):
+            spec = FilmStatsSpec(int(stokes_component), FILM_STATS_SCALES.index(scale), int(nbins), flags, float(lo), float(hi))
+            rec = (FilmStats * max(planes, 1))()
+            hist = np.zeros((planes, min(int(nbins), FILM_STATS_MAX_BINS)), dtype=np.uint64)
+            call(spec, rec, hist.ctypes.data if hist.size else None)
+            return spec, rec, hist
+
+        if range is None:
+            # the range pass: no bins; then the histogram from the smallest positive (dB) or smallest (linear) to the largest element of all planes
+            _, rec, _ = one_pass(0.0, 0.0, 0)
+            lows = np.array([r.min_positive if scale == "dB" else r.min for r in rec], dtype=np.float64)
+            highs = np.array([r.max for r in rec], dtype=np.float64)
+            if np.isnan(lows).all() or not np.isfinite(np.nanmax(highs)):
+                raise ValueError(f"{what}: range=None needs a finite {'positive ' if scale == 'dB' else ''}element to take the range from; pass a range")
+            lo, hi = float(np.nanmin(lows)), float(np.nanmax(highs))
+            if scale == "dB":
+                # a margin of 1e-3 dB (2e-4 of the value, far above f32 rounding) keeps both ends inside the bins
+                lo, hi = 10.0 * math.log10(lo) - 1e-3, 10.0 * math.log10(hi) + 1e-3
+            else:
+                pad = max(math.fabs(lo), math.fabs(hi), 1e-30) * 1e-6
+                lo, hi = lo - pad, hi + pad
+            range = (lo, hi)
+        spec, rec, hist = one_pass(range[0], range[1], bins)
+        edges = np.zeros(spec.bins + 1, dtype=np.float32)
+        _check(load_library().wtgpu_film_stats_edges(C.byref(spec), edges.ctypes.data))
+        out = {name: np.array([getattr(r, name) for r in rec], dtype=dt) for name, dt in
+               (("n", np.uint64), ("n_nan", np.uint64), ("n_negative", np.uint64), ("n_zero", np.uint64), ("n_below", np.uint64), ("n_above", np.uint64),
+                ("min", np.float32), ("max", np.float32), ("min_positive", np.float32), ("sum", np.float64))}
+        out.update(hist=hist, edges=edges, scale=scale, range=(float(spec.lo), float(spec.hi)), bins=int(spec.bins))
+        return out
+
+    def film_stats_device(self, value, weight, light, spe, *, stokes_component=0, scale="dB", range=None, bins=256, abs=False, luminance=False, mask=None,
+                          stream=None):
+        """Range, histogram and sum of the developed planes of one Stokes component, computed where the films are (wtgpu_film_stats_device): value /
+        weight / light are the torch f64 films on the scene's device, mask an H x W f32 tensor there (sensor_mask; elements of pixels with
+        mask > 0 count) or None.  One record per channel, plus the BT.709 luminance of an RGB film with luminance=True; abs=True takes |x|.
+        scale / range / bins: the histogram's axis, `bins` equal steps from range[0] to range[1] in dB (10 log10 x) or linear units.
+        range=None: two passes, the first without bins for the smallest positive (dB) or smallest (linear) and the largest element.
+        Returns a dict of numpy arrays indexed by plane: n, n_nan, n_negative, n_zero, n_below, n_above (uint64), min, max, min_positive
+        (float32), sum (float64), hist [planes, bins] uint64; and edges [bins + 1] float32, scale, range, bins.  imageio.percentiles reads it."""
+        import torch
+        dev = self._device_films("film_stats_device", value, weight, light, mask)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        lib = load_library()
+
+        def call(spec, rec, hist):
+            _check(lib.wtgpu_film_stats_device(self._h, C.c_void_p(st) if st else None, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
+                                               C.byref(spec), None if mask is None else mask.data_ptr(), C.cast(rec, C.c_void_p), hist))
+        return self._film_stats("film_stats_device", call, stokes_component, scale, range, bins, abs, luminance)
+
+    def film_stats_host(self, value, weight, light, spe, *, stokes_component=0, scale="dB", range=None, bins=256, abs=False, luminance=False, mask=None,
+                        threads=0):
+        """film_stats_device's twin on host threads from numpy films (wtgpu_film_stats_host; threads 0 = all cores): the same dict, every field bit
+        for bit the device's.  No device needed."""
+        import numpy as np
+        v = np.ascontiguousarray(value, dtype=np.float64)
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        l = np.ascontiguousarray(light, dtype=np.float64)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+        n = self.width * self.height
+        if v.size != n * self.channels or l.size != v.size or w.size != n or (m is not None and m.size != n):
+            raise ValueError("film_stats_host: films of the scene's size expected")
+        lib = load_library()
+
+        def call(spec, rec, hist):
+            _check(lib.wtgpu_film_stats_host(self._h, v.ctypes.data, w.ctypes.data, l.ctypes.data, int(spe), C.byref(spec), None if m is None else m.ctypes.data,
+                                             int(threads), C.cast(rec, C.c_void_p), hist))
+        return self._film_stats("film_stats_host", call, stokes_component, scale, range, bins, abs, luminance)
 
     def profile_counters(self, n=8):
         """Test hook (wtgpu_test_hooks.h): the first n WTGPU_PROFILE scratch counters, accumulated since upload."""

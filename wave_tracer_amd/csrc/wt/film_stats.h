@@ -1,0 +1,101 @@
+// wave_tracer_amd — film statistics (range, histogram, sum): the arithmetic the device kernels (kernels_stats.hip) and their host twin share.
+//
+// Element value.  x = develop_plane(...) of wt/tonemap.h, the f32 wtgpu_develop writes, of plane  channel * stokes + stokes_component;  with
+// FS_LUMINANCE a 3-channel film has a fourth plane, tm_luminance of the three developed values (taken before FS_ABS).  FS_ABS: fabsf(x), for the
+// signed Stokes components Q / U / V (a NaN stays a NaN).
+// Membership.  A pixel's elements are included iff no mask is given or mask[pixel] > 0 (a NaN mask value excludes).
+// Classes.  An included element is exactly one of: NaN;  x < 0;  x == 0;  0 < x < edge[0] (below);  x >= edge[bins] (above);  bin i with
+// edge[i] <= x < edge[i + 1].  edge[] holds bins + 1 strictly increasing f32 thresholds in x's own scale, built ONCE on the host in f64 and
+// rounded (fs_edge): linear  lo + i (hi - lo) / bins,  dB  10^((lo + i (hi - lo) / bins) / 10).  No logf runs per element, so every count is the
+// same on both sides, bit for bit.  bins = 0: the single edge of lo splits the positive elements into below and above.
+// Extrema.  min / max / min_positive over the non-NaN included elements under the total order of fs_key (-0 sorts below +0), so they do not
+// depend on the order the elements are met in; NaN when there is no such element.
+// Sum.  f64, over the non-NaN included elements, in ONE fixed order: the plane's elements in row-major order in chunks of kFsChunk = 256, a chunk
+// reduced by the butterfly pairing a[i] += a[i + d] (i < d) for d = 128, 64, ... 1 with +0.0 for excluded, NaN and missing elements; the
+// chunk sums reduced by the same rule, level after level, until one number is left (fs_level_count).  Only additions: nothing to contract.
+#pragma once
+#include "core.h"
+#include "tonemap.h"
+
+namespace wt {
+
+enum film_stats_flag_e : uint32_t { FS_ABS = 1u, FS_LUMINANCE = 2u };
+enum film_stats_scale_e : uint32_t { FS_LINEAR = 0u, FS_DB = 1u };
+constexpr uint32_t kFsMaxBins = 4096;
+constexpr uint32_t kFsMaxPlanes = 4;    // three channels and the luminance
+constexpr uint32_t kFsChunk = 256;
+
+// wtgpu_film_stats as the kernels fill it: the three extrema travel as keys until the last kernel turns them into floats
+struct film_stats_rec_t {
+    unsigned long long n, n_nan, n_negative, n_zero, n_below, n_above;
+    uint32_t min_inv, max_key, minpos_inv, pad;   // ~fs_key of the minima (so that all three grow, from 0 = "no element"), fs_key of the maximum
+    double sum;
+};
+static_assert(sizeof(film_stats_rec_t) == 72, "wtgpu_film_stats");
+
+// edge i of the table, in f64 until the one rounding (the host builds the table; nothing on the device calls this)
+inline float fs_edge(uint32_t scale, double lo, double hi, uint32_t bins, uint32_t i) {
+    const double t = bins ? lo + double(i) * (hi - lo) / double(bins) : lo;
+    return (float)(scale == FS_DB ? std::pow(10.0, t / 10.0) : t);
+}
+
+// A key that orders the non-NaN floats as the reals order them, -0 below +0: unsigned comparison of keys = comparison of values.  No value
+// maps to 0 or to 0xffffffff (the keys of the NaNs with all mantissa bits set), which is what makes 0 the mark of "no element".
+WT_HD uint32_t fs_key(float x) {
+    uint32_t u;
+    __builtin_memcpy(&u, &x, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+WT_HD float fs_unkey(uint32_t k) {
+    if (k == 0u) k = 0x7fc00000u ^ 0x80000000u;   // no element: a quiet NaN
+    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float x;
+    __builtin_memcpy(&x, &u, 4);
+    return x;
+}
+
+enum film_stats_class_e : uint32_t { FS_NAN = 0, FS_NEGATIVE = 1, FS_ZERO = 2, FS_BELOW = 3, FS_ABOVE = 4, FS_BIN = 5 };
+// The class of an element; for FS_BIN the bin's index goes to `bin`.  The search keeps edge[lo] <= x < edge[hi].
+WT_HD uint32_t fs_classify(float x, const float* edge, uint32_t bins, uint32_t& bin) {
+    if (!(x == x)) return FS_NAN;
+    if (x < 0.f) return FS_NEGATIVE;
+    if (x == 0.f) return FS_ZERO;
+    if (x < edge[0]) return FS_BELOW;
+    if (x >= edge[bins]) return FS_ABOVE;
+    uint32_t lo = 0, hi = bins;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (x >= edge[mid]) lo = mid;
+        else hi = mid;
+    }
+    bin = lo;
+    return FS_BIN;
+}
+
+// the developed value of output plane c (< channels) of a pixel, and the element it stands for
+WT_HD float fs_develop(const double* value, const double* light, double w, double sl, uint64_t pixel, uint32_t channels, uint32_t stokes, uint32_t s, uint32_t c) {
+    const uint64_t i = pixel * (channels * stokes) + c * stokes + s;
+    return develop_plane(value[i], w, light[i], sl);
+}
+WT_HD float fs_element(float x, uint32_t flags) { return (flags & FS_ABS) ? fabsf(x) : x; }
+// what an element adds to its plane's sum
+WT_HD double fs_addend(float x, bool included) { return included && x == x ? (double)x : 0.0; }
+
+// The butterfly over one chunk (host form; the device holds four elements per lane and pairs them the same way: kernels_stats.hip).
+inline double fs_chunk_sum(double a[kFsChunk]) {
+    for (uint32_t d = kFsChunk / 2; d; d >>= 1)
+        for (uint32_t i = 0; i < d; ++i) a[i] += a[i + d];
+    return a[0];
+}
+// sums per level: n elements -> ceil(n / 256) chunk sums -> ... -> 1.  A single chunk sum IS the sum (no further level adds +0.0 to it).
+WT_HD uint64_t fs_chunks(uint64_t n) { return (n + kFsChunk - 1) / kFsChunk; }
+WT_HD uint64_t fs_scratch_len(uint64_t n_elements) {   // doubles of scratch one plane needs for all its levels
+    uint64_t total = 0, n = fs_chunks(n_elements);
+    for (;;) {
+        total += n;
+        if (n <= 1) return total;
+        n = fs_chunks(n);
+    }
+}
+
+}   // namespace wt

@@ -8,6 +8,7 @@
 //   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
 //   kernels_mask.hip    k_sensor_mask_wave / k_sensor_mask_lane: by-geometry sensor masks (not part of a render)
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
+//   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -424,6 +425,14 @@ int develop_tonemap_launch(const sensor_t& sn, hipStream_t stream, const double*
                            const tonemap_args_t& t, uint32_t s, const float* d_mask, uint32_t format, uint32_t lds_table, void* d_out);
 void develop_tonemap_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, const tonemap_args_t& t, uint32_t s,
                           const float* mask, uint32_t format, uint32_t n_threads, void* out);
+// kernels_stats.hip: film statistics (wtgpu_film_stats_device / wtgpu_film_stats_host; wt/film_stats.h).  Films as wtgpu_render fills them; s: the Stokes
+// component; flags: FS_ABS | FS_LUMINANCE; edges: bins + 1 thresholds (DEVICE for the launch); rec: film_stats_rec_t per plane and hist: [planes][bins],
+// both ZEROED by the caller of the launch (the host twin clears its own); d_sums: kFsMaxPlanes x fs_scratch_len(pixels) doubles.  Two kernels on
+// `stream`; the launch returns a hipError_t.
+int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe, uint32_t s,
+                      uint32_t flags, const float* d_mask, const float* d_edges, uint32_t bins, void* d_rec, unsigned long long* d_hist, double* d_sums);
+void film_stats_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, uint32_t s, uint32_t flags, const float* mask,
+                     const float* edges, uint32_t bins, uint32_t n_threads, void* out_rec, unsigned long long* out_hist);
 
 }   // namespace wtk
 using namespace wtk;

@@ -1,8 +1,9 @@
 // wave_tracer_amd — entry points that are not a render: ray / cone / region queries, by-geometry sensor masks, the probes of the kernel tests
-// (wtgpu_test_hooks.h), the PMC calibration copy, develop and tonemap.
+// (wtgpu_test_hooks.h), the PMC calibration copy, develop and tonemap, film statistics.
 #include "wtgpu_host.h"
 #include "wt/sources_probe.h"
 #include "wt/tonemap.h"
+#include "wt/film_stats.h"
 
 extern "C" {
 
@@ -286,6 +287,99 @@ int wtgpu_tonemap_host(const wtgpu_scene* s, const double* value, const double* 
     if (const int rc = tonemap_args_for(s, tm, stokes_component, format, args, own)) return rc;
     try {
         develop_tonemap_host(s->host.sensor, value, weight, light, spe, args, stokes_component, mask, format, n_threads, out);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+
+// ---- film statistics (kernels_stats.hip; wt/film_stats.h) -----------------------------------------------------------------------------------
+static_assert(sizeof(wtgpu_film_stats) == sizeof(film_stats_rec_t), "the kernels' record is wtgpu_film_stats");
+// what a spec says by itself, and its edge table
+static int film_stats_edges_for(const wtgpu_film_stats_spec* spec, float* edges) {
+    if (spec->scale > FS_DB) return fail(WTGPU_ERR_INVALID, "film_stats: scale 0 (linear) or 1 (dB) expected");
+    if (spec->flags & ~(FS_ABS | FS_LUMINANCE)) return fail(WTGPU_ERR_INVALID, "film_stats: flags 1 (ABS) and 2 (LUMINANCE) expected");
+    if (spec->bins > kFsMaxBins) return fail(WTGPU_ERR_INVALID, "film_stats: bins " + std::to_string(spec->bins) + " above the " + std::to_string(kFsMaxBins) + " the histogram holds");
+    if (!std::isfinite(spec->lo) || (spec->bins > 0 && !std::isfinite(spec->hi))) return fail(WTGPU_ERR_INVALID, "film_stats: a finite range expected");
+    if (spec->bins > 0 && !(spec->lo < spec->hi)) return fail(WTGPU_ERR_INVALID, "film_stats: lo < hi expected with bins > 0");
+    for (uint32_t i = 0; i <= spec->bins; ++i) {
+        edges[i] = fs_edge(spec->scale, spec->lo, spec->hi, spec->bins, i);
+        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i - 1] < edges[i])))
+            return fail(WTGPU_ERR_INVALID, "film_stats: degenerate edges: edge " + std::to_string(i) + " of " + std::to_string(spec->bins) + " is not above edge " +
+                                               std::to_string(i ? i - 1 : 0) + " after rounding to f32 (fewer bins or a wider range)");
+    }
+    return WTGPU_OK;
+}
+// ... and against the scene's film; planes: records per call
+static int film_stats_check(const wtgpu_scene* s, const wtgpu_film_stats_spec* spec, uint32_t& planes) {
+    const sensor_t& sn = s->host.sensor;
+    if (sn.channels != 1 && sn.channels != 3) return fail(WTGPU_ERR_INVALID, "film_stats: a film of 1 or 3 channels expected");
+    if (spec->stokes_component >= film_stokes(sn))
+        return fail(WTGPU_ERR_INVALID, "film_stats: stokes_component " + std::to_string(spec->stokes_component) + " out of range (the film has " + std::to_string(film_stokes(sn)) + ")");
+    if ((spec->flags & FS_LUMINANCE) && sn.channels != 3) return fail(WTGPU_ERR_INVALID, "film_stats: LUMINANCE needs a 3-channel film (this one has " + std::to_string(sn.channels) + ")");
+    planes = sn.channels + ((spec->flags & FS_LUMINANCE) ? 1u : 0u);
+    return WTGPU_OK;
+}
+int wtgpu_film_stats_edges(const wtgpu_film_stats_spec* spec, float* edges) {
+    if (!spec || !edges) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (spec->bins > kFsMaxBins) return film_stats_edges_for(spec, nullptr);   // (refused before anything is written)
+    return film_stats_edges_for(spec, edges);
+}
+
+// the scene's scratch block: records, histogram, edge table — on the device and, pinned, on the host
+constexpr size_t kFsRecBytes = kFsMaxPlanes * sizeof(film_stats_rec_t), kFsHistBytes = (size_t)kFsMaxPlanes * kFsMaxBins * sizeof(uint64_t);
+constexpr size_t kFsEdgeOffset = kFsRecBytes + kFsHistBytes, kFsBlockBytes = kFsEdgeOffset + (kFsMaxBins + 1) * sizeof(float);
+
+int wtgpu_film_stats_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                            const wtgpu_film_stats_spec* spec, const float* d_mask, wtgpu_film_stats* out, uint64_t* hist) {
+    if (!s || !d_value || !d_weight || !d_light || !spec || !out || (!hist && spec->bins > 0)) return fail(WTGPU_ERR_INVALID, "null argument");
+    uint32_t planes = 0;
+    float edges[kFsMaxBins + 1];
+    if (const int rc = film_stats_edges_for(spec, edges)) return rc;
+    if (const int rc = film_stats_check(s, spec, planes)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    const sensor_t& sn = s->host.sensor;
+    const uint64_t npix = (uint64_t)sn.width * sn.height;
+    if (npix == 0) return fail(WTGPU_ERR_INVALID, "film_stats: the film has no pixels");
+    device_guard_t guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!s->d_fs) {   // first use: the block, its pinned copy, the chunk sums of this scene's film (all levels, kFsMaxPlanes planes)
+        unsigned char* d = nullptr;
+        double* sums = nullptr;
+        if (const int rc = dmalloc(s, &d, kFsBlockBytes)) return rc;
+        if (const int rc = dmalloc(s, &sums, (size_t)kFsMaxPlanes * fs_scratch_len(npix))) return rc;
+        HIP_CHECK(hipHostMalloc((void**)&s->h_fs, kFsBlockBytes, hipHostMallocDefault));
+        int n_cu = 256;
+        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device);
+        s->fs_cus = (uint32_t)std::max(1, n_cu);
+        s->d_fs_sums = sums;
+        s->d_fs = d;
+    }
+    // The call waits for its own result below, so the block is free again when it returns.
+    const size_t result_bytes = kFsRecBytes + (size_t)planes * spec->bins * sizeof(uint64_t), edge_bytes = (spec->bins + 1) * sizeof(float);
+    std::memcpy(s->h_fs + kFsEdgeOffset, edges, edge_bytes);
+    HIP_CHECK(hipMemcpyAsync(s->d_fs + kFsEdgeOffset, s->h_fs + kFsEdgeOffset, edge_bytes, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemsetAsync(s->d_fs, 0, result_bytes, stream));
+    const int e = film_stats_launch(sn, stream, s->fs_cus, d_value, d_weight, d_light, spe, spec->stokes_component, spec->flags, d_mask,
+                                    reinterpret_cast<const float*>(s->d_fs + kFsEdgeOffset), spec->bins, s->d_fs, reinterpret_cast<unsigned long long*>(s->d_fs + kFsRecBytes),
+                                    s->d_fs_sums);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_stats: ") + hipGetErrorString((hipError_t)e));
+    HIP_CHECK(hipMemcpyAsync(s->h_fs, s->d_fs, result_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    std::memcpy(out, s->h_fs, planes * sizeof(wtgpu_film_stats));
+    if (spec->bins) std::memcpy(hist, s->h_fs + kFsRecBytes, (size_t)planes * spec->bins * sizeof(uint64_t));
+    return WTGPU_OK;
+}
+int wtgpu_film_stats_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_film_stats_spec* spec,
+                          const float* mask, uint32_t n_threads, wtgpu_film_stats* out, uint64_t* hist) {
+    if (!s || !value || !weight || !light || !spec || !out || (!hist && spec->bins > 0)) return fail(WTGPU_ERR_INVALID, "null argument");
+    uint32_t planes = 0;
+    float edges[kFsMaxBins + 1];
+    if (const int rc = film_stats_edges_for(spec, edges)) return rc;
+    if (const int rc = film_stats_check(s, spec, planes)) return rc;
+    try {
+        film_stats_host(s->host.sensor, value, weight, light, spe, spec->stokes_component, spec->flags, mask, edges, spec->bins, n_threads, out,
+                        reinterpret_cast<unsigned long long*>(hist));
     } catch (const std::exception& e) {
         return fail(WTGPU_ERR_INVALID, e.what());
     }

@@ -315,6 +315,10 @@ void release_device(wtgpu_scene* s) {
     s->h_tm_table = nullptr;
     if (s->ev_tm) (void)hipEventDestroy(s->ev_tm);
     s->ev_tm = nullptr;
+    s->d_fs = nullptr;           // (freed with dev_allocs)
+    s->d_fs_sums = nullptr;
+    if (s->h_fs) (void)hipHostFree(s->h_fs);
+    s->h_fs = nullptr;
     s->uploaded = false;
 }
 

@@ -60,6 +60,40 @@ def colour_table(name, n=256):
     return colourmap(np.arange(n, dtype=np.float64) / (n - 1), name.lower()).astype(np.float32)
 
 
+def percentiles(stats, q):
+    """Percentiles q (0 .. 100, a number or a sequence) of every plane of a Scene.film_stats_device / film_stats_host result, from its counts and
+    edges alone, in the histogram's own scale (dB or linear units: what tonemap's db_range and an exposure are stated in).  The population is what
+    has a place on that axis: the elements below the range, those in the bins, those above it — NaNs, negative elements and exact zeros are
+    not ranked.  Rank q / 100 x population is looked up in the cumulative counts and interpolated linearly inside its bin; a rank that falls
+    among the elements below (above) the range gives range[0] (range[1]); without bins every rank gives range[0], the one edge.  Returns float64 [planes, len(q)] ([planes] for a number); NaN where
+    the population is empty."""
+    qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if ((qs < 0) | (qs > 100)).any():
+        raise ValueError("percentiles: q in 0 .. 100 expected")
+    hist = np.asarray(stats["hist"], dtype=np.float64)
+    planes, bins = hist.shape
+    lo, hi = stats["range"]
+    below, above = np.asarray(stats["n_below"], dtype=np.float64), np.asarray(stats["n_above"], dtype=np.float64)
+    out = np.full((planes, len(qs)), np.nan)
+    for p in range(planes):
+        total = below[p] + hist[p].sum() + above[p]
+        if total == 0:
+            continue
+        cum = below[p] + np.concatenate(([0.0], np.cumsum(hist[p])))     # elements left of edge i
+        for k, rank in enumerate(qs / 100.0 * total):
+            filled = np.flatnonzero(hist[p])
+            if rank < below[p] or bins == 0:                            # (no bins: lo is the one edge there is)
+                out[p, k] = lo
+            elif rank > cum[-1] or len(filled) == 0:
+                out[p, k] = hi if above[p] > 0 else lo
+            elif rank == cum[-1]:                                       # the upper edge of the last filled bin
+                out[p, k] = lo + (filled[-1] + 1) * (hi - lo) / bins
+            else:
+                i = int(np.searchsorted(cum, rank, "right")) - 1        # cum[i] <= rank < cum[i + 1]: a filled bin
+                out[p, k] = lo + (i + (rank - cum[i]) / hist[p, i]) * (hi - lo) / bins
+    return out[:, 0] if np.ndim(q) == 0 else out
+
+
 def tonemap(img, op="sRGB", mode="select", gamma=2.2, db_range=(-60.0, 0.0), cmap="turbo"):
     """tonemap_t::operator() on a developed film [H,W,1] or [H,W,3] -> RGB in [0,1].
     op: linear | gamma | sRGB | dB;  mode: select (colour map for monochrome, per channel for RGB) | normal | colourmap."""

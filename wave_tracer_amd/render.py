@@ -38,6 +38,20 @@ def develop_device(scene, value, weight, light, spe, stream=None):
     return out.cpu().numpy()
 
 
+def auto_db_range(scene, films, spe, *, percentiles=(1, 99), mask=None):
+    """A dB range for the films as they are: the two percentiles of 10 log10 x over the positive elements (of the pixels where mask > 0), from a
+    256-bin histogram between the smallest positive and the largest element — Scene.film_stats_device on torch films on the scene's device
+    (nothing but counts crosses to the host), Scene.film_stats_host on numpy films.  An RGB film is judged by its luminance, a polarimetric
+    one by its intensity (Stokes component 0).  Returns (db_min, db_max): tonemap_device's {"op": "dB", "db_range": ...}."""
+    from . import imageio
+    value, weight, light = films
+    stats_of = scene.film_stats_host if isinstance(value, np.ndarray) else scene.film_stats_device
+    lum = scene.spectral_channels == 3
+    stats = stats_of(value, weight, light, spe, scale="dB", range=None, bins=256, luminance=lum, mask=mask)
+    lo, hi = imageio.percentiles(stats, percentiles)[-1 if lum else 0]
+    return float(lo), float(hi)
+
+
 def render(scene, spp, seed=1, device=0, sample_begin=0):
     """Renders `spp` samples per element on one GPU; returns (value, weight, light) as numpy f64 arrays."""
     import torch
