@@ -314,6 +314,43 @@ int wtgpu_film_stats_device(wtgpu_scene* scene, void* stream, const double* d_va
 int wtgpu_film_stats_host(const wtgpu_scene* scene, const double* value, const double* weight, const double* light, uint64_t spe,
                           const wtgpu_film_stats_spec* spec, const float* mask, uint32_t n_threads, wtgpu_film_stats* out, uint64_t* hist);
 
+/* Film comparison: difference statistics of two sets of films of this scene's size, A and B, without either leaving the device — parity and A/B
+ * checks, and the half-film noise estimate (two films that took alternating sample ranges: ||a - b|| / ||a + b|| from sum_sq, sum_a_sq, sum_b_sq).
+ *   planes   as for the film statistics: the film's channels (plane c: the developed values xa, xb of film plane c * stokes + stokes_component of
+ *            A with spe_a and of B with spe_b, bit for bit wtgpu_develop's), plus one with flag 2 LUMINANCE (3-channel films only); flag 1 ABS
+ *            compares |xa| with |xb|.
+ *   members  all pixels, or with a mask ([height][width] f32) those where mask > 0.
+ *   classes  a member pair is non-finite (either value is NaN or infinite: counted in n_nonfinite, and in n_nonfinite_mismatch unless both are NaN
+ *            or xa == xb; it enters no sum and not the maximum) or finite: d = (double)xa - (double)xb, counted in n_differ iff xa != xb (-0 and
+ *            +0 do not differ).
+ *   record   n members and the three counts; max_abs = max |d| over the finite pairs and argmax, the row-major index of the pixel that has it,
+ *            the lowest on a tie — 0 and UINT64_MAX where no finite pair differs; five f64 sums over the finite pairs: sum_abs |d|, sum_sq d d,
+ *            sum_a_sq xa xa, sum_b_sq xb xb, sum_rel d d / (xb xb + eps), each in the fixed order of the film statistics' sum, so device and host
+ *            agree on every field bit for bit.
+ *   diff     optional: [height][width][planes] f32, xa - xb as one f32 subtraction (whatever that gives for a non-finite pair; a NaN is stored
+ *            as the quiet NaN 0x7fc00000), 0 for a pixel the mask excludes.
+ * Errors (WTGPU_ERR_INVALID with a message): stokes_component >= the film's stokes, LUMINANCE on a film that is not 3-channel, unknown flags, an
+ * eps that is not finite and > 0.  spe = 0 is what it is to wtgpu_develop: no light term. */
+typedef struct wtgpu_film_compare_spec {
+    uint32_t stokes_component, flags /* 1 ABS, 2 LUMINANCE */;
+    double eps;
+} wtgpu_film_compare_spec;
+typedef struct wtgpu_film_compare {
+    uint64_t n, n_nonfinite, n_nonfinite_mismatch, n_differ, argmax;
+    double max_abs, sum_abs, sum_sq, sum_a_sq, sum_b_sq, sum_rel;
+} wtgpu_film_compare;
+/* On the device, on `stream`: one pass over both sets (as wtgpu_render fills them; A and B may be the same memory) that develops in registers and
+ * writes d_diff (DEVICE, may be NULL) on its way, then a small kernel and the copy of the records, for which the call waits: out[planes] is HOST
+ * memory.  d_mask: DEVICE, may be NULL.  Needs an uploaded scene (WTGPU_ERR_INVALID otherwise); its scratch memory is allocated at the first call
+ * and freed with the scene; touches neither films nor counters. */
+int wtgpu_film_compare_device(wtgpu_scene* scene, void* stream, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                              const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec,
+                              const float* d_mask, wtgpu_film_compare* out, float* d_diff);
+/* The same on `n_threads` host threads (0: all cores) from HOST films; diff: HOST, may be NULL; the result does not depend on n_threads.  No device needed. */
+int wtgpu_film_compare_host(const wtgpu_scene* scene, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                            const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec,
+                            const float* mask, uint32_t n_threads, wtgpu_film_compare* out, float* diff);
+
 void wtgpu_scene_destroy(wtgpu_scene* scene);
 const char* wtgpu_last_error(void);
 const char* wtgpu_scene_stats_json(const wtgpu_scene* scene);

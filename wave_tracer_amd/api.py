@@ -56,6 +56,19 @@ class FilmStats(C.Structure):        # wtgpu_film_stats
                 ("min", C.c_float), ("max", C.c_float), ("min_positive", C.c_float), ("pad", C.c_float), ("sum", C.c_double)]
 
 
+class FilmCompareSpec(C.Structure):  # wtgpu_film_compare_spec
+    _fields_ = [("stokes_component", C.c_uint32), ("flags", C.c_uint32), ("eps", C.c_double)]
+
+
+FILM_COMPARE_FIELDS = [("n", C.c_uint64), ("n_nonfinite", C.c_uint64), ("n_nonfinite_mismatch", C.c_uint64), ("n_differ", C.c_uint64), ("argmax", C.c_uint64),
+                       ("max_abs", C.c_double), ("sum_abs", C.c_double), ("sum_sq", C.c_double), ("sum_a_sq", C.c_double), ("sum_b_sq", C.c_double),
+                       ("sum_rel", C.c_double)]
+
+
+class FilmCompare(C.Structure):      # wtgpu_film_compare
+    _fields_ = FILM_COMPARE_FIELDS
+
+
 FILM_STATS_SCALES = ["linear", "dB"]
 FILM_STATS_ABS, FILM_STATS_LUMINANCE = 1, 2
 FILM_STATS_MAX_BINS = 4096
@@ -91,7 +104,8 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_cancel", "wtgpu_pause", "wtgpu_resume", "wtgpu_capture_intermediate", "wtgpu_comm_unique_id", "wtgpu_comm_create", "wtgpu_film_reduce", "wtgpu_comm_destroy", "wtgpu_scene_create_from_xml",
            "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host",
            "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host",
-           "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host"]
+           "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host",
+           "wtgpu_film_compare_device", "wtgpu_film_compare_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
 CAPTURE_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_void_p)
 
@@ -161,6 +175,8 @@ def load_library():
     lib.wtgpu_film_stats_edges.argtypes = [C.POINTER(FilmStatsSpec), vp]
     lib.wtgpu_film_stats_device.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(FilmStatsSpec), vp, vp, vp]
     lib.wtgpu_film_stats_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(FilmStatsSpec), vp, u32, vp, vp]
+    lib.wtgpu_film_compare_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmCompareSpec), vp, vp, vp]
+    lib.wtgpu_film_compare_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmCompareSpec), vp, u32, vp, vp]
     lib.wtgpu_calibrate_copy.argtypes = [u64, i32]
     lib.wtgpu_get_counters.argtypes = [vp, C.POINTER(Counters)]
     lib.wtgpu_reset_counters.argtypes = [vp]
@@ -681,6 +697,74 @@ class Scene:
             _check(lib.wtgpu_film_stats_host(self._h, v.ctypes.data, w.ctypes.data, l.ctypes.data, int(spe), C.byref(spec), None if m is None else m.ctypes.data,
                                              int(threads), C.cast(rec, C.c_void_p), hist))
         return self._film_stats("film_stats_host", call, stokes_component, scale, range, bins, abs, luminance)
+
+    # ---- film comparison (wtgpu_film_compare_*; csrc/wt/film_compare.h) ----
+    def _film_compare(self, call, stokes_component, abs, luminance, eps):
+        """What film_compare_device / film_compare_host share: the spec, the records as a dict, the values derived from the sums."""
+        import numpy as np
+        planes = self.spectral_channels + (1 if luminance else 0)
+        spec = FilmCompareSpec(int(stokes_component), (FILM_STATS_ABS if abs else 0) | (FILM_STATS_LUMINANCE if luminance else 0), float(eps))
+        rec = (FilmCompare * max(planes, 1))()
+        call(spec, rec, planes)
+        out = {name: np.array([getattr(r, name) for r in rec], dtype=np.uint64 if t is C.c_uint64 else np.float64) for name, t in FILM_COMPARE_FIELDS}
+        finite = (out["n"] - out["n_nonfinite"]).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["rmse"] = np.sqrt(out["sum_sq"] / finite)
+            out["mean_abs"] = out["sum_abs"] / finite
+            out["rel_l2"] = np.sqrt(out["sum_sq"] / out["sum_b_sq"])
+            out["rel_mse"] = out["sum_rel"] / finite
+        return out
+
+    def film_compare_device(self, films_a, spe_a, films_b, spe_b, *, stokes_component=0, abs=False, luminance=False, mask=None, eps=1e-4, diff=False, stream=None):
+        """Difference statistics of two sets of films where they are (wtgpu_film_compare_device): films_a / films_b are (value, weight, light), torch f64
+        tensors on the scene's device (the same tensors twice are fine), developed with spe_a / spe_b samples per element; mask an H x W f32 tensor there
+        (pixels with mask > 0 count) or None.  One record per channel of Stokes component `stokes_component`, plus the BT.709 luminance of an RGB film
+        with luminance=True; abs=True compares |xa| with |xb|.  Returns a dict of numpy arrays indexed by plane: n, n_nonfinite, n_nonfinite_mismatch,
+        n_differ, argmax (uint64; the row-major pixel of max_abs, 2^64 - 1 where nothing differs), max_abs, sum_abs, sum_sq, sum_a_sq, sum_b_sq, sum_rel
+        (float64; over the pairs of finite values, d = xa - xb) and, derived here from the sums, rmse, mean_abs, rel_l2 = sqrt(sum_sq / sum_b_sq) and
+        rel_mse = sum_rel / (n - n_nonfinite) with sum_rel's addends d d / (xb xb + eps) (NaN where there is nothing to divide by).  diff=True adds
+        "diff": xa - xb as a torch f32 tensor H x W x planes on the device, 0 where the mask excludes."""
+        import torch
+        dev = self._device_films("film_compare_device", *films_a, mask)
+        self._device_films("film_compare_device", *films_b)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        d = {}
+
+        def call(spec, rec, planes):
+            if diff:
+                d["diff"] = torch.empty((self.height, self.width, planes), dtype=torch.float32, device=dev)
+            _check(load_library().wtgpu_film_compare_device(self._h, C.c_void_p(st) if st else None, *(t.data_ptr() for t in films_a), int(spe_a),
+                                                            *(t.data_ptr() for t in films_b), int(spe_b), C.byref(spec), None if mask is None else mask.data_ptr(),
+                                                            C.cast(rec, C.c_void_p), d["diff"].data_ptr() if diff else None))
+        out = self._film_compare(call, stokes_component, abs, luminance, eps)
+        out.update(d)
+        return out
+
+    def film_compare_host(self, films_a, spe_a, films_b, spe_b, *, stokes_component=0, abs=False, luminance=False, mask=None, eps=1e-4, diff=False, threads=0):
+        """film_compare_device's twin on host threads from numpy films (wtgpu_film_compare_host; threads 0 = all cores): the same dict, every field bit
+        for bit the device's, "diff" a numpy array.  No device needed."""
+        import numpy as np
+        n = self.width * self.height
+        sets = []
+        for films in (films_a, films_b):
+            v, w, l = (np.ascontiguousarray(t, dtype=np.float64) for t in films)
+            if v.size != n * self.channels or l.size != v.size or w.size != n:
+                raise ValueError("film_compare_host: films of the scene's size expected")
+            sets.append((v, w, l))
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+        if m is not None and m.size != n:
+            raise ValueError("film_compare_host: a mask of the scene's size expected")
+        d = {}
+
+        def call(spec, rec, planes):
+            if diff:
+                d["diff"] = np.zeros((self.height, self.width, planes), dtype=np.float32)
+            _check(load_library().wtgpu_film_compare_host(self._h, *(t.ctypes.data for t in sets[0]), int(spe_a), *(t.ctypes.data for t in sets[1]), int(spe_b),
+                                                          C.byref(spec), None if m is None else m.ctypes.data, int(threads), C.cast(rec, C.c_void_p),
+                                                          d["diff"].ctypes.data if diff else None))
+        out = self._film_compare(call, stokes_component, abs, luminance, eps)
+        out.update(d)
+        return out
 
     def profile_counters(self, n=8):
         """Test hook (wtgpu_test_hooks.h): the first n WTGPU_PROFILE scratch counters, accumulated since upload."""

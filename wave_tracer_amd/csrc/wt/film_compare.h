@@ -1,0 +1,91 @@
+// wave_tracer_amd — comparison of two films (difference statistics, noise estimate): the arithmetic the device kernels (kernels_compare.hip) and
+// their host twin share.
+//
+// Planes.  As in wt/film_stats.h: plane c is the developed value of film plane  c * stokes + stokes_component;  FC_LUMINANCE (3-channel films)
+// adds tm_luminance of the three developed values (taken before FC_ABS), so there are at most kFsMaxPlanes = 4; FC_ABS takes fabsf of both
+// values.  An included pixel gives per plane the pair  xa = develop_plane(A.., spe_a),  xb = develop_plane(B.., spe_b): the f32 wtgpu_develop writes.
+// Membership.  A pixel is included iff no mask is given or mask[pixel] > 0 (a NaN mask value excludes).
+// Classes.  A member pair is exactly one of
+//   non-finite  either value is NaN or infinite: counted in n_nonfinite, and in n_nonfinite_mismatch unless both are NaN or xa == xb (equal
+//               infinities); it enters no sum and not the maximum;
+//   finite      d = (double)xa - (double)xb; counted in n_differ iff xa != xb (-0 and +0 do not differ).
+// Record per plane.  n members, the three counts, max_abs = max |d| over the finite pairs and argmax, the row-major index of the pixel that has
+// it — the lowest on a tie; 0 and UINT64_MAX where no finite pair differs (fc_best_t) — and five f64 sums over the finite pairs:
+//   sum_abs  |d|     sum_sq  d d     sum_a_sq  xa xa     sum_b_sq  xb xb     sum_rel  d d / (xb xb + eps)      (eps: f64, finite, > 0)
+// Sum order.  wt/film_stats.h's, for each of the five: chunks of kFsChunk in row-major order, the butterfly at distances 128 .. 1, the chunk
+// sums by the same rule level after level, +0.0 for excluded, non-finite and missing elements (fs_chunk_sum, fs_chunks, fs_scratch_len).
+// Only f64  + - x /  and comparisons: nothing to contract (the library is built with -ffp-contract=off), no libm, so device and host agree on
+// every field bit for bit.
+// Difference plane.  [height][width][planes] f32:  xa - xb  as ONE f32 subtraction (whatever that gives for a non-finite pair: an infinity or a
+// NaN), 0.f for an excluded pixel.  A NaN is stored as THE quiet NaN 0x7fc00000: IEEE 754 leaves sign and payload of an invalid operation's
+// result open (inf - inf is a negative NaN on x86), and the plane is to be the same on every machine, bit for bit.
+#pragma once
+#include "film_stats.h"
+
+namespace wt {
+
+enum film_compare_flag_e : uint32_t { FC_ABS = 1u, FC_LUMINANCE = 2u };
+enum film_compare_sum_e : uint32_t { FC_SUM_ABS = 0, FC_SUM_SQ = 1, FC_SUM_A_SQ = 2, FC_SUM_B_SQ = 3, FC_SUM_REL = 4, kFcSums = 5 };
+constexpr unsigned long long kFcNoPixel = ~0ull;   // argmax where nothing differs
+
+// wtgpu_film_compare as the kernels fill it
+struct film_compare_rec_t {
+    unsigned long long n, n_nonfinite, n_nonfinite_mismatch, n_differ, argmax;
+    double max_abs;
+    double sum[kFcSums];
+};
+static_assert(sizeof(film_compare_rec_t) == 88, "wtgpu_film_compare");
+
+WT_HD bool fc_finite(float x) {
+    uint32_t u;
+    __builtin_memcpy(&u, &x, 4);
+    return (u & 0x7f800000u) != 0x7f800000u;
+}
+
+// What one pair gives: its class, its five addends (all +0.0 unless the pair is an included finite one) and its |d|.
+struct fc_pair_t {
+    uint32_t nonfinite, mismatch, differ;   // 0 or 1
+    double add[kFcSums];
+    double abs_d;
+};
+WT_HD fc_pair_t fc_pair(float xa, float xb, bool included, double eps) {
+    fc_pair_t r;
+    const bool fin = fc_finite(xa) && fc_finite(xb);
+    r.nonfinite = included && !fin ? 1u : 0u;
+    r.mismatch = r.nonfinite && !((xa != xa && xb != xb) || xa == xb) ? 1u : 0u;
+    r.differ = included && fin && xa != xb ? 1u : 0u;
+    const bool take = included && fin;
+    const double a = take ? (double)xa : 0.0, b = take ? (double)xb : 0.0, d = a - b, sq = d * d, bb = b * b;
+    r.abs_d = d < 0.0 ? -d : d;
+    r.add[FC_SUM_ABS] = r.abs_d;
+    r.add[FC_SUM_SQ] = sq;
+    r.add[FC_SUM_A_SQ] = a * a;
+    r.add[FC_SUM_B_SQ] = bb;
+    r.add[FC_SUM_REL] = sq / (bb + eps);
+    return r;
+}
+
+// The largest |d| met so far and the pixel that has it.  Only a pair with |d| > 0 is a candidate, and among equal candidates the lower pixel
+// wins: a total order, so the result does not depend on the order the pairs (or the partial results of lanes, wavefronts, threads) are merged in.
+struct fc_best_t {
+    double v = 0.0;
+    unsigned long long pixel = kFcNoPixel;
+};
+WT_HD void fc_best_merge(fc_best_t& m, double v, unsigned long long pixel) {   // (selects, no branches: the kernel runs this per pair)
+    const bool take = (v > m.v) | ((v == m.v) & (pixel < m.pixel));
+    m.v = take ? v : m.v;
+    m.pixel = take ? pixel : m.pixel;
+}
+WT_HD void fc_best_take(fc_best_t& m, double abs_d, unsigned long long pixel) { fc_best_merge(m, abs_d, abs_d > 0.0 ? pixel : kFcNoPixel); }
+
+WT_HD float fc_element(float x, uint32_t flags) { return (flags & FC_ABS) ? fabsf(x) : x; }
+// an element of the difference plane
+WT_HD float fc_diff(float xa, float xb, bool included) {
+    const float d = xa - xb;
+    const uint32_t u = 0x7fc00000u;
+    float nan;
+    __builtin_memcpy(&nan, &u, 4);
+    return included ? (d == d ? d : nan) : 0.f;
+}
+
+}   // namespace wt

@@ -6,7 +6,7 @@
 //   wtgpu_knobs.hip      the environment knobs: one table, read_knobs (wtgpu_knobs.h; plain C++)
 //   wtgpu_trace_ab.hip   WTGPU_TRACE_AB replay harness, the alternative forms of the per-lane traversal
 //   wtgpu_counters.hip   wtgpu_get_counters and its profile printers, reset
-//   wtgpu_queries.hip    ray / cone / region queries, sensor masks, the test probes, develop and tonemap, film statistics
+//   wtgpu_queries.hip    ray / cone / region queries, sensor masks, the test probes, develop and tonemap, film statistics, film comparison
 //   wtgpu_control.hip    cancel / pause / resume / capture / progressive render; the RCCL film reduction
 #pragma once
 #include <hip/hip_runtime.h>
@@ -111,6 +111,11 @@ struct wtgpu_scene {
     unsigned char* h_fs = nullptr;       // the same block pinned on the host,
     double* d_fs_sums = nullptr;         // the chunk sums of every level of the fixed summation order (wt/film_stats.h: fs_scratch_len)
     uint32_t fs_cus = 0;                 // compute units of the device: the grid's upper end
+    unsigned char* d_fc = nullptr;       // wtgpu_film_compare_device, allocated at its first call: the records on the device,
+    unsigned char* h_fc = nullptr;       // the same block pinned on the host,
+    double* d_fc_sums = nullptr;         // the chunk sums of every level, five sums per plane (wt/film_compare.h),
+    unsigned char* d_fc_wave = nullptr;  // the wavefronts' records (kernels_compare.hip: film_compare_wave_bytes)
+    uint32_t fc_cus = 0;
     // WTGPU_TRACE_AB (diagnostic, tests/test_gpu_traversal.py): accumulated over the replayed rounds — milliseconds of k_trace_refill / k_trace_sm on the
     // same queue, words of their outputs that differ (traversal records + triangle lists + heavy-queue checksums), walks replayed
     double ab_ms[2] = {0, 0};

@@ -9,6 +9,7 @@
 //   kernels_mask.hip    k_sensor_mask_wave / k_sensor_mask_lane: by-geometry sensor masks (not part of a render)
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
+//   kernels_compare.hip k_film_compare / k_film_compare_finish: difference statistics of two films (not part of a render)
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -433,6 +434,17 @@ int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, co
                       uint32_t flags, const float* d_mask, const float* d_edges, uint32_t bins, void* d_rec, unsigned long long* d_hist, double* d_sums);
 void film_stats_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, uint32_t s, uint32_t flags, const float* mask,
                      const float* edges, uint32_t bins, uint32_t n_threads, void* out_rec, unsigned long long* out_hist);
+// kernels_compare.hip: comparison of two films (wtgpu_film_compare_device / wtgpu_film_compare_host; wt/film_compare.h).  Two sets of films as wtgpu_render fills
+// them (the same pointers twice are fine); s: the Stokes component; flags: FC_ABS | FC_LUMINANCE; eps: finite, > 0.  d_rec: film_compare_rec_t per plane;
+// d_sums: kFsMaxPlanes x kFcSums x fs_scratch_len(pixels) doubles; d_wave: film_compare_wave_bytes(pixels, n_cus) bytes — none of them has to be
+// cleared; d_diff: null or [height][width][planes] f32.  Two kernels on `stream`; the launch returns a hipError_t.
+size_t film_compare_wave_bytes(uint64_t npix, uint32_t n_cus);
+int film_compare_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                        const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, uint32_t s, uint32_t flags, double eps, const float* d_mask,
+                        void* d_rec, double* d_sums, void* d_wave, float* d_diff);
+void film_compare_host(const sensor_t& sn, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                       const double* b_weight, const double* b_light, uint64_t spe_b, uint32_t s, uint32_t flags, double eps, const float* mask, uint32_t n_threads,
+                       void* out_rec, float* diff);
 
 }   // namespace wtk
 using namespace wtk;

@@ -4,6 +4,7 @@
 #include "wt/sources_probe.h"
 #include "wt/tonemap.h"
 #include "wt/film_stats.h"
+#include "wt/film_compare.h"
 
 extern "C" {
 
@@ -380,6 +381,74 @@ int wtgpu_film_stats_host(const wtgpu_scene* s, const double* value, const doubl
     try {
         film_stats_host(s->host.sensor, value, weight, light, spe, spec->stokes_component, spec->flags, mask, edges, spec->bins, n_threads, out,
                         reinterpret_cast<unsigned long long*>(hist));
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+
+
+// ---- film comparison (kernels_compare.hip; wt/film_compare.h) -------------------------------------------------------------------------------
+static_assert(sizeof(wtgpu_film_compare) == sizeof(film_compare_rec_t), "the kernels' record is wtgpu_film_compare");
+// what a spec says by itself and against the scene's film; planes: records per call
+static int film_compare_check(const wtgpu_scene* s, const wtgpu_film_compare_spec* spec, uint32_t& planes) {
+    const sensor_t& sn = s->host.sensor;
+    if (spec->flags & ~(FC_ABS | FC_LUMINANCE)) return fail(WTGPU_ERR_INVALID, "film_compare: flags 1 (ABS) and 2 (LUMINANCE) expected");
+    if (!std::isfinite(spec->eps) || !(spec->eps > 0.0)) return fail(WTGPU_ERR_INVALID, "film_compare: a finite eps > 0 expected");
+    if (sn.channels != 1 && sn.channels != 3) return fail(WTGPU_ERR_INVALID, "film_compare: a film of 1 or 3 channels expected");
+    if (spec->stokes_component >= film_stokes(sn))
+        return fail(WTGPU_ERR_INVALID, "film_compare: stokes_component " + std::to_string(spec->stokes_component) + " out of range (the film has " + std::to_string(film_stokes(sn)) + ")");
+    if ((spec->flags & FC_LUMINANCE) && sn.channels != 3) return fail(WTGPU_ERR_INVALID, "film_compare: LUMINANCE needs a 3-channel film (this one has " + std::to_string(sn.channels) + ")");
+    planes = sn.channels + ((spec->flags & FC_LUMINANCE) ? 1u : 0u);
+    return WTGPU_OK;
+}
+constexpr size_t kFcRecBytes = kFsMaxPlanes * sizeof(film_compare_rec_t);
+
+int wtgpu_film_compare_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                              const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec, const float* d_mask,
+                              wtgpu_film_compare* out, float* d_diff) {
+    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    uint32_t planes = 0;
+    if (const int rc = film_compare_check(s, spec, planes)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    const sensor_t& sn = s->host.sensor;
+    const uint64_t npix = (uint64_t)sn.width * sn.height;
+    if (npix == 0) return fail(WTGPU_ERR_INVALID, "film_compare: the film has no pixels");
+    device_guard_t guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!s->d_fc) {   // first use: the records, their pinned copy, the chunk sums (all levels, kFsMaxPlanes planes of kFcSums sums) and the wavefronts' records
+        unsigned char *d = nullptr, *wave = nullptr;
+        double* sums = nullptr;
+        int n_cu = 256;
+        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device);
+        const uint32_t cus = (uint32_t)std::max(1, n_cu);
+        if (const int rc = dmalloc(s, &d, kFcRecBytes)) return rc;
+        if (const int rc = dmalloc(s, &sums, (size_t)kFsMaxPlanes * kFcSums * fs_scratch_len(npix))) return rc;
+        if (const int rc = dmalloc(s, &wave, film_compare_wave_bytes(npix, cus))) return rc;
+        HIP_CHECK(hipHostMalloc((void**)&s->h_fc, kFcRecBytes, hipHostMallocDefault));
+        s->fc_cus = cus;
+        s->d_fc_sums = sums;
+        s->d_fc_wave = wave;
+        s->d_fc = d;
+    }
+    // The call waits for its own result below, so the block is free again when it returns.
+    const int e = film_compare_launch(sn, stream, s->fc_cus, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec->stokes_component, spec->flags, spec->eps,
+                                      d_mask, s->d_fc, s->d_fc_sums, s->d_fc_wave, d_diff);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_compare: ") + hipGetErrorString((hipError_t)e));
+    HIP_CHECK(hipMemcpyAsync(s->h_fc, s->d_fc, planes * sizeof(film_compare_rec_t), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    std::memcpy(out, s->h_fc, planes * sizeof(wtgpu_film_compare));
+    return WTGPU_OK;
+}
+int wtgpu_film_compare_host(const wtgpu_scene* s, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                            const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec, const float* mask, uint32_t n_threads,
+                            wtgpu_film_compare* out, float* diff) {
+    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    uint32_t planes = 0;
+    if (const int rc = film_compare_check(s, spec, planes)) return rc;
+    try {
+        film_compare_host(s->host.sensor, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec->stokes_component, spec->flags, spec->eps, mask, n_threads,
+                          out, diff);
     } catch (const std::exception& e) {
         return fail(WTGPU_ERR_INVALID, e.what());
     }

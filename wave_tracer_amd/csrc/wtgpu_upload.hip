@@ -319,6 +319,11 @@ void release_device(wtgpu_scene* s) {
     s->d_fs_sums = nullptr;
     if (s->h_fs) (void)hipHostFree(s->h_fs);
     s->h_fs = nullptr;
+    s->d_fc = nullptr;           // (freed with dev_allocs)
+    s->d_fc_sums = nullptr;
+    s->d_fc_wave = nullptr;
+    if (s->h_fc) (void)hipHostFree(s->h_fc);
+    s->h_fc = nullptr;
     s->uploaded = false;
 }
 

@@ -52,6 +52,70 @@ def auto_db_range(scene, films, spe, *, percentiles=(1, 99), mask=None):
     return float(lo), float(hi)
 
 
+def noise_estimate(scene, films_a, films_b, spe, *, mask=None):
+    """How noisy is the film that two half-films add up to?  films_a / films_b are (value, weight, light) of two renders of `spe` samples per element
+    each over DISJOINT sample ranges (render_to_noise interleaves them), torch tensors on the scene's device (Scene.film_compare_device: only one
+    record crosses to the host) or numpy arrays (Scene.film_compare_host).  Returns  ||a - b|| / ||a + b||  over the developed values of Stokes
+    component 0 — the luminance of an RGB film, the one plane of a monochromatic one — of the pixels where mask > 0.  With independent halves of
+    equal size, a - b has the variance of a + b, so the quotient estimates the relative RMS error of the merged film; it is an ESTIMATE: one
+    draw of a random quantity, blind to any bias the two halves share.  Computed as  sqrt(sum_sq / (2 sum_a_sq + 2 sum_b_sq - sum_sq))  from three
+    sums of squares (||a + b||^2 = 2 ||a||^2 + 2 ||b||^2 - ||a - b||^2), which spares the cancellation a sum of products a b would bring.  0 for
+    two all-zero films."""
+    compare = scene.film_compare_host if isinstance(films_a[0], np.ndarray) else scene.film_compare_device
+    lum = scene.spectral_channels == 3
+    c = compare(films_a, spe, films_b, spe, luminance=lum, mask=mask)
+    k = -1 if lum else 0
+    num, den = float(c["sum_sq"][k]), 2.0 * float(c["sum_a_sq"][k]) + 2.0 * float(c["sum_b_sq"][k]) - float(c["sum_sq"][k])
+    return float(np.sqrt(num / den)) if den > 0 else 0.0
+
+
+def _render_range_hip(scene, device):
+    """render_to_noise's default renderer: the HIP path into fresh films on the scene's GPU (there is no CPU fallback)."""
+    import torch
+    if scene.device is None:
+        scene.upload(device)
+    dev = torch.device("cuda", scene.device)
+
+    def renderer(begin, end, seed):
+        with torch.cuda.device(dev):
+            films = alloc_films(scene, dev)
+            scene.render_into(*films, begin, end, seed, torch.cuda.current_stream(dev).cuda_stream)
+        return films
+    return renderer
+
+
+def render_to_noise(scene, target, *, max_spp, chunk_spp=8, seed=1, device=0, mask=None, renderer=None):
+    """Renders until noise_estimate says the film is good enough, or until max_spp samples per element (even: both halves keep equal counts).  Two
+    film sets: pair i renders the samples [2 i c, (2 i + 1) c) into A and [(2 i + 1) c, (2 i + 2) c) into B, c = chunk_spp (the last pair is
+    shortened to what max_spp leaves); the RNG counter is (pixel, sample, stream), so A + B is the film one render of the same samples gives, up
+    to the order of its additions.  After every pair one noise_estimate of A against B (on the device nothing but its record is downloaded);
+    the loop stops when it is <= target.  `renderer(begin, end, seed) -> (value, weight, light)` (torch tensors, or numpy arrays for a CPU
+    renderer) stands in for the HIP path in tests, as shard_renderer does in render_distributed.
+    Returns ((value, weight, light) merged: A += B where the films are, samples per element, [(spp, estimate), ...] one entry per pair)."""
+    max_spp, c = int(max_spp), max(1, int(chunk_spp))
+    if max_spp < 2 or max_spp % 2:
+        raise ValueError(f"render_to_noise: an even max_spp >= 2 expected (two halves of equal size), got {max_spp}")
+    render_range = renderer or _render_range_hip(scene, device)
+    a = b = None
+    done, history = 0, []
+    while done < max_spp:
+        h = min(c, (max_spp - done) // 2)
+        parts = render_range(done, done + h, seed), render_range(done + h, done + 2 * h, seed)
+        if a is None:
+            a, b = parts
+        else:
+            for acc, part in zip((a, b), parts):
+                for t, u in zip(acc, part):
+                    t += u
+        done += 2 * h
+        history.append((done, noise_estimate(scene, a, b, done // 2, mask=mask)))
+        if history[-1][1] <= target:
+            break
+    for t, u in zip(a, b):
+        t += u
+    return a, done, history
+
+
 def render(scene, spp, seed=1, device=0, sample_begin=0):
     """Renders `spp` samples per element on one GPU; returns (value, weight, light) as numpy f64 arrays."""
     import torch
