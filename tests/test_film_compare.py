@@ -13,7 +13,7 @@ import math
 import numpy as np
 import pytest
 
-from test_film_stats import PLANES, butterfly_sum, checker, elements, option_cases, restate_edges, same_bits, stats_films, stats_scene
+from test_film_stats import LEVELS, PLANES, butterfly_sum, checker, elements, option_cases, restate_edges, same_bits, stats_films, stats_scene
 
 F32 = np.float32
 W, H = 37, 23
@@ -122,6 +122,20 @@ def test_host_twin_equals_the_restatement(scenes, P):
                 moved = not masked or mask.reshape(-1)[500] > 0
                 assert got["n_differ"][0] == int(moved) and got["argmax"][0] == (500 if moved else NO_PIXEL), case
                 assert not got["n_differ"][1:channels].any() and (got["argmax"][1:channels] == NO_PIXEL).all(), case
+
+
+def test_host_twin_equals_the_restatement_over_two_levels(built, tmp_path):
+    """At LEVELS (test_film_stats.py) the loop over the levels runs twice and its second pass reads what the first wrote.  Two draws of an RGB
+    film with its luminance under the checker mask, every field and the difference plane."""
+    w, h = LEVELS
+    sc = stats_scene(tmp_path, 3, w, h)
+    mask = checker(h, w)
+    fa, fb = films_of(3, 800, h, w), films_of(3, 801, h, w)
+    got = sc.film_compare_host(fa, SPE_A, fb, SPE_B, luminance=True, mask=mask, diff=True, threads=3)
+    want = restate_compare(elements(3, 1, fa, SPE_A, 0, False, True), elements(3, 1, fb, SPE_B, 0, False, True), mask, 1e-4)
+    assert got["diff"].shape == (h, w, 4) and (got["n"] == int((mask > 0).sum())).all()
+    check_against_restatement(got, want, LEVELS)
+    assert got["n_nonfinite"].all() and got["n_differ"].all() and all(got[name].all() for name in SUMS)
 
 
 def test_two_draws_meet_a_mismatch(scenes):

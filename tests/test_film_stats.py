@@ -15,6 +15,8 @@ from test_sensor_mask import _write
 from test_tonemap import F32, MONO, RGB, film_xml, restate_develop
 
 W, H = 37, 23                       # 851 pixels: three whole chunks of 256 and a part of a fourth
+LEVELS = (257, 256)                 # W x H = 65,792 pixels: 257 chunk sums, then 2 (the second of ONE sum), then 1 — the smallest film whose chunk sums take two levels
+assert [-(-LEVELS[0] * LEVELS[1] // 256), -(-(-(-LEVELS[0] * LEVELS[1] // 256)) // 256)] == [257, 2]
 PLANES = {1: (MONO, False, 1, 1), 3: (RGB, False, 3, 1), 4: (MONO, True, 1, 4), 12: (RGB, True, 3, 4)}     # P: response, polarimetric, channels, stokes
 BINS = [0, 1, 7, 256, 4096]
 RANGES = {"dB": (-50.0, 10.0), "linear": (0.25, 3.0)}
@@ -33,6 +35,18 @@ def stats_scene(d, P, width=W, height=H):
 def scenes(built, tmp_path_factory):
     d = tmp_path_factory.mktemp("film_stats")
     return {P: stats_scene(d, P) for P in PLANES}
+
+
+# what the two device test files (test_gpu_film_stats.py, test_gpu_film_compare.py) share
+def device_scenes(d, sizes):
+    """{(W, H, P): uploaded scene}: every plane count at `sizes`, P = 3 and 12 at LEVELS"""
+    return {(w, h, P): stats_scene(d, P, w, h).upload(0) for w, h in list(sizes) + [LEVELS] for P in (PLANES if (w, h) != LEVELS else (3, 12))}
+
+
+def to_device(sc, arrays):
+    import torch
+    dev = torch.device("cuda", sc.device)
+    return tuple(None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays)
 
 
 # ---- the restatement ------------------------------------------------------------------------------------------------------------------------
@@ -241,6 +255,22 @@ def test_host_twin_equals_the_restatement(scenes, P, bins):
                 if bins and not masked and not lum:     # the film was built to meet every class, and the three edges from both sides
                     assert got["n_nan"].all() and got["n_zero"].all() and got["n_below"].all() and got["n_above"].all() and (abs_ or got["n_negative"].all()), label
                     assert got["hist"][:, 0].all() and got["hist"][:, -1].all(), label
+
+
+def test_host_twin_equals_the_restatement_over_two_levels(built, tmp_path):
+    """At LEVELS the loop over the levels runs twice and its second pass reads what the first wrote; the last chunk of the level above the chunk
+    sums holds one sum.  An RGB film with its luminance under the checker mask, every field."""
+    w, h = LEVELS
+    sc = stats_scene(tmp_path, 3, w, h)
+    mask = checker(h, w)
+    lo, hi = RANGES["dB"]
+    edges = restate_edges("dB", lo, hi, 256)
+    for infinities in (False, True):
+        films = stats_films(h, w, 3, 1, 700 + infinities, edges, infinities)
+        got = sc.film_stats_host(*films, SPE, range=(lo, hi), bins=256, luminance=True, mask=mask, threads=3)
+        assert same_bits(got["edges"], edges) and got["hist"].shape == (4, 256) and (got["n"] == int((mask > 0).sum())).all()
+        check_against_restatement(got, restate_stats(elements(3, 1, films, SPE, 0, False, True), edges, mask), (LEVELS, infinities))
+        assert got["hist"].all(axis=1).any() and got["sum"].all()
 
 
 def test_the_edge_values_fall_where_the_classes_say(scenes):

@@ -2,7 +2,8 @@
 max_abs and argmax, the five sums and the difference plane — the additions have one order and the maximum's order is total
 (wt/film_compare.h), so there is nothing to tolerate.  The host twin itself is held to a numpy restatement by tests/test_film_compare.py, whose
 pairs and options are used here: P = 1, 3, 4, 12 planes at 37 x 23 (851 pixels: a part of one block, chunks that end inside the film) and one
-pair at 256 x 192 (192 chunks: 48 blocks, a second level of chunk sums).  Then rendered films, render_to_noise against the one-shot render, and
+pair at 256 x 192 (192 chunks: 48 blocks, a second level of chunk sums); P = 3 and 12 at 257 x 256 (257 chunks, then 2, then 1: the reduction's
+loop runs twice).  Then rendered films, render_to_noise against the one-shot render, and
 what the calls leave alone."""
 import ctypes as C
 
@@ -10,7 +11,8 @@ import numpy as np
 import pytest
 
 from test_film_compare import FIELDS, NO_PIXEL, SPE_A, SPE_B, films_of, pairs
-from test_film_stats import F32, PLANES, checker, option_cases, same_bits, stats_scene
+from test_film_stats import F32, LEVELS, PLANES, checker, device_scenes, option_cases, same_bits, stats_scene
+from test_film_stats import to_device as _to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -21,13 +23,7 @@ DERIVED = ("rmse", "mean_abs", "rel_l2", "rel_mse")
 @pytest.fixture(scope="module")
 def scenes(built, tmp_path_factory):
     d = tmp_path_factory.mktemp("gpu_film_compare")
-    return {(W, H, P): stats_scene(d, P, W, H).upload(0) for W, H in SIZES for P in PLANES}
-
-
-def _to_device(sc, arrays):
-    import torch
-    dev = torch.device("cuda", sc.device)
-    return tuple(None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays)
+    return device_scenes(d, SIZES)
 
 
 def _same(sc, fa, d_fa, spe_a, fb, d_fb, spe_b, mask, d_mask, label, **kw):
@@ -61,7 +57,17 @@ def test_device_equals_host_twin(scenes, P):
 
 @pytest.mark.parametrize("P", sorted(PLANES))
 def test_device_equals_host_twin_on_many_chunks(scenes, P):
-    W, H = SIZES[1]
+    _many_chunks(scenes, SIZES[1], P)
+
+
+@pytest.mark.parametrize("P", [3, 12])
+def test_device_equals_host_twin_over_two_levels(scenes, P):
+    """257 x 256: k_film_compare_finish goes round its loop twice, the second time over what the first wrote."""
+    _many_chunks(scenes, LEVELS, P)
+
+
+def _many_chunks(scenes, size, P):
+    W, H = size
     sc = scenes[(W, H, P)]
     _, _, channels, stokes = PLANES[P]
     fa, fb = films_of(P, 500 + P, H, W), films_of(P, 600 + P, H, W)
@@ -69,7 +75,7 @@ def test_device_equals_host_twin_on_many_chunks(scenes, P):
     mask = checker(H, W)
     d_mask, = _to_device(sc, (mask,))
     for s, abs_, lum, masked in option_cases(channels, stokes):
-        got = _same(sc, fa, d_fa, SPE_A, fb, d_fb, SPE_B, mask if masked else None, d_mask if masked else None, (P, "256 x 192"), stokes_component=s, abs=abs_,
+        got = _same(sc, fa, d_fa, SPE_A, fb, d_fb, SPE_B, mask if masked else None, d_mask if masked else None, (P, size), stokes_component=s, abs=abs_,
                     luminance=lum)
         assert got["n"][0] == (int((mask > 0).sum()) if masked else W * H) and got["n_differ"].all()
 

@@ -2,11 +2,13 @@
 min / max / min_positive and the sum — the classification compares f32 values with one f32 edge table and the additions have one order
 (wt/film_stats.h), so there is nothing to tolerate.  The host twin itself is held to a numpy restatement by tests/test_film_stats.py, whose
 films and options are used here: P = 1, 3, 4, 12 planes at 37 x 23 (851 pixels: a part of one block, chunks that end inside the film) and at
-256 x 192 (192 chunks: 48 blocks, a second level of chunk sums)."""
+256 x 192 (192 chunks: 48 blocks, a second level of chunk sums); P = 3 and 12 at 257 x 256 (257 chunks, then 2, then 1: the reduction's loop
+runs twice)."""
 import numpy as np
 import pytest
 
-from test_film_stats import BINS, F32, PLANES, RANGES, SPE, checker, option_cases, restate_edges, same_bits, stats_films, stats_scene
+from test_film_stats import BINS, F32, LEVELS, PLANES, RANGES, SPE, checker, device_scenes, option_cases, restate_edges, same_bits, stats_films, stats_scene
+from test_film_stats import to_device as _to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -17,13 +19,7 @@ FIELDS = ("n", "n_nan", "n_negative", "n_zero", "n_below", "n_above", "min", "ma
 @pytest.fixture(scope="module")
 def scenes(built, tmp_path_factory):
     d = tmp_path_factory.mktemp("gpu_film_stats")
-    return {(W, H, P): stats_scene(d, P, W, H).upload(0) for W, H in SIZES for P in PLANES}
-
-
-def _to_device(sc, arrays):
-    import torch
-    dev = torch.device("cuda", sc.device)
-    return tuple(None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays)
+    return device_scenes(d, SIZES)
 
 
 def _same(sc, films, d_films, mask, d_mask, label, spe=SPE, **kw):
@@ -52,6 +48,23 @@ def test_device_equals_host_twin(scenes, size, P):
                             abs=abs_, luminance=lum)
                 assert got["n"][0] == (int((mask > 0).sum()) if masked else W * H) and got["hist"].shape == (channels + lum, bins)
                 assert bins == 0 or got["hist"].any()
+
+
+@pytest.mark.parametrize("P", [3, 12])
+def test_device_equals_host_twin_over_two_levels(scenes, P):
+    """257 x 256: k_film_stats_finish goes round its loop twice, the second time over what the first wrote; 256 bins, every option case."""
+    W, H = LEVELS
+    sc = scenes[(W, H, P)]
+    _, _, channels, stokes = PLANES[P]
+    mask = checker(H, W)
+    d_mask, = _to_device(sc, (mask,))
+    lo, hi = RANGES["dB"]
+    films = stats_films(H, W, channels, stokes, 700 + P, restate_edges("dB", lo, hi, 256))
+    d_films = _to_device(sc, films)
+    for s, abs_, lum, masked in option_cases(channels, stokes):
+        got = _same(sc, films, d_films, mask if masked else None, d_mask if masked else None, (W, H, P), stokes_component=s, range=(lo, hi), bins=256, abs=abs_,
+                    luminance=lum)
+        assert got["n"][0] == (int((mask > 0).sum()) if masked else W * H) and got["hist"].shape == (channels + lum, 256) and got["hist"].any()
 
 
 def test_all_values_in_one_of_4096_bins(scenes):

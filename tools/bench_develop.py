@@ -11,16 +11,10 @@ the copy.  Also the two A/B choices of csrc/kernels_develop.hip, alternated the 
 variants' outputs are compared bit for bit.  Films are seeded random numbers: the time does not depend on their content.
 Prints one JSON line; --out also writes it to a file.  Needs a GPU.  Not part of bench.py."""
 import argparse
-import json
 import os
-import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-FILMS = {"cornell_1440": ("cornell_box", dict(res=1440, mesh_detail=0, lut=(32, 32))),
-         "bidir_room_1920_polarimetric": ("bidir_room", dict(res=1920, mesh_detail=0, lut=(32, 32), polarimetric=1))}
+from film_bench_util import FILMS, alternate, event_ms, finish, need_gpu
 
 
 def _scene(name, kw, env=None):
@@ -33,28 +27,6 @@ def _scene(name, kw, env=None):
     finally:
         for k, v in old.items():
             os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
-
-
-def _event_ms(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _alternate(fns, reps, warmup=3):
-    """fns: {label: callable -> ms or dict of ms}; every round calls each once, in turn.  Returns the medians."""
-    rows = {k: [] for k in fns}
-    for r in range(warmup + reps):
-        for k, fn in fns.items():
-            v = fn()
-            if r >= warmup:
-                rows[k].append(v)
-    med = lambda xs: statistics.median(xs)
-    return {k: ({f: med([x[f] for x in v]) for f in v[0]} if isinstance(v[0], dict) else med(v)) for k, v in rows.items()}
 
 
 def bench_film(label, reps):
@@ -85,7 +57,7 @@ def bench_film(label, reps):
 
     def new():
         t0 = time.perf_counter()
-        k_ms, pic = _event_ms(lambda: sc.tonemap_device(value, weight, light, spe, tm, 0, mask=mask, fmt="u8"))
+        k_ms, pic = event_ms(lambda: sc.tonemap_device(value, weight, light, spe, tm, 0, mask=mask, fmt="u8"))
         t1 = time.perf_counter()
         pic.cpu()
         t2 = time.perf_counter()
@@ -94,8 +66,8 @@ def bench_film(label, reps):
         return {"total_ms": (t2 - t0) * 1e3, "launch_and_wait_ms": (t1 - t0) * 1e3, "kernel_ms": k_ms, "copy_ms": (t2 - t1) * 1e3}
 
     out = {"film": [W, H, P], "bytes_f64_films": int(8 * (2 * value.numel() + weight.numel())), "bytes_rgba8": H * W * 4}
-    out.update(_alternate({"parent": parent, "new": new}, reps))
-    out["new_back_to_back"] = _alternate({"new": new}, reps)["new"]     # the new path alone, the GPU kept busy
+    out.update(alternate({"parent": parent, "new": new}, reps))
+    out["new_back_to_back"] = alternate({"new": new}, reps)["new"]     # the new path alone, the GPU kept busy
     # the films are read once: value and light whole (their lines are fetched whole whichever Stokes component is wanted), the weights, the mask
     moved = out["bytes_f64_films"] + 4 * H * W + out["bytes_rgba8"]
     out["new"]["kernel_GBps"] = moved / out["new"]["kernel_ms"] / 1e6
@@ -106,8 +78,8 @@ def bench_film(label, reps):
     torch.cuda.synchronize(dev)
     assert torch.equal(a.view(torch.int32), b.view(torch.int32)), "the two k_develop mappings differ"
     del a, b
-    out["k_develop_ms"] = _alternate({"lane_per_plane": lambda: _event_ms(lambda: sc.develop_device(value, weight, light, spe))[0],
-                                      "lane_per_pixel": lambda: _event_ms(lambda: per_pixel.develop_device(value, weight, light, spe))[0]}, reps)
+    out["k_develop_ms"] = alternate({"lane_per_plane": lambda: event_ms(lambda: sc.develop_device(value, weight, light, spe))[0],
+                                      "lane_per_pixel": lambda: event_ms(lambda: per_pixel.develop_device(value, weight, light, spe))[0]}, reps)
     # A/B 2: the colour table of k_develop_tonemap (colourmap mode: every pixel goes through the 256-entry table)
     lds = _scene(name, kw, {"WTGPU_TONEMAP_LDS_TABLE": "1"})
     tm_cm = {"op": "sRGB", "mode": "colourmap", "table": imageio.colour_table("turbo")}
@@ -116,8 +88,8 @@ def bench_film(label, reps):
     torch.cuda.synchronize(dev)
     assert torch.equal(a, b), "the two table placements differ"
     del a, b
-    out["k_develop_tonemap_colourmap_ms"] = _alternate({"table_through_caches": lambda: _event_ms(lambda: call(sc))[0],
-                                                        "table_in_lds": lambda: _event_ms(lambda: call(lds))[0]}, reps)
+    out["k_develop_tonemap_colourmap_ms"] = alternate({"table_through_caches": lambda: event_ms(lambda: call(sc))[0],
+                                                        "table_in_lds": lambda: event_ms(lambda: call(lds))[0]}, reps)
     return out
 
 
@@ -127,16 +99,9 @@ def main():
     ap.add_argument("--films", default=",".join(FILMS))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("bench_develop.py needs a GPU: a time taken anywhere else says nothing")
+    need_gpu("bench_develop")
     res = {"tool": "bench_develop", "reps": max(15, args.reps), "films": {f: bench_film(f, max(15, args.reps)) for f in args.films.split(",")}}
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    finish(res, args.out)
 
 
 if __name__ == "__main__":

@@ -13,37 +13,10 @@ quotient is to be held against the HBM read rate.  --kernel-only runs the device
 its own.  Films are seeded random numbers, log-uniform over eight decades; B is A with noise of a few per cent.
 Prints one JSON line; --out also writes it to a file.  Needs a GPU.  Not part of bench.py."""
 import argparse
-import json
-import os
-import statistics
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-FILMS = {"cornell_1440": ("cornell_box", dict(res=1440, mesh_detail=0, lut=(32, 32))),
-         "bidir_room_1920_polarimetric": ("bidir_room", dict(res=1920, mesh_detail=0, lut=(32, 32), polarimetric=1))}
-
-
-def _event_ms(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _alternate(fns, reps, warmup=3):
-    """fns: {label: callable -> dict of ms}; every round calls each once, in turn.  Returns the medians."""
-    rows = {k: [] for k in fns}
-    for r in range(warmup + reps):
-        for k, fn in fns.items():
-            v = fn()
-            if r >= warmup:
-                rows[k].append(v)
-    return {k: {f: statistics.median([x[f] for x in v]) for f in v[0]} for k, v in rows.items()}
+from film_bench_util import FILMS, alternate, event_ms, finish, log_uniform_films, need_gpu
 
 
 def make_films(label):
@@ -53,10 +26,7 @@ def make_films(label):
     sc = Scene(name, **kw).upload(0, 65536)     # a small batch: nothing is rendered here
     dev = torch.device("cuda", 0)
     H, W, P = sc.height, sc.width, sc.channels
-    g = torch.Generator(device=dev).manual_seed(1)
-    weight = torch.rand((H, W), dtype=torch.float64, device=dev, generator=g) * 40 + 1
-    value = 10.0 ** (torch.rand((H, W, P), dtype=torch.float64, device=dev, generator=g) * 8 - 6) * weight[..., None]
-    light = torch.rand((H, W, P), dtype=torch.float64, device=dev, generator=g) * 1e-7
+    g, value, weight, light = log_uniform_films(sc, dev)
     value_b = value * (1 + 0.03 * (torch.rand((H, W, P), dtype=torch.float64, device=dev, generator=g) - 0.5))
     value_b[::3] = value[::3]                   # a third of the rows agree exactly
     return sc, (value, weight, light), (value_b, weight.clone(), light.clone())
@@ -99,14 +69,14 @@ def bench_film(label, reps):
     planes = sc.spectral_channels
     out = {"film": [W, H, sc.channels], "bytes_two_f64_film_sets": films_bytes, "bytes_diff_plane": 4 * H * W * planes, "paths_agree": agree,
            "rel_l2": [float(x) for x in n["rel_l2"]], "n_differ": [int(x) for x in n["n_differ"]]}
-    out.update(_alternate({"parent": strip(parent), "new": strip(new)}, reps))
-    out["new_back_to_back"] = _alternate({"new": strip(new)}, reps)["new"]     # the new path alone, the GPU kept busy
+    out.update(alternate({"parent": strip(parent), "new": strip(new)}, reps))
+    out["new_back_to_back"] = alternate({"new": strip(new)}, reps)["new"]     # the new path alone, the GPU kept busy
     # one call = k_film_compare + k_film_compare_finish + the copy of the records, between two device events
     lum = planes == 3
-    passes = _alternate({"records": lambda: {"ms": _event_ms(lambda: sc.film_compare_device(a, spe, b, spe))[0]},
-                         "records_luminance": lambda: {"ms": _event_ms(lambda: sc.film_compare_device(a, spe, b, spe, luminance=lum))[0]},
-                         "records_and_diff": lambda: {"ms": _event_ms(lambda: sc.film_compare_device(a, spe, b, spe, diff=True))[0]},
-                         "same_pointers": lambda: {"ms": _event_ms(lambda: sc.film_compare_device(a, spe, a, spe))[0]}}, reps)
+    passes = alternate({"records": lambda: {"ms": event_ms(lambda: sc.film_compare_device(a, spe, b, spe))[0]},
+                         "records_luminance": lambda: {"ms": event_ms(lambda: sc.film_compare_device(a, spe, b, spe, luminance=lum))[0]},
+                         "records_and_diff": lambda: {"ms": event_ms(lambda: sc.film_compare_device(a, spe, b, spe, diff=True))[0]},
+                         "same_pointers": lambda: {"ms": event_ms(lambda: sc.film_compare_device(a, spe, a, spe))[0]}}, reps)
     out["device_events"] = {k: {"ms": v["ms"], "films_GBps": films_bytes / v["ms"] / 1e6} for k, v in passes.items()}
     return out
 
@@ -129,19 +99,12 @@ def main():
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("bench_film_compare.py needs a GPU: a time taken anywhere else says nothing")
+    need_gpu("bench_film_compare")
     if args.kernel_only:
         res = {"tool": "bench_film_compare", "kernel_only": {f: kernel_only(f, 20) for f in args.films.split(",")}}
     else:
         res = {"tool": "bench_film_compare", "reps": max(15, args.reps), "films": {f: bench_film(f, max(15, args.reps)) for f in args.films.split(",")}}
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    finish(res, args.out)
     if not args.kernel_only and not all(f["paths_agree"] for f in res["films"].values()):
         sys.exit("the two paths disagree")
 

@@ -13,37 +13,9 @@ once (of a polarimetric film the lines of all four Stokes components are fetched
 against the HBM read rate.  Films are seeded random numbers, log-uniform over eight decades.
 Prints one JSON line; --out also writes it to a file.  Needs a GPU.  Not part of bench.py."""
 import argparse
-import json
-import os
-import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-FILMS = {"cornell_1440": ("cornell_box", dict(res=1440, mesh_detail=0, lut=(32, 32))),
-         "bidir_room_1920_polarimetric": ("bidir_room", dict(res=1920, mesh_detail=0, lut=(32, 32), polarimetric=1))}
-
-
-def _event_ms(fn):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), out
-
-
-def _alternate(fns, reps, warmup=3):
-    """fns: {label: callable -> dict of ms}; every round calls each once, in turn.  Returns the medians."""
-    rows = {k: [] for k in fns}
-    for r in range(warmup + reps):
-        for k, fn in fns.items():
-            v = fn()
-            if r >= warmup:
-                rows[k].append(v)
-    return {k: {f: statistics.median([x[f] for x in v]) for f in v[0]} for k, v in rows.items()}
+from film_bench_util import FILMS, alternate, event_ms, finish, log_uniform_films, need_gpu
 
 
 def bench_film(label, reps):
@@ -54,10 +26,7 @@ def bench_film(label, reps):
     sc = Scene(name, **kw).upload(0, 65536)     # a small batch: nothing is rendered here
     dev = torch.device("cuda", 0)
     H, W, P, stokes = sc.height, sc.width, sc.channels, sc.stokes
-    g = torch.Generator(device=dev).manual_seed(1)
-    weight = torch.rand((H, W), dtype=torch.float64, device=dev, generator=g) * 40 + 1
-    value = 10.0 ** (torch.rand((H, W, P), dtype=torch.float64, device=dev, generator=g) * 8 - 6) * weight[..., None]
-    light = torch.rand((H, W, P), dtype=torch.float64, device=dev, generator=g) * 1e-7
+    _, value, weight, light = log_uniform_films(sc, dev)
     spe = 16
 
     def parent():
@@ -88,13 +57,13 @@ def bench_film(label, reps):
     strip = lambda fn: (lambda: {k: v for k, v in fn().items() if not k.startswith("_")})
     films_bytes = int(8 * (2 * value.numel() + weight.numel()))
     out = {"film": [W, H, P], "bytes_f64_films": films_bytes}
-    out.update(_alternate({"parent": strip(parent), "new": strip(new)}, reps))
-    out["new_back_to_back"] = _alternate({"new": strip(new)}, reps)["new"]     # the new path alone, the GPU kept busy
+    out.update(alternate({"parent": strip(parent), "new": strip(new)}, reps))
+    out["new_back_to_back"] = alternate({"new": strip(new)}, reps)["new"]     # the new path alone, the GPU kept busy
     # one call = memset + edge upload + k_film_stats + k_film_stats_finish + result copy, between two device events
     lo, hi = sc.film_stats_device(value, weight, light, spe)["range"]
-    passes = _alternate({"range_pass": lambda: {"ms": _event_ms(lambda: sc.film_stats_device(value, weight, light, spe, range=(0.0, 0.0), bins=0))[0]},
-                         "histogram_pass": lambda: {"ms": _event_ms(lambda: sc.film_stats_device(value, weight, light, spe, range=(lo, hi), bins=256))[0]},
-                         "histogram_pass_4096": lambda: {"ms": _event_ms(lambda: sc.film_stats_device(value, weight, light, spe, range=(lo, hi), bins=4096))[0]}}, reps)
+    passes = alternate({"range_pass": lambda: {"ms": event_ms(lambda: sc.film_stats_device(value, weight, light, spe, range=(0.0, 0.0), bins=0))[0]},
+                         "histogram_pass": lambda: {"ms": event_ms(lambda: sc.film_stats_device(value, weight, light, spe, range=(lo, hi), bins=256))[0]},
+                         "histogram_pass_4096": lambda: {"ms": event_ms(lambda: sc.film_stats_device(value, weight, light, spe, range=(lo, hi), bins=4096))[0]}}, reps)
     out["device_events"] = {k: {"ms": v["ms"], "films_GBps": films_bytes / v["ms"] / 1e6} for k, v in passes.items()}
     return out
 
@@ -105,16 +74,9 @@ def main():
     ap.add_argument("--films", default=",".join(FILMS))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("bench_film_stats.py needs a GPU: a time taken anywhere else says nothing")
+    need_gpu("bench_film_stats")
     res = {"tool": "bench_film_stats", "reps": max(15, args.reps), "films": {f: bench_film(f, max(15, args.reps)) for f in args.films.split(",")}}
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    finish(res, args.out)
 
 
 if __name__ == "__main__":

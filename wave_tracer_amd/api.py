@@ -522,8 +522,7 @@ class Scene:
         dev = torch.device("cuda", self.device)
         n, flags = self._mask_args(samples, shapes)
         out = torch.empty((self.height, self.width), dtype=torch.float32, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        _check(load_library().wtgpu_sensor_mask(self._h, C.c_void_p(st) if st else None, None if flags is None else flags.ctypes.data, n, int(seed),
+        _check(load_library().wtgpu_sensor_mask(self._h, self._stream_arg(stream, dev), None if flags is None else flags.ctypes.data, n, int(seed),
                                                 out.data_ptr()))
         return out
 
@@ -560,6 +559,23 @@ class Scene:
                      float(db[0]), float(db[1]), None if tab is None else tab.ctypes.data_as(C.POINTER(C.c_float)), 0 if tab is None else len(tab))
         return st, tab
 
+    @staticmethod
+    def _stream_arg(stream, dev):
+        """The void* a device entry point takes for `stream` (None: torch's current stream on `dev`; its null stream goes as NULL)."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        return C.c_void_p(st) if st else None
+
+    def _host_films(self, what, value, weight, light, mask=None):
+        """_device_films' numpy mirror for the host twins: contiguous f64 films (and an f32 mask or None) of the scene's size, or a refusal."""
+        import numpy as np
+        v, w, l = (np.ascontiguousarray(t, dtype=np.float64) for t in (value, weight, light))
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+        n = self.width * self.height
+        if v.size != n * self.channels or l.size != v.size or w.size != n or (m is not None and m.size != n):
+            raise ValueError(f"{what}: films of the scene's size expected")
+        return v, w, l, m
+
     def _device_films(self, what, value, weight, light, mask=None):
         """The device entry points read the films by their sizes: refuse tensors of another size, type or device before a kernel does."""
         import torch
@@ -580,8 +596,7 @@ class Scene:
         import torch
         dev = self._device_films("develop_device", value, weight, light)
         out = torch.empty(tuple(value.shape), dtype=torch.float32, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        _check(load_library().wtgpu_develop_device(self._h, C.c_void_p(st) if st else None, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
+        _check(load_library().wtgpu_develop_device(self._h, self._stream_arg(stream, dev), value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
                                                    out.data_ptr()))
         return out
 
@@ -595,8 +610,7 @@ class Scene:
         st_tm, keep = self._tonemap_struct(tm)
         dtype = {"f32": torch.float32, "u8": torch.uint8, "u16": torch.int16}[fmt]
         out = torch.empty((self.height, self.width, 4 if mask is not None else 3), dtype=dtype, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        _check(load_library().wtgpu_tonemap_device(self._h, C.c_void_p(st) if st else None, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
+        _check(load_library().wtgpu_tonemap_device(self._h, self._stream_arg(stream, dev), value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
                                                    None if st_tm is None else C.byref(st_tm), int(stokes_component),
                                                    None if mask is None else mask.data_ptr(), TONEMAP_FORMATS[fmt], out.data_ptr()))
         del keep
@@ -606,13 +620,7 @@ class Scene:
         """The same computation on host threads from numpy films (wtgpu_tonemap_host; threads 0 = all cores): a numpy array H x W x 3 (x 4 with
         a mask) of float32 / uint8 / uint16.  No device needed."""
         import numpy as np
-        v = np.ascontiguousarray(value, dtype=np.float64)
-        w = np.ascontiguousarray(weight, dtype=np.float64)
-        l = np.ascontiguousarray(light, dtype=np.float64)
-        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
-        n = self.width * self.height
-        if v.size != n * self.channels or l.size != v.size or w.size != n or (m is not None and m.size != n):
-            raise ValueError("tonemap_host: films of the scene's size expected")
+        v, w, l, m = self._host_films("tonemap_host", value, weight, light, mask)
         st_tm, keep = self._tonemap_struct(tm)
         out = np.zeros((self.height, self.width, 4 if m is not None else 3), {"f32": np.float32, "u8": np.uint8, "u16": np.uint16}[fmt])
         _check(load_library().wtgpu_tonemap_host(self._h, v.ctypes.data, w.ctypes.data, l.ctypes.data, int(spe), None if st_tm is None else C.byref(st_tm),
@@ -669,13 +677,12 @@ class Scene:
         range=None: two passes, the first without bins for the smallest positive (dB) or smallest (linear) and the largest element.
         Returns a dict of numpy arrays indexed by plane: n, n_nan, n_negative, n_zero, n_below, n_above (uint64), min, max, min_positive
         (float32), sum (float64), hist [planes, bins] uint64; and edges [bins + 1] float32, scale, range, bins.  imageio.percentiles reads it."""
-        import torch
         dev = self._device_films("film_stats_device", value, weight, light, mask)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        st = self._stream_arg(stream, dev)
         lib = load_library()
 
         def call(spec, rec, hist):
-            _check(lib.wtgpu_film_stats_device(self._h, C.c_void_p(st) if st else None, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
+            _check(lib.wtgpu_film_stats_device(self._h, st, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
                                                C.byref(spec), None if mask is None else mask.data_ptr(), C.cast(rec, C.c_void_p), hist))
         return self._film_stats("film_stats_device", call, stokes_component, scale, range, bins, abs, luminance)
 
@@ -683,14 +690,7 @@ class Scene:
                         threads=0):
         """film_stats_device's twin on host threads from numpy films (wtgpu_film_stats_host; threads 0 = all cores): the same dict, every field bit
         for bit the device's.  No device needed."""
-        import numpy as np
-        v = np.ascontiguousarray(value, dtype=np.float64)
-        w = np.ascontiguousarray(weight, dtype=np.float64)
-        l = np.ascontiguousarray(light, dtype=np.float64)
-        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
-        n = self.width * self.height
-        if v.size != n * self.channels or l.size != v.size or w.size != n or (m is not None and m.size != n):
-            raise ValueError("film_stats_host: films of the scene's size expected")
+        v, w, l, m = self._host_films("film_stats_host", value, weight, light, mask)
         lib = load_library()
 
         def call(spec, rec, hist):
@@ -727,13 +727,13 @@ class Scene:
         import torch
         dev = self._device_films("film_compare_device", *films_a, mask)
         self._device_films("film_compare_device", *films_b)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        st = self._stream_arg(stream, dev)
         d = {}
 
         def call(spec, rec, planes):
             if diff:
                 d["diff"] = torch.empty((self.height, self.width, planes), dtype=torch.float32, device=dev)
-            _check(load_library().wtgpu_film_compare_device(self._h, C.c_void_p(st) if st else None, *(t.data_ptr() for t in films_a), int(spe_a),
+            _check(load_library().wtgpu_film_compare_device(self._h, st, *(t.data_ptr() for t in films_a), int(spe_a),
                                                             *(t.data_ptr() for t in films_b), int(spe_b), C.byref(spec), None if mask is None else mask.data_ptr(),
                                                             C.cast(rec, C.c_void_p), d["diff"].data_ptr() if diff else None))
         out = self._film_compare(call, stokes_component, abs, luminance, eps)
@@ -744,15 +744,9 @@ class Scene:
         """film_compare_device's twin on host threads from numpy films (wtgpu_film_compare_host; threads 0 = all cores): the same dict, every field bit
         for bit the device's, "diff" a numpy array.  No device needed."""
         import numpy as np
-        n = self.width * self.height
-        sets = []
-        for films in (films_a, films_b):
-            v, w, l = (np.ascontiguousarray(t, dtype=np.float64) for t in films)
-            if v.size != n * self.channels or l.size != v.size or w.size != n:
-                raise ValueError("film_compare_host: films of the scene's size expected")
-            sets.append((v, w, l))
+        sets = [self._host_films("film_compare_host", *films)[:3] for films in (films_a, films_b)]
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
-        if m is not None and m.size != n:
+        if m is not None and m.size != self.width * self.height:
             raise ValueError("film_compare_host: a mask of the scene's size expected")
         d = {}
 

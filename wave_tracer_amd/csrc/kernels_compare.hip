@@ -5,24 +5,16 @@
 // k_film_compare_finish reduces the chunk sums level after level and merges the wavefronts' records.  No atomics: every field is the same
 // whatever the schedule.  The arithmetic is wt/film_compare.h's, shared with the host twin at the end of the file: every count, the maximum and
 // its pixel, the five sums and the difference plane are the same on both sides, bit for bit.  No render kernel is compiled here.
-#include <algorithm>
-#include <atomic>
 #include <cstring>
 #include <mutex>
-#include <thread>
-#include <vector>
 
-#include "wtgpu_kernels.h"
+#include "kernels_film.h"
 #include "wt/film_compare.h"
 
 namespace wtk {
 
-constexpr int kCompareBlock = 256;                       // four wavefronts; a wavefront owns whole chunks of kFsChunk = 256 pixels
-constexpr uint32_t kCompareWaves = kCompareBlock / 64;
-static_assert(kFsChunk == 4 * 64, "a lane holds four elements of a chunk");
-// A lane's u32 counts cannot overflow: it meets four pixels per chunk and a wavefront takes at most kCompareMaxChunksPerWave chunks (the grid grows
-// with the film beyond that), so a wavefront's counts stay below 64 x 4 x 2^20 = 2^28.
-constexpr uint64_t kCompareMaxChunksPerWave = 1ull << 20;
+// A lane's u32 counts cannot overflow: it meets four pixels per chunk and a wavefront takes at most kFilmMaxChunksPerWave chunks, so a
+// wavefront's counts stay below 64 x 4 x 2^20 = 2^28.
 constexpr uint32_t kCompareBlocksPerCU = 8;
 
 // what a wavefront leaves behind for one plane
@@ -33,17 +25,7 @@ struct fc_wave_rec_t {
 };
 static_assert(sizeof(fc_wave_rec_t) == 32, "fc_wave_rec_t");
 
-// the butterfly's distances 32 .. 1 inside a wavefront: lane i adds lane i + d; lane 0 ends with the sum of the 64
-WT_D double fc_wave_butterfly(double t) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) t += __shfl_down(t, d, 64);
-    return t;
-}
-WT_D unsigned long long fc_wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;
-}
+// the largest difference of a wavefront's lanes, by the distances of kernels_film.h's reductions
 WT_D fc_best_t fc_wave_best(fc_best_t m) {
 #pragma unroll
     for (int d = 32; d; d >>= 1) {
@@ -55,20 +37,18 @@ WT_D fc_best_t fc_wave_best(fc_best_t m) {
 }
 
 // ---- k_film_compare: two sets of f64 films [H][W][P], [H][W] -> chunk sums, wavefront records, difference plane ------------------------------
-// One lane per pixel.  Wavefront g of the grid takes chunks g, g + waves, ...; of chunk k lane l holds pixels 256 k + 64 j + l, j = 0 .. 3 (four
-// loads of 64 consecutive pixels), so the butterfly's distances 128 and 64 are the lane's own (t0 + t2) + (t1 + t3) and the rest are shuffles: no
-// LDS, no barrier.  The loads are unconditional (a pixel past the film's end re-reads the last one) so that all of a chunk's are in flight
-// together; `included` gates what they give.  A chunk's developed pairs stay in registers as f32 while ONE plane at a time has its twenty
-// f64 addends live.  Counts and the largest difference are per-lane registers over all the wavefront's chunks, reduced once at its end.
+// One lane per pixel, in the chunk geometry of kernels_film.h.  The loads are unconditional (a pixel past the film's end re-reads the last
+// one) so that all of a chunk's are in flight together; `included` gates what they give.  A chunk's developed pairs stay in registers as f32
+// while ONE plane at a time has its twenty f64 addends live.  Counts and the largest difference are per-lane registers over all the wavefront's chunks, reduced once at its end.
 template <uint32_t C, bool kLum>
-__global__ void __launch_bounds__(kCompareBlock) k_film_compare(const double* __restrict__ a_value, const double* __restrict__ a_weight, const double* __restrict__ a_light,
-                                                                double sl_a, const double* __restrict__ b_value, const double* __restrict__ b_weight,
-                                                                const double* __restrict__ b_light, double sl_b, uint32_t stokes, uint32_t s, uint32_t flags, double eps,
-                                                                const float* __restrict__ mask, uint64_t npix, double* __restrict__ sums, uint64_t sums_stride,
-                                                                fc_wave_rec_t* __restrict__ wrec, float* __restrict__ diff) {
+__global__ void __launch_bounds__(kFilmBlock) k_film_compare(const double* __restrict__ a_value, const double* __restrict__ a_weight, const double* __restrict__ a_light,
+                                                             double sl_a, const double* __restrict__ b_value, const double* __restrict__ b_weight,
+                                                             const double* __restrict__ b_light, double sl_b, uint32_t stokes, uint32_t s, uint32_t flags, double eps,
+                                                             const float* __restrict__ mask, uint64_t npix, double* __restrict__ sums, uint64_t sums_stride,
+                                                             fc_wave_rec_t* __restrict__ wrec, float* __restrict__ diff) {
     constexpr uint32_t NP = C + (kLum ? 1u : 0u);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t n_chunks = fs_chunks(npix), n_waves = (uint64_t)gridDim.x * kCompareWaves, wave = (uint64_t)blockIdx.x * kCompareWaves + (threadIdx.x >> 6);
+    const uint64_t n_chunks = fs_chunks(npix), n_waves = film_waves(), wave = film_first_chunk();
     fc_best_t best[NP];
     uint32_t n_nonfinite[NP], n_mismatch[NP], n_differ[NP], n_included = 0;
 #pragma unroll
@@ -78,23 +58,13 @@ __global__ void __launch_bounds__(kCompareBlock) k_film_compare(const double* __
         bool included[4];
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
-            const uint64_t p = chunk * kFsChunk + j * 64u + lane, q = p < npix ? p : npix - 1;
+            const uint64_t p = chunk_element(chunk, j), q = p < npix ? p : npix - 1;
             included[j] = p < npix && (!mask || mask[q] > 0.f);
-            const double wa = a_weight[q], wb = b_weight[q];
+            float a[NP], b[NP];
+            fs_planes(a_value, a_light, a_weight[q], sl_a, q, C, stokes, s, kLum, flags, a);
+            fs_planes(b_value, b_light, b_weight[q], sl_b, q, C, stokes, s, kLum, flags, b);
 #pragma unroll
-            for (uint32_t c = 0; c < C; ++c) {
-                xa[c][j] = fs_develop(a_value, a_light, wa, sl_a, q, C, stokes, s, c);
-                xb[c][j] = fs_develop(b_value, b_light, wb, sl_b, q, C, stokes, s, c);
-            }
-            if constexpr (kLum) {
-                xa[C][j] = tm_luminance(xa[0][j], xa[1][j], xa[2][j]);
-                xb[C][j] = tm_luminance(xb[0][j], xb[1][j], xb[2][j]);
-            }
-#pragma unroll
-            for (uint32_t c = 0; c < NP; ++c) {
-                xa[c][j] = fc_element(xa[c][j], flags);
-                xb[c][j] = fc_element(xb[c][j], flags);
-            }
+            for (uint32_t c = 0; c < NP; ++c) xa[c][j] = a[c], xb[c][j] = b[c];
             n_included += included[j] ? 1u : 0u;
             if (diff && p < npix) {
 #pragma unroll
@@ -110,71 +80,51 @@ __global__ void __launch_bounds__(kCompareBlock) k_film_compare(const double* __
                 n_nonfinite[c] += r.nonfinite;
                 n_mismatch[c] += r.mismatch;
                 n_differ[c] += r.differ;
-                fc_best_take(best[c], r.abs_d, chunk * kFsChunk + j * 64u + lane);
+                fc_best_take(best[c], r.abs_d, chunk_element(chunk, j));
 #pragma unroll
                 for (uint32_t k = 0; k < kFcSums; ++k) t[k][j] = r.add[k];
             }
 #pragma unroll
             for (uint32_t k = 0; k < kFcSums; ++k) {
-                const double v = fc_wave_butterfly((t[k][0] + t[k][2]) + (t[k][1] + t[k][3]));
+                const double v = chunk_sum(t[k][0], t[k][1], t[k][2], t[k][3]);
                 if (lane == 0) sums[(c * kFcSums + k) * sums_stride + chunk] = v;
             }
         }
     }
     // every wavefront of the grid leaves its records, also one that met no chunk: the finish kernel reads them all
-    const unsigned long long n_all = fc_wave_sum_u64(n_included);
+    const unsigned long long n_all = wave_sum_u64(n_included);
 #pragma unroll
     for (uint32_t c = 0; c < NP; ++c) {
         const fc_best_t m = fc_wave_best(best[c]);
-        const unsigned long long nf = fc_wave_sum_u64(n_nonfinite[c]), mm = fc_wave_sum_u64(n_mismatch[c]), df = fc_wave_sum_u64(n_differ[c]);
+        const unsigned long long nf = wave_sum_u64(n_nonfinite[c]), mm = wave_sum_u64(n_mismatch[c]), df = wave_sum_u64(n_differ[c]);
         if (lane == 0) wrec[c * n_waves + wave] = fc_wave_rec_t{m.v, m.pixel, (uint32_t)n_all, (uint32_t)nf, (uint32_t)mm, (uint32_t)df};
     }
 }
 
 // ---- k_film_compare_finish: kFcSums + 1 blocks per plane ----------------------------------------------------------------------------------------
-// Block (c, k < kFcSums) reduces the n chunk sums of sum k of plane c by the same rule, level after level (a 1920 x 1088 film: 8160 -> 32 -> 1),
-// each level written behind the one it reads.  Block (c, kFcSums) merges the wavefronts' records of plane c: integer counts, and a maximum whose
-// order is total.  Every field of the record is written, so nobody has to clear it.
-__global__ void __launch_bounds__(kCompareBlock) k_film_compare_finish(film_compare_rec_t* __restrict__ rec, double* sums, uint64_t sums_stride, uint64_t n_chunks,
-                                                                       const fc_wave_rec_t* __restrict__ wrec, uint64_t n_waves) {
+// Block (c, k < kFcSums) reduces the chunk sums of sum k of plane c (film_reduce_levels).  Block (c, kFcSums) merges the wavefronts' records of
+// plane c: integer counts, and a maximum whose order is total.  Every field of the record is written, so nobody has to clear it.
+__global__ void __launch_bounds__(kFilmBlock) k_film_compare_finish(film_compare_rec_t* __restrict__ rec, double* sums, uint64_t sums_stride, uint64_t n_chunks,
+                                                                    const fc_wave_rec_t* __restrict__ wrec, uint64_t n_waves) {
     const uint32_t lane = threadIdx.x & 63u, c = blockIdx.x / (kFcSums + 1u), k = blockIdx.x % (kFcSums + 1u);
     if (k < kFcSums) {
-        double* in = sums + (c * kFcSums + k) * sums_stride;
-        uint64_t n = n_chunks;
-        while (n > 1) {
-            double* out = in + n;
-            const uint64_t m = fs_chunks(n);
-            for (uint64_t chunk = threadIdx.x >> 6; chunk < m; chunk += kCompareWaves) {
-                double d[4];
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    const uint64_t i = chunk * kFsChunk + j * 64u + lane;
-                    d[j] = i < n ? in[i] : 0.0;
-                }
-                const double t = fc_wave_butterfly((d[0] + d[2]) + (d[1] + d[3]));
-                if (lane == 0) out[chunk] = t;
-            }
-            __threadfence_block();
-            __syncthreads();
-            in = out;
-            n = m;
-        }
-        if (threadIdx.x == 0) rec[c].sum[k] = n ? in[0] : 0.0;
+        const double sum = film_reduce_levels(sums + (c * kFcSums + k) * sums_stride, n_chunks);
+        if (threadIdx.x == 0) rec[c].sum[k] = sum;
         return;
     }
-    __shared__ double s_best_v[kCompareWaves];
-    __shared__ unsigned long long s_best_pixel[kCompareWaves];
-    __shared__ unsigned long long s_count[kCompareWaves][4];
+    __shared__ double s_best_v[kFilmWaves];
+    __shared__ unsigned long long s_best_pixel[kFilmWaves];
+    __shared__ unsigned long long s_count[kFilmWaves][4];
     fc_best_t m;
     unsigned long long cnt[4] = {0ull, 0ull, 0ull, 0ull};
-    for (uint64_t w = threadIdx.x; w < n_waves; w += kCompareBlock) {
+    for (uint64_t w = threadIdx.x; w < n_waves; w += kFilmBlock) {
         const fc_wave_rec_t r = wrec[c * n_waves + w];
         fc_best_merge(m, r.max_abs, r.pixel);
         cnt[0] += r.n, cnt[1] += r.nonfinite, cnt[2] += r.mismatch, cnt[3] += r.differ;
     }
     m = fc_wave_best(m);
 #pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) cnt[i] = fc_wave_sum_u64(cnt[i]);
+    for (uint32_t i = 0; i < 4; ++i) cnt[i] = wave_sum_u64(cnt[i]);
     if (lane == 0) {
         s_best_v[threadIdx.x >> 6] = m.v;
         s_best_pixel[threadIdx.x >> 6] = m.pixel;
@@ -183,7 +133,7 @@ __global__ void __launch_bounds__(kCompareBlock) k_film_compare_finish(film_comp
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (uint32_t w = 1; w < kCompareWaves; ++w) {
+        for (uint32_t w = 1; w < kFilmWaves; ++w) {
             fc_best_merge(m, s_best_v[w], s_best_pixel[w]);
             for (uint32_t i = 0; i < 4; ++i) cnt[i] += s_count[w][i];
         }
@@ -194,15 +144,9 @@ __global__ void __launch_bounds__(kCompareBlock) k_film_compare_finish(film_comp
     }
 }
 
-// The grid follows the film: one wavefront per chunk while that is fewer than kCompareBlocksPerCU blocks per CU (a 37 x 23 film: one block, of which
-// one wavefront has a partial chunk; 1920 x 1088: 8160 chunks on 2040 blocks), then that many blocks whose wavefronts stride over the chunks, and
-// more again only where a wavefront would exceed kCompareMaxChunksPerWave.
-uint32_t film_compare_blocks(uint64_t npix, uint32_t n_cus) {
-    const uint64_t n_chunks = fs_chunks(npix), quads = (n_chunks + kCompareWaves - 1) / kCompareWaves;
-    const uint64_t need = (n_chunks + kCompareWaves * kCompareMaxChunksPerWave - 1) / (kCompareWaves * kCompareMaxChunksPerWave);
-    return (uint32_t)std::min<uint64_t>(quads, std::max<uint64_t>((uint64_t)std::max(1u, n_cus) * kCompareBlocksPerCU, need));
-}
-size_t film_compare_wave_bytes(uint64_t npix, uint32_t n_cus) { return (size_t)kFsMaxPlanes * film_compare_blocks(npix, n_cus) * kCompareWaves * sizeof(fc_wave_rec_t); }
+// kCompareBlocksPerCU blocks per CU at most (1920 x 1088: 8160 chunks on 2040 blocks, one per wavefront)
+static uint32_t film_compare_blocks(uint64_t npix, uint32_t n_cus) { return film_grid_blocks(npix, n_cus, kCompareBlocksPerCU); }
+size_t film_compare_wave_bytes(uint64_t npix, uint32_t n_cus) { return (size_t)kFsMaxPlanes * film_compare_blocks(npix, n_cus) * kFilmWaves * sizeof(fc_wave_rec_t); }
 
 int film_compare_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
                         const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, uint32_t s, uint32_t flags, double eps, const float* d_mask,
@@ -210,25 +154,19 @@ int film_compare_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, 
     const uint64_t npix = (uint64_t)sn.width * sn.height;
     if (npix == 0) return (int)hipErrorInvalidValue;
     const double sl_a = develop_scale(spe_a), sl_b = develop_scale(spe_b);
-    const bool lum = (flags & FC_LUMINANCE) != 0;
+    const bool lum = (flags & FS_LUMINANCE) != 0;
     const uint64_t n_chunks = fs_chunks(npix), stride = fs_scratch_len(npix);
     const uint32_t blocks = film_compare_blocks(npix, n_cus), stokes = film_stokes(sn);
-    const uint64_t n_waves = (uint64_t)blocks * kCompareWaves;
+    const uint64_t n_waves = (uint64_t)blocks * kFilmWaves;
     film_compare_rec_t* rec = static_cast<film_compare_rec_t*>(d_rec);
     fc_wave_rec_t* wrec = static_cast<fc_wave_rec_t*>(d_wave);
-    if (sn.channels == 1 && !lum)
-        hipLaunchKernelGGL((k_film_compare<1, false>), dim3(blocks), dim3(kCompareBlock), 0, stream, a_value, a_weight, a_light, sl_a, b_value, b_weight, b_light, sl_b, stokes, s,
-                           flags, eps, d_mask, npix, d_sums, stride, wrec, d_diff);
-    else if (sn.channels == 3 && !lum)
-        hipLaunchKernelGGL((k_film_compare<3, false>), dim3(blocks), dim3(kCompareBlock), 0, stream, a_value, a_weight, a_light, sl_a, b_value, b_weight, b_light, sl_b, stokes, s,
-                           flags, eps, d_mask, npix, d_sums, stride, wrec, d_diff);
-    else if (sn.channels == 3)
-        hipLaunchKernelGGL((k_film_compare<3, true>), dim3(blocks), dim3(kCompareBlock), 0, stream, a_value, a_weight, a_light, sl_a, b_value, b_weight, b_light, sl_b, stokes, s,
-                           flags, eps, d_mask, npix, d_sums, stride, wrec, d_diff);
-    else
+    if (!film_dispatch(sn.channels, lum, [&](auto c, auto l) {
+            hipLaunchKernelGGL((k_film_compare<decltype(c)::value, decltype(l)::value>), dim3(blocks), dim3(kFilmBlock), 0, stream, a_value, a_weight, a_light, sl_a, b_value,
+                               b_weight, b_light, sl_b, stokes, s, flags, eps, d_mask, npix, d_sums, stride, wrec, d_diff);
+        }))
         return (int)hipErrorInvalidValue;
     if (const hipError_t e = hipGetLastError()) return (int)e;
-    hipLaunchKernelGGL(k_film_compare_finish, dim3((sn.channels + (lum ? 1u : 0u)) * (kFcSums + 1u)), dim3(kCompareBlock), 0, stream, rec, d_sums, stride, n_chunks, wrec, n_waves);
+    hipLaunchKernelGGL(k_film_compare_finish, dim3((sn.channels + (lum ? 1u : 0u)) * (kFcSums + 1u)), dim3(kFilmBlock), 0, stream, rec, d_sums, stride, n_chunks, wrec, n_waves);
     return (int)hipGetLastError();
 }
 
@@ -237,34 +175,26 @@ int film_compare_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, 
 void film_compare_host(const sensor_t& sn, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
                        const double* b_weight, const double* b_light, uint64_t spe_b, uint32_t s, uint32_t flags, double eps, const float* mask, uint32_t n_threads,
                        void* out_rec, float* diff) {
-    const uint32_t C = sn.channels, stokes = film_stokes(sn), NP = C + ((flags & FC_LUMINANCE) ? 1u : 0u);
+    const uint32_t C = sn.channels, stokes = film_stokes(sn), NP = C + ((flags & FS_LUMINANCE) ? 1u : 0u);
     const uint64_t npix = (uint64_t)sn.width * sn.height, n_chunks = fs_chunks(npix), stride = fs_scratch_len(npix);
     const double sl_a = develop_scale(spe_a), sl_b = develop_scale(spe_b);
     film_compare_rec_t* rec = static_cast<film_compare_rec_t*>(out_rec);
     std::memset(rec, 0, NP * sizeof(film_compare_rec_t));
     std::vector<double> sums((size_t)NP * kFcSums * std::max<uint64_t>(stride, 1), 0.0);
     std::vector<fc_best_t> best(NP);
-    std::atomic<uint64_t> next_chunk{0};
     std::mutex merge;
-    auto work = [&]() {
+    on_threads(n_chunks, n_threads, [&](auto claim) {
         std::vector<film_compare_rec_t> my(NP, film_compare_rec_t{});
         std::vector<fc_best_t> my_best(NP);
         std::vector<double> a((size_t)kFsMaxPlanes * kFcSums * kFsChunk);
-        for (uint64_t chunk = next_chunk++; chunk < n_chunks; chunk = next_chunk++) {
+        for (uint64_t chunk = claim(); chunk < n_chunks; chunk = claim()) {
             for (uint32_t i = 0; i < kFsChunk; ++i) {
                 const uint64_t p = chunk * kFsChunk + i;
                 const bool included = p < npix && (!mask || mask[p] > 0.f);
                 float xa[kFsMaxPlanes] = {0.f, 0.f, 0.f, 0.f}, xb[kFsMaxPlanes] = {0.f, 0.f, 0.f, 0.f};
                 if (included) {
-                    for (uint32_t c = 0; c < C; ++c) {
-                        xa[c] = fs_develop(a_value, a_light, a_weight[p], sl_a, p, C, stokes, s, c);
-                        xb[c] = fs_develop(b_value, b_light, b_weight[p], sl_b, p, C, stokes, s, c);
-                    }
-                    if (NP > C) {
-                        xa[NP - 1] = tm_luminance(xa[0], xa[1], xa[2]);
-                        xb[NP - 1] = tm_luminance(xb[0], xb[1], xb[2]);
-                    }
-                    for (uint32_t c = 0; c < NP; ++c) xa[c] = fc_element(xa[c], flags), xb[c] = fc_element(xb[c], flags);
+                    fs_planes(a_value, a_light, a_weight[p], sl_a, p, C, stokes, s, NP > C, flags, xa);
+                    fs_planes(b_value, b_light, b_weight[p], sl_b, p, C, stokes, s, NP > C, flags, xb);
                 }
                 for (uint32_t c = 0; c < NP; ++c) {
                     const fc_pair_t r = fc_pair(xa[c], xb[c], included, eps);
@@ -285,31 +215,10 @@ void film_compare_host(const sensor_t& sn, const double* a_value, const double* 
             r.n += my[c].n, r.n_nonfinite += my[c].n_nonfinite, r.n_nonfinite_mismatch += my[c].n_nonfinite_mismatch, r.n_differ += my[c].n_differ;
             fc_best_merge(best[c], my_best[c].v, my_best[c].pixel);
         }
-    };
-    if (n_threads == 0) n_threads = std::max(1u, std::thread::hardware_concurrency());
-    n_threads = (uint32_t)std::min<uint64_t>(n_threads, std::max<uint64_t>(1, n_chunks));
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+    });
     // the levels above the chunks (k_film_compare_finish)
     for (uint32_t c = 0; c < NP; ++c) {
-        for (uint32_t k = 0; k < kFcSums; ++k) {
-            double* in = sums.data() + ((size_t)c * kFcSums + k) * stride;
-            uint64_t n = n_chunks;
-            while (n > 1) {
-                double* out = in + n;
-                const uint64_t m = fs_chunks(n);
-                for (uint64_t chunk = 0; chunk < m; ++chunk) {
-                    double lvl[kFsChunk];
-                    for (uint32_t i = 0; i < kFsChunk; ++i) lvl[i] = chunk * kFsChunk + i < n ? in[chunk * kFsChunk + i] : 0.0;
-                    out[chunk] = fs_chunk_sum(lvl);
-                }
-                in = out;
-                n = m;
-            }
-            rec[c].sum[k] = n ? in[0] : 0.0;
-        }
+        for (uint32_t k = 0; k < kFcSums; ++k) rec[c].sum[k] = fs_reduce_levels(sums.data() + ((size_t)c * kFcSums + k) * stride, n_chunks);
         rec[c].max_abs = best[c].v;
         rec[c].argmax = best[c].pixel;
     }

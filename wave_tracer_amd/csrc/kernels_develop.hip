@@ -4,13 +4,7 @@
 // operator, the mode and the colour table, appends an optional mask as alpha and writes f32 / 8-bit / 16-bit pixels — the developed values
 // never reach memory.  The arithmetic is wt/tonemap.h's, shared with the host twins at the end of the file.  Both kernels stream: every film
 // byte is read once, and the time is the memory system's.  No render kernel is compiled here.
-#include <algorithm>
-#include <atomic>
-#include <thread>
-#include <vector>
-
-#include "wtgpu_kernels.h"
-#include "wt/tonemap.h"
+#include "kernels_film.h"
 
 namespace wtk {
 
@@ -52,11 +46,8 @@ __global__ void __launch_bounds__(kDevelopBlock) k_develop_tonemap(const double*
     }
     const uint64_t p = blockIdx.x * (uint64_t)kDevelopBlock + threadIdx.x;
     if (p >= npix) return;
-    const double w = weight[p];
-    const uint64_t base = p * (C * stokes) + s;
     float v[C], rgb[3];
-#pragma unroll
-    for (uint32_t c = 0; c < C; ++c) v[c] = develop_plane(value[base + c * stokes], w, light[base + c * stokes], sl);
+    fs_planes(value, light, weight[p], sl, p, C, stokes, s, false, 0u, v);
     tm_pixel(t, v, C, rgb);
     if (!mask) {
         tm_store(out, p, format, 3, rgb, 0.f);
@@ -120,41 +111,27 @@ int develop_tonemap_launch(const sensor_t& sn, hipStream_t stream, const double*
     // against 0.100 - 0.108 ms on the room film (two runs) — no difference to be had, so the block does not spend a barrier and 3 KB of copies on
     // it.  To RGBA8 in normal mode the kernel takes 0.040 ms on the cornell film and 0.086 ms on the room film back to back, 0.042 and 0.28 - 0.30 ms
     // when the GPU has idled for 100 ms before the launch.
-    if (sn.channels == 1)
-        tonemap_launch_c<1>(stream, d_value, d_weight, d_light, sl, stokes, s, t, d_mask, format, lds, npix, d_out);
-    else if (sn.channels == 3)
-        tonemap_launch_c<3>(stream, d_value, d_weight, d_light, sl, stokes, s, t, d_mask, format, lds, npix, d_out);
-    else
+    if (!film_dispatch(sn.channels, false, [&](auto c, auto) {
+            tonemap_launch_c<decltype(c)::value>(stream, d_value, d_weight, d_light, sl, stokes, s, t, d_mask, format, lds, npix, d_out);
+        }))
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
-// ---- the host twins: the same wt/tonemap.h functions on host threads, one task per row (the pattern of sensor_mask_host) ---------------------
-template <class F>
-static void rows_on_threads(uint32_t H, uint32_t n_threads, F&& row) {
-    std::atomic<uint32_t> next_row{0};
-    auto work = [&]() {
-        for (uint32_t y = next_row++; y < H; y = next_row++) row(y);
-    };
-    if (n_threads == 0) n_threads = std::max(1u, std::thread::hardware_concurrency());
-    n_threads = std::min(n_threads, std::max(1u, H));
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-}
+// ---- the host twin: the same wt/tonemap.h functions on host threads, one task per row -------------------------------------------------------
 void develop_tonemap_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, const tonemap_args_t& t, uint32_t s,
                           const float* mask, uint32_t format, uint32_t n_threads, void* out) {
-    const uint32_t W = sn.width, C = sn.channels, stokes = film_stokes(sn);
+    const uint32_t W = sn.width, H = sn.height, C = sn.channels, stokes = film_stokes(sn);
     const double sl = develop_scale(spe);
-    rows_on_threads(sn.height, n_threads, [&](uint32_t y) {
-        for (uint32_t x = 0; x < W; ++x) {
-            const size_t p = (size_t)y * W + x, base = p * (C * stokes) + s;
-            float v[3] = {0.f, 0.f, 0.f}, rgb[3];
-            for (uint32_t c = 0; c < C; ++c) v[c] = develop_plane(value[base + c * stokes], weight[p], light[base + c * stokes], sl);
-            tm_pixel(t, v, C, rgb);
-            tm_store(out, p, format, mask ? 4u : 3u, rgb, mask ? mask[p] : 0.f);
-        }
+    on_threads(H, n_threads, [&](auto claim) {
+        for (uint64_t y = claim(); y < H; y = claim())
+            for (uint32_t x = 0; x < W; ++x) {
+                const size_t p = (size_t)y * W + x;
+                float v[3] = {0.f, 0.f, 0.f}, rgb[3];
+                fs_planes(value, light, weight[p], sl, p, C, stokes, s, false, 0u, v);
+                tm_pixel(t, v, C, rgb);
+                tm_store(out, p, format, mask ? 4u : 3u, rgb, mask ? mask[p] : 0.f);
+            }
     });
 }
 

@@ -4,12 +4,7 @@
 // (a miss counts as nothing).  The reference accumulates 1 / float(samples) per such sample in a float: the integer count is reproduced
 // here as that same sequential f32 sum (mask_value), so the device, the host threads and the reference agree bit for bit.
 // No render kernel is compiled here.
-#include <algorithm>
-#include <atomic>
-#include <thread>
-#include <vector>
-
-#include "wtgpu_kernels.h"
+#include "kernels_film.h"   // (on_threads)
 
 namespace wtk {
 
@@ -89,23 +84,16 @@ int sensor_mask_launch(const scene_t& sc, hipStream_t stream, const uint8_t* d_s
 // stack holds 64 entries like the device's (kLdsStack + kSpillStack): a full stack drops the same children on both.
 void sensor_mask_host(const scene_t& sc, const uint8_t* shape_matches, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out) {
     const uint32_t W = sc.sensor.width, H = sc.sensor.height;
-    std::atomic<uint32_t> next_row{0};
-    auto work = [&]() {
+    on_threads(H, n_threads, [&](auto claim) {
         stack_entry_t entries[kLdsStack + kSpillStack];
         const stack_ref_t stack = make_stack_ref(entries, 1, kLdsStack + kSpillStack, kLdsStack + kSpillStack, nullptr);
-        for (uint32_t y = next_row++; y < H; y = next_row++)
+        for (uint32_t y = (uint32_t)claim(); y < H; y = (uint32_t)claim())
             for (uint32_t x = 0; x < W; ++x) {
                 uint32_t n = 0;
                 for (uint32_t s = 0; s < samples; ++s) n += mask_sample_counts(sc, shape_matches, x, y, samples, s, seed, stack) ? 1u : 0u;
                 out[(size_t)y * W + x] = mask_value(n, samples);
             }
-    };
-    if (n_threads == 0) n_threads = std::max(1u, std::thread::hardware_concurrency());
-    n_threads = std::min(n_threads, std::max(1u, H));
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+    });
 }
 
 }   // namespace wtk

@@ -6,62 +6,40 @@
 // bin, the extrema and the sum are the same on both sides, bit for bit.  Measured on the MI355X (tools/bench_film_stats.py, docs/FEATURES.md): 0.39 ms
 // for the 418 MB of the polarimetric 1920 x 1088 film, 1.06 TB/s — a fifth of k_develop's rate on the same film: the per-element work, not the
 // memory system, sets the time.  No render kernel is compiled here.
-#include <algorithm>
-#include <atomic>
 #include <cstring>
 #include <mutex>
-#include <thread>
-#include <vector>
 
-#include "wtgpu_kernels.h"
-#include "wt/film_stats.h"
+#include "kernels_film.h"
 
 namespace wtk {
 
-constexpr int kStatsBlock = 256;                       // four wavefronts; a wavefront owns whole chunks of kFsChunk = 256 pixels
-constexpr uint32_t kStatsWaves = kStatsBlock / 64;
 // Two instantiations by LDS: 4 (cap + 1 + planes x cap) bytes with cap = 1024 (20 KB at four planes: several blocks per CU) or 4096 (80 KB of the
 // CU's 160: one block).  There is no overflow path: bins <= kFsMaxBins is checked before the launch.
 constexpr uint32_t kStatsSmallBins = 1024;
-static_assert(kFsChunk == 4 * 64, "a lane holds four elements of a chunk");
-// A block's u32 bins cannot overflow: a wavefront takes at most kStatsMaxChunksPerWave chunks (the grid grows with the film beyond that), so a
-// block counts at most 4 x 2^20 x 256 = 2^30 elements per plane.
-constexpr uint64_t kStatsMaxChunksPerWave = 1ull << 20;
+// A block's u32 bins cannot overflow: a wavefront takes at most kFilmMaxChunksPerWave chunks, so a block counts at most 4 x 2^20 x 256 = 2^30
+// elements per plane.
 constexpr uint32_t kStatsBlocksPerCU = 4;
 
-// the butterfly's distances 32 .. 1 inside a wavefront: lane i adds lane i + d; lane 0 ends with the sum of the 64
-WT_D double wave_butterfly(double t) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) t += __shfl_down(t, d, 64);
-    return t;
-}
-WT_D uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v = max(v, (uint32_t)__shfl_down((int)v, d, 64));
-    return v;
-}
-
 // ---- k_film_stats: f64 films [H][W][P], [H][W] -> records, histogram, chunk sums ----------------------------------------------------------
-// One lane per pixel, its C = 1 or 3 developed values of Stokes component s (and their luminance) in registers.  Wavefront g of the grid takes
-// chunks g, g + waves, ...; of chunk k lane l holds pixels 256 k + 64 j + l, j = 0 .. 3 (four loads of 64 consecutive pixels), so the
-// butterfly's distances 128 and 64 are the lane's own (d0 + d2) + (d1 + d3) and the rest are shuffles: no LDS, no barrier per chunk.
+// One lane per pixel, its C = 1 or 3 developed values of Stokes component s (and their luminance) in registers, in the chunk geometry of
+// kernels_film.h.  The loads are conditional: an excluded pixel's films are not read.
 // Bins: LDS atomics on the block's u32 histogram, flushed with 64-bit global atomics at the end (non-zero bins only).  The five classes
 // outside the bins and n are wavefront-uniform counts (ballots): zeros of an unlit background would otherwise all hit one LDS word.
 // Extrema: per lane as keys (fs_key) over all its chunks, one wavefront reduction and one global atomic each at the end.
 template <uint32_t C, bool kLum, uint32_t kBinCap>
-__global__ void __launch_bounds__(kStatsBlock) k_film_stats(const double* __restrict__ value, const double* __restrict__ weight, const double* __restrict__ light,
-                                                            double sl, uint32_t stokes, uint32_t s, uint32_t flags, const float* __restrict__ mask, uint64_t npix,
-                                                            const float* __restrict__ edges, uint32_t bins, film_stats_rec_t* __restrict__ rec,
-                                                            unsigned long long* __restrict__ hist, double* __restrict__ sums, uint64_t sums_stride) {
+__global__ void __launch_bounds__(kFilmBlock) k_film_stats(const double* __restrict__ value, const double* __restrict__ weight, const double* __restrict__ light,
+                                                           double sl, uint32_t stokes, uint32_t s, uint32_t flags, const float* __restrict__ mask, uint64_t npix,
+                                                           const float* __restrict__ edges, uint32_t bins, film_stats_rec_t* __restrict__ rec,
+                                                           unsigned long long* __restrict__ hist, double* __restrict__ sums, uint64_t sums_stride) {
     constexpr uint32_t NP = C + (kLum ? 1u : 0u);
     __shared__ float s_edge[kBinCap + 1];
     __shared__ uint32_t s_hist[NP * kBinCap];
-    for (uint32_t k = threadIdx.x; k <= bins; k += kStatsBlock) s_edge[k] = edges[k];
-    for (uint32_t k = threadIdx.x; k < NP * bins; k += kStatsBlock) s_hist[k] = 0u;
+    for (uint32_t k = threadIdx.x; k <= bins; k += kFilmBlock) s_edge[k] = edges[k];
+    for (uint32_t k = threadIdx.x; k < NP * bins; k += kFilmBlock) s_hist[k] = 0u;
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t n_chunks = fs_chunks(npix), n_waves = (uint64_t)gridDim.x * kStatsWaves;
+    const uint64_t n_chunks = fs_chunks(npix), n_waves = film_waves();
     uint32_t min_inv[NP], max_key[NP], minpos_inv[NP], count[NP][FS_BIN];   // count: the same in every lane
     uint32_t n_included = 0;
 #pragma unroll
@@ -70,23 +48,16 @@ __global__ void __launch_bounds__(kStatsBlock) k_film_stats(const double* __rest
 #pragma unroll
         for (uint32_t k = 0; k < FS_BIN; ++k) count[c][k] = 0u;
     }
-    for (uint64_t chunk = (uint64_t)blockIdx.x * kStatsWaves + (threadIdx.x >> 6); chunk < n_chunks; chunk += n_waves) {
+    for (uint64_t chunk = film_first_chunk(); chunk < n_chunks; chunk += n_waves) {
         double d[NP][4];
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
-            const uint64_t p = chunk * kFsChunk + j * 64u + lane;
+            const uint64_t p = chunk_element(chunk, j);
             const bool included = p < npix && (!mask || mask[p] > 0.f);
             float x[NP];
 #pragma unroll
             for (uint32_t c = 0; c < NP; ++c) x[c] = 0.f;
-            if (included) {
-                const double w = weight[p];
-#pragma unroll
-                for (uint32_t c = 0; c < C; ++c) x[c] = fs_develop(value, light, w, sl, p, C, stokes, s, c);
-                if constexpr (kLum) x[C] = tm_luminance(x[0], x[1], x[2]);
-#pragma unroll
-                for (uint32_t c = 0; c < NP; ++c) x[c] = fs_element(x[c], flags);
-            }
+            if (included) fs_planes(value, light, weight[p], sl, p, C, stokes, s, kLum, flags, x);
             n_included += (uint32_t)__popcll(__ballot(included));
 #pragma unroll
             for (uint32_t c = 0; c < NP; ++c) {
@@ -108,7 +79,7 @@ __global__ void __launch_bounds__(kStatsBlock) k_film_stats(const double* __rest
         }
 #pragma unroll
         for (uint32_t c = 0; c < NP; ++c) {
-            const double t = wave_butterfly((d[c][0] + d[c][2]) + (d[c][1] + d[c][3]));
+            const double t = chunk_sum(d[c][0], d[c][1], d[c][2], d[c][3]);
             if (lane == 0) sums[c * sums_stride + chunk] = t;
         }
     }
@@ -128,38 +99,18 @@ __global__ void __launch_bounds__(kStatsBlock) k_film_stats(const double* __rest
         }
     }
     __syncthreads();
-    for (uint32_t k = threadIdx.x; k < NP * bins; k += kStatsBlock)
+    for (uint32_t k = threadIdx.x; k < NP * bins; k += kFilmBlock)
         if (const uint32_t v = s_hist[k]) atomicAdd(&hist[k], (unsigned long long)v);
 }
 
 // ---- k_film_stats_finish: one block per plane ---------------------------------------------------------------------------------------------
-// Reduces the plane's n chunk sums by the same rule, level after level (a 1920 x 1088 film: 8160 -> 32 -> 1), each level written behind the
-// one it reads; then the sum goes into the record and the extrema's keys become floats (NaN where no element was met).
-__global__ void __launch_bounds__(kStatsBlock) k_film_stats_finish(film_stats_rec_t* __restrict__ rec, double* sums, uint64_t sums_stride, uint64_t n_chunks) {
-    const uint32_t lane = threadIdx.x & 63u;
-    double* in = sums + blockIdx.x * sums_stride;
-    uint64_t n = n_chunks;
-    while (n > 1) {
-        double* out = in + n;
-        const uint64_t m = fs_chunks(n);
-        for (uint64_t chunk = threadIdx.x >> 6; chunk < m; chunk += kStatsWaves) {
-            double d[4];
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                const uint64_t i = chunk * kFsChunk + j * 64u + lane;
-                d[j] = i < n ? in[i] : 0.0;
-            }
-            const double t = wave_butterfly((d[0] + d[2]) + (d[1] + d[3]));
-            if (lane == 0) out[chunk] = t;
-        }
-        __threadfence_block();
-        __syncthreads();
-        in = out;
-        n = m;
-    }
+// Reduces the plane's chunk sums (film_reduce_levels); then the sum goes into the record and the extrema's keys become floats (NaN where no
+// element was met).
+__global__ void __launch_bounds__(kFilmBlock) k_film_stats_finish(film_stats_rec_t* __restrict__ rec, double* sums, uint64_t sums_stride, uint64_t n_chunks) {
+    const double sum = film_reduce_levels(sums + blockIdx.x * sums_stride, n_chunks);
     if (threadIdx.x == 0) {
         film_stats_rec_t& r = rec[blockIdx.x];
-        r.sum = n ? in[0] : 0.0;
+        r.sum = sum;
         r.min_inv = __float_as_uint(fs_unkey(r.min_inv ? ~r.min_inv : 0u));
         r.max_key = __float_as_uint(fs_unkey(r.max_key));
         r.minpos_inv = __float_as_uint(fs_unkey(r.minpos_inv ? ~r.minpos_inv : 0u));
@@ -171,10 +122,10 @@ static void film_stats_launch_c(hipStream_t stream, uint32_t blocks, const doubl
                                 const float* mask, uint64_t npix, const float* edges, uint32_t bins, film_stats_rec_t* rec, unsigned long long* hist, double* sums,
                                 uint64_t stride) {
     if (bins <= kStatsSmallBins)
-        hipLaunchKernelGGL((k_film_stats<C, kLum, kStatsSmallBins>), dim3(blocks), dim3(kStatsBlock), 0, stream, v, w, l, sl, stokes, s, flags, mask, npix, edges, bins, rec,
+        hipLaunchKernelGGL((k_film_stats<C, kLum, kStatsSmallBins>), dim3(blocks), dim3(kFilmBlock), 0, stream, v, w, l, sl, stokes, s, flags, mask, npix, edges, bins, rec,
                            hist, sums, stride);
     else
-        hipLaunchKernelGGL((k_film_stats<C, kLum, kFsMaxBins>), dim3(blocks), dim3(kStatsBlock), 0, stream, v, w, l, sl, stokes, s, flags, mask, npix, edges, bins, rec, hist,
+        hipLaunchKernelGGL((k_film_stats<C, kLum, kFsMaxBins>), dim3(blocks), dim3(kFilmBlock), 0, stream, v, w, l, sl, stokes, s, flags, mask, npix, edges, bins, rec, hist,
                            sums, stride);
 }
 int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe, uint32_t s,
@@ -183,23 +134,18 @@ int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, co
     if (npix == 0 || bins > kFsMaxBins) return (int)hipErrorInvalidValue;
     const double sl = develop_scale(spe);
     const bool lum = (flags & FS_LUMINANCE) != 0;
-    const uint64_t n_chunks = fs_chunks(npix), stride = fs_scratch_len(npix), quads = (n_chunks + kStatsWaves - 1) / kStatsWaves;
-    // The grid follows the film: one wavefront per chunk while that is fewer than kStatsBlocksPerCU blocks per CU (a 37 x 23 film: one block), then
-    // that many blocks whose wavefronts stride over the chunks (1920 x 1088: 8160 chunks on 1024 blocks, two per wavefront) — each block flushes its
-    // histogram once, so more blocks mean more global atomics — and more again only where a wavefront would exceed kStatsMaxChunksPerWave.
-    const uint64_t need = (n_chunks + kStatsWaves * kStatsMaxChunksPerWave - 1) / (kStatsWaves * kStatsMaxChunksPerWave);
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(quads, std::max<uint64_t>((uint64_t)std::max(1u, n_cus) * kStatsBlocksPerCU, need));
+    const uint64_t n_chunks = fs_chunks(npix), stride = fs_scratch_len(npix);
+    // kStatsBlocksPerCU blocks per CU at most (1920 x 1088: 8160 chunks on 1024 blocks, two per wavefront): each block flushes its histogram once,
+    // so more blocks mean more global atomics.
+    const uint32_t blocks = film_grid_blocks(npix, n_cus, kStatsBlocksPerCU);
     film_stats_rec_t* rec = static_cast<film_stats_rec_t*>(d_rec);
-    if (sn.channels == 1 && !lum)
-        film_stats_launch_c<1, false>(stream, blocks, d_value, d_weight, d_light, sl, film_stokes(sn), s, flags, d_mask, npix, d_edges, bins, rec, d_hist, d_sums, stride);
-    else if (sn.channels == 3 && !lum)
-        film_stats_launch_c<3, false>(stream, blocks, d_value, d_weight, d_light, sl, film_stokes(sn), s, flags, d_mask, npix, d_edges, bins, rec, d_hist, d_sums, stride);
-    else if (sn.channels == 3)
-        film_stats_launch_c<3, true>(stream, blocks, d_value, d_weight, d_light, sl, film_stokes(sn), s, flags, d_mask, npix, d_edges, bins, rec, d_hist, d_sums, stride);
-    else
+    if (!film_dispatch(sn.channels, lum, [&](auto c, auto l) {
+            film_stats_launch_c<decltype(c)::value, decltype(l)::value>(stream, blocks, d_value, d_weight, d_light, sl, film_stokes(sn), s, flags, d_mask, npix, d_edges, bins,
+                                                                        rec, d_hist, d_sums, stride);
+        }))
         return (int)hipErrorInvalidValue;
     if (const hipError_t e = hipGetLastError()) return (int)e;
-    hipLaunchKernelGGL(k_film_stats_finish, dim3(sn.channels + (lum ? 1u : 0u)), dim3(kStatsBlock), 0, stream, rec, d_sums, stride, n_chunks);
+    hipLaunchKernelGGL(k_film_stats_finish, dim3(sn.channels + (lum ? 1u : 0u)), dim3(kFilmBlock), 0, stream, rec, d_sums, stride, n_chunks);
     return (int)hipGetLastError();
 }
 
@@ -214,22 +160,17 @@ void film_stats_host(const sensor_t& sn, const double* value, const double* weig
     std::memset(rec, 0, NP * sizeof(film_stats_rec_t));
     if (out_hist) std::memset(out_hist, 0, (size_t)NP * bins * sizeof(unsigned long long));
     std::vector<double> sums((size_t)NP * std::max<uint64_t>(stride, 1), 0.0);
-    std::atomic<uint64_t> next_chunk{0};
     std::mutex merge;
-    auto work = [&]() {
+    on_threads(n_chunks, n_threads, [&](auto claim) {
         std::vector<film_stats_rec_t> my(NP, film_stats_rec_t{});
         std::vector<unsigned long long> my_hist((size_t)NP * bins, 0ull);
         double a[kFsMaxPlanes][kFsChunk];
-        for (uint64_t chunk = next_chunk++; chunk < n_chunks; chunk = next_chunk++) {
+        for (uint64_t chunk = claim(); chunk < n_chunks; chunk = claim()) {
             for (uint32_t i = 0; i < kFsChunk; ++i) {
                 const uint64_t p = chunk * kFsChunk + i;
                 const bool included = p < npix && (!mask || mask[p] > 0.f);
                 float x[kFsMaxPlanes] = {0.f, 0.f, 0.f, 0.f};
-                if (included) {
-                    for (uint32_t c = 0; c < C; ++c) x[c] = fs_develop(value, light, weight[p], sl, p, C, stokes, s, c);
-                    if (NP > C) x[NP - 1] = tm_luminance(x[0], x[1], x[2]);
-                    for (uint32_t c = 0; c < NP; ++c) x[c] = fs_element(x[c], flags);
-                }
+                if (included) fs_planes(value, light, weight[p], sl, p, C, stokes, s, NP > C, flags, x);
                 for (uint32_t c = 0; c < NP; ++c) {
                     a[c][i] = fs_addend(x[c], included);
                     if (!included) continue;
@@ -257,30 +198,11 @@ void film_stats_host(const sensor_t& sn, const double* value, const double* weig
         }
         if (out_hist)
             for (size_t k = 0; k < my_hist.size(); ++k) out_hist[k] += my_hist[k];
-    };
-    if (n_threads == 0) n_threads = std::max(1u, std::thread::hardware_concurrency());
-    n_threads = (uint32_t)std::min<uint64_t>(n_threads, std::max<uint64_t>(1, n_chunks));
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < n_threads; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+    });
     // the levels above the chunks, and the keys (k_film_stats_finish)
     for (uint32_t c = 0; c < NP; ++c) {
-        double* in = sums.data() + c * stride;
-        uint64_t n = n_chunks;
-        while (n > 1) {
-            double* out = in + n;
-            const uint64_t m = fs_chunks(n);
-            for (uint64_t chunk = 0; chunk < m; ++chunk) {
-                double a[kFsChunk];
-                for (uint32_t i = 0; i < kFsChunk; ++i) a[i] = chunk * kFsChunk + i < n ? in[chunk * kFsChunk + i] : 0.0;
-                out[chunk] = fs_chunk_sum(a);
-            }
-            in = out;
-            n = m;
-        }
         film_stats_rec_t& r = rec[c];
-        r.sum = n ? in[0] : 0.0;
+        r.sum = fs_reduce_levels(sums.data() + c * stride, n_chunks);
         const float mn = fs_unkey(r.min_inv ? ~r.min_inv : 0u), mx = fs_unkey(r.max_key), mp = fs_unkey(r.minpos_inv ? ~r.minpos_inv : 0u);
         std::memcpy(&r.min_inv, &mn, 4);
         std::memcpy(&r.max_key, &mx, 4);

@@ -1,9 +1,9 @@
 // wave_tracer_amd — comparison of two films (difference statistics, noise estimate): the arithmetic the device kernels (kernels_compare.hip) and
 // their host twin share.
 //
-// Planes.  As in wt/film_stats.h: plane c is the developed value of film plane  c * stokes + stokes_component;  FC_LUMINANCE (3-channel films)
-// adds tm_luminance of the three developed values (taken before FC_ABS), so there are at most kFsMaxPlanes = 4; FC_ABS takes fabsf of both
-// values.  An included pixel gives per plane the pair  xa = develop_plane(A.., spe_a),  xb = develop_plane(B.., spe_b): the f32 wtgpu_develop writes.
+// Planes.  wt/film_stats.h's (fs_planes, with its flags): plane c is the developed value of film plane  c * stokes + stokes_component;  FS_LUMINANCE
+// (3-channel films) adds tm_luminance of the three developed values (taken before FS_ABS), so there are at most kFsMaxPlanes = 4; FS_ABS takes fabsf
+// of both values.  An included pixel gives per plane the pair  xa = develop_plane(A.., spe_a),  xb = develop_plane(B.., spe_b): the f32 wtgpu_develop writes.
 // Membership.  A pixel is included iff no mask is given or mask[pixel] > 0 (a NaN mask value excludes).
 // Classes.  A member pair is exactly one of
 //   non-finite  either value is NaN or infinite: counted in n_nonfinite, and in n_nonfinite_mismatch unless both are NaN or xa == xb (equal
@@ -24,7 +24,6 @@
 
 namespace wt {
 
-enum film_compare_flag_e : uint32_t { FC_ABS = 1u, FC_LUMINANCE = 2u };
 enum film_compare_sum_e : uint32_t { FC_SUM_ABS = 0, FC_SUM_SQ = 1, FC_SUM_A_SQ = 2, FC_SUM_B_SQ = 3, FC_SUM_REL = 4, kFcSums = 5 };
 constexpr unsigned long long kFcNoPixel = ~0ull;   // argmax where nothing differs
 
@@ -78,7 +77,6 @@ WT_HD void fc_best_merge(fc_best_t& m, double v, unsigned long long pixel) {   /
 }
 WT_HD void fc_best_take(fc_best_t& m, double abs_d, unsigned long long pixel) { fc_best_merge(m, abs_d, abs_d > 0.0 ? pixel : kFcNoPixel); }
 
-WT_HD float fc_element(float x, uint32_t flags) { return (flags & FC_ABS) ? fabsf(x) : x; }
 // an element of the difference plane
 WT_HD float fc_diff(float xa, float xb, bool included) {
     const float d = xa - xb;

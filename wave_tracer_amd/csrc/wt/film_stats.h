@@ -1,4 +1,6 @@
 // wave_tracer_amd — film statistics (range, histogram, sum): the arithmetic the device kernels (kernels_stats.hip) and their host twin share.
+// What a pixel's planes are (fs_planes), the flags and the summation order are also the film comparison's (wt/film_compare.h) and, for the
+// developed values, the tonemapper's (kernels_develop.hip).
 //
 // Element value.  x = develop_plane(...) of wt/tonemap.h, the f32 wtgpu_develop writes, of plane  channel * stokes + stokes_component;  with
 // FS_LUMINANCE a 3-channel film has a fourth plane, tm_luminance of the three developed values (taken before FS_ABS).  FS_ABS: fabsf(x), for the
@@ -72,16 +74,19 @@ WT_HD uint32_t fs_classify(float x, const float* edge, uint32_t bins, uint32_t& 
     return FS_BIN;
 }
 
-// the developed value of output plane c (< channels) of a pixel, and the element it stands for
-WT_HD float fs_develop(const double* value, const double* light, double w, double sl, uint64_t pixel, uint32_t channels, uint32_t stokes, uint32_t s, uint32_t c) {
-    const uint64_t i = pixel * (channels * stokes) + c * stokes + s;
-    return develop_plane(value[i], w, light[i], sl);
+// A pixel's planes: the developed values of planes  c * stokes + s  of its `channels` channels, behind them — with `luminance`, 3-channel films
+// only — the luminance of the three, taken before FS_ABS; then FS_ABS of all.  x: channels + luminance floats.
+WT_HD void fs_planes(const double* value, const double* light, double w, double sl, uint64_t pixel, uint32_t channels, uint32_t stokes, uint32_t s, bool luminance,
+                     uint32_t flags, float* x) {
+    const uint64_t base = pixel * (channels * stokes) + s;
+    for (uint32_t c = 0; c < channels; ++c) x[c] = develop_plane(value[base + c * stokes], w, light[base + c * stokes], sl);
+    if (luminance) x[channels] = tm_luminance(x[0], x[1], x[2]);
+    for (uint32_t c = 0; c < channels + (luminance ? 1u : 0u); ++c) x[c] = (flags & FS_ABS) ? fabsf(x[c]) : x[c];
 }
-WT_HD float fs_element(float x, uint32_t flags) { return (flags & FS_ABS) ? fabsf(x) : x; }
 // what an element adds to its plane's sum
 WT_HD double fs_addend(float x, bool included) { return included && x == x ? (double)x : 0.0; }
 
-// The butterfly over one chunk (host form; the device holds four elements per lane and pairs them the same way: kernels_stats.hip).
+// The butterfly over one chunk (host form; the device holds four elements per lane and pairs them the same way: kernels_film.h).
 inline double fs_chunk_sum(double a[kFsChunk]) {
     for (uint32_t d = kFsChunk / 2; d; d >>= 1)
         for (uint32_t i = 0; i < d; ++i) a[i] += a[i + d];
@@ -96,6 +101,24 @@ WT_HD uint64_t fs_scratch_len(uint64_t n_elements) {   // doubles of scratch one
         if (n <= 1) return total;
         n = fs_chunks(n);
     }
+}
+// The levels above the chunks (host form; kernels_film.h has the device's): `sums` holds a plane's n_chunks chunk sums and, behind them, room for
+// every further level (fs_scratch_len).  Each level is written behind the one it reads; returns the one number left, +0.0 where there is no chunk.
+inline double fs_reduce_levels(double* sums, uint64_t n_chunks) {
+    double* in = sums;
+    uint64_t n = n_chunks;
+    while (n > 1) {
+        double* out = in + n;
+        const uint64_t m = fs_chunks(n);
+        for (uint64_t chunk = 0; chunk < m; ++chunk) {
+            double a[kFsChunk];
+            for (uint32_t i = 0; i < kFsChunk; ++i) a[i] = chunk * kFsChunk + i < n ? in[chunk * kFsChunk + i] : 0.0;
+            out[chunk] = fs_chunk_sum(a);
+        }
+        in = out;
+        n = m;
+    }
+    return n ? in[0] : 0.0;
 }
 
 }   // namespace wt

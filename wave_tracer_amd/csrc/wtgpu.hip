@@ -83,10 +83,9 @@ struct batch_launcher_t {
         return i;
     }
     explicit batch_launcher_t(wtgpu_scene* s_) : s(s_), K(s_->knobs) {
-        int n_cu = 256;   // persistent grids: enough blocks to fill the 256 CUs; wavefronts pull work until the queue is empty
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device);
-        grid_round = (uint32_t)n_cu * K.round_blocks_per_cu;
-        grid_heavy = (uint32_t)n_cu * K.heavy_waves_per_cu;
+        // persistent grids: enough blocks to fill the 256 CUs; wavefronts pull work until the queue is empty
+        grid_round = s->n_cus * K.round_blocks_per_cu;
+        grid_heavy = s->n_cus * K.heavy_waves_per_cu;
         path_mode = s->host.opts.integrator != INTEGRATOR_BDPT;
         hp_on = K.host_prof != 0;
         trace_on = K.trace_launch != 0;

@@ -6,7 +6,8 @@
 //   wtgpu_knobs.hip      the environment knobs: one table, read_knobs (wtgpu_knobs.h; plain C++)
 //   wtgpu_trace_ab.hip   WTGPU_TRACE_AB replay harness, the alternative forms of the per-lane traversal
 //   wtgpu_counters.hip   wtgpu_get_counters and its profile printers, reset
-//   wtgpu_queries.hip    ray / cone / region queries, sensor masks, the test probes, develop and tonemap, film statistics, film comparison
+//   wtgpu_queries.hip    ray / cone / region queries, sensor masks, the test probes
+//   wtgpu_film.hip       what reads films: develop and tonemap, film statistics, film comparison
 //   wtgpu_control.hip    cancel / pause / resume / capture / progressive render; the RCCL film reduction
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,12 +57,22 @@ struct chunk_rec_t {
     bool busy = false;
 };
 
+// What a film feature (wtgpu_film.hip) keeps with the scene from its first call on: its results on the device (the statistics: records, histogram
+// and edge table; the comparison: records, then the wavefronts' records), their head pinned on the host, and the chunk sums of every level of the
+// fixed summation order (wt/film_stats.h: fs_scratch_len).
+struct film_scratch_t {
+    unsigned char* d_block = nullptr;
+    unsigned char* h_block = nullptr;
+    double* d_sums = nullptr;
+};
+
 struct wtgpu_scene {
     std::unique_ptr<wth::scene_builder_t> builder;   // owns the host arrays (named scenes)
     scene_t host{};                                  // host-pointer scene
     scene_t dev{};                                   // device-pointer scene
     std::vector<void*> dev_allocs;
     int device = -1;
+    uint32_t n_cus = 0;   // compute units of the device, read at upload: what the persistent grids and the film kernels' grids are sized by
     bool uploaded = false;
     std::vector<device_state_t> slices;              // per-batch path state, one slice per internal stream
     std::vector<const path_state_t*> d_path_slices;  // ... and its plt_path part (device copies)
@@ -107,15 +118,7 @@ struct wtgpu_scene {
     float* d_tm_table = nullptr;         // wtgpu_tonemap_device: the colour table of the last call (kMaxTonemapTable entries), staged the same way
     float* h_tm_table = nullptr;
     hipEvent_t ev_tm = nullptr;
-    unsigned char* d_fs = nullptr;       // wtgpu_film_stats_device, allocated at its first call: records + histogram + edge table on the device,
-    unsigned char* h_fs = nullptr;       // the same block pinned on the host,
-    double* d_fs_sums = nullptr;         // the chunk sums of every level of the fixed summation order (wt/film_stats.h: fs_scratch_len)
-    uint32_t fs_cus = 0;                 // compute units of the device: the grid's upper end
-    unsigned char* d_fc = nullptr;       // wtgpu_film_compare_device, allocated at its first call: the records on the device,
-    unsigned char* h_fc = nullptr;       // the same block pinned on the host,
-    double* d_fc_sums = nullptr;         // the chunk sums of every level, five sums per plane (wt/film_compare.h),
-    unsigned char* d_fc_wave = nullptr;  // the wavefronts' records (kernels_compare.hip: film_compare_wave_bytes)
-    uint32_t fc_cus = 0;
+    film_scratch_t fs, fc;               // wtgpu_film_stats_device, wtgpu_film_compare_device
     // WTGPU_TRACE_AB (diagnostic, tests/test_gpu_traversal.py): accumulated over the replayed rounds — milliseconds of k_trace_refill / k_trace_sm on the
     // same queue, words of their outputs that differ (traversal records + triangle lists + heavy-queue checksums), walks replayed
     double ab_ms[2] = {0, 0};
@@ -171,6 +174,7 @@ struct scene_extents_t {
 // ---- what one unit needs of another
 scene_extents_t scene_extents(const scene_t& sc);
 void release_device(wtgpu_scene* s);   // wtgpu_upload.hip
+void film_scratch_free(film_scratch_t& f);   // wtgpu_film.hip
 int drain_all(wtgpu_scene* s);         // wtgpu.hip: finishes the pending batches, waits for every batch in flight
 // wtgpu_trace_ab.hip
 void launch_trace_alt(const wtgpu_scene* s, const launch_args_t& a, hipStream_t st_, int in, int first, uint32_t round, uint32_t g0);

@@ -10,6 +10,7 @@
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
 //   kernels_compare.hip k_film_compare / k_film_compare_finish: difference statistics of two films (not part of a render)
+//   kernels_film.h      what the last three share on the device and in their host twins: chunk geometry, level reduction, grid, dispatch, host threads
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -435,7 +436,7 @@ int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, co
 void film_stats_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, uint32_t s, uint32_t flags, const float* mask,
                      const float* edges, uint32_t bins, uint32_t n_threads, void* out_rec, unsigned long long* out_hist);
 // kernels_compare.hip: comparison of two films (wtgpu_film_compare_device / wtgpu_film_compare_host; wt/film_compare.h).  Two sets of films as wtgpu_render fills
-// them (the same pointers twice are fine); s: the Stokes component; flags: FC_ABS | FC_LUMINANCE; eps: finite, > 0.  d_rec: film_compare_rec_t per plane;
+// them (the same pointers twice are fine); s: the Stokes component; flags: FS_ABS | FS_LUMINANCE; eps: finite, > 0.  d_rec: film_compare_rec_t per plane;
 // d_sums: kFsMaxPlanes x kFcSums x fs_scratch_len(pixels) doubles; d_wave: film_compare_wave_bytes(pixels, n_cus) bytes — none of them has to be
 // cleared; d_diff: null or [height][width][planes] f32.  Two kernels on `stream`; the launch returns a hipError_t.
 size_t film_compare_wave_bytes(uint64_t npix, uint32_t n_cus);

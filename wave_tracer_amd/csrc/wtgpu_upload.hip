@@ -248,6 +248,9 @@ static uint64_t size_batches(const wtgpu_scene* s, uint64_t max_batch, uint32_t&
 
 static int upload_impl(wtgpu_scene* s, uint64_t max_batch) {
     read_knobs(s->knobs);
+    int n_cu = 256;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device);
+    s->n_cus = (uint32_t)std::max(1, n_cu);
     int rc;
     if ((rc = upload_scene_arrays(s)) != WTGPU_OK) return rc;
     uint32_t n_slices = 0;
@@ -315,15 +318,8 @@ void release_device(wtgpu_scene* s) {
     s->h_tm_table = nullptr;
     if (s->ev_tm) (void)hipEventDestroy(s->ev_tm);
     s->ev_tm = nullptr;
-    s->d_fs = nullptr;           // (freed with dev_allocs)
-    s->d_fs_sums = nullptr;
-    if (s->h_fs) (void)hipHostFree(s->h_fs);
-    s->h_fs = nullptr;
-    s->d_fc = nullptr;           // (freed with dev_allocs)
-    s->d_fc_sums = nullptr;
-    s->d_fc_wave = nullptr;
-    if (s->h_fc) (void)hipHostFree(s->h_fc);
-    s->h_fc = nullptr;
+    film_scratch_free(s->fs);
+    film_scratch_free(s->fc);
     s->uploaded = false;
 }
 
