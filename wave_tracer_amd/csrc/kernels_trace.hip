@@ -713,39 +713,42 @@ __global__ void __launch_bounds__(kBlock, WTGPU_LB_TRACE) k_tr_tail(launch_args_
 }
 
 // Heavy traversals: one wavefront (64-thread block) per walk, persistent blocks pulling from the heavy queue.
-__global__ void __launch_bounds__(64, WTGPU_LB_HEAVY) k_trace_heavy(launch_args_t a) {
-    __shared__ coop_shared_t sh;
+// What a wavefront keeps across coop_traverse is the same in all 64 lanes — the walk's envelope, the resume state, the counters: it is read through
+// uniform() (wt/coop.h) into scalar registers.  PROF: the phase clocks of WTGPU_PROFILE=2 (k_trace_heavy_prof); the default kernel carries none.
+template <bool PROF>
+WT_D void trace_heavy_body(const launch_args_t& a, coop_shared_t& sh) {
     coop_set_dropped_counter(sh, a.st.counters + kDroppedSlot);
     uint32_t* ctl = a.st.ctl;
     const uint32_t n = ctl[CTL_HEAVY_COUNT];
     const uint32_t* hq = a.st.heavy_queue;
     uint32_t* head = ctl + CTL_HEAVY_HEAD;
-    bdpt_counters_t ctr;
-    memset(&ctr, 0, sizeof(ctr));
-    const size_t W2 = 2 * (size_t)a.st.cap;
+    // the counters this kernel touches (bdpt_counters_t), summed wave-uniformly: one copy per wavefront, flushed by lane 0
+    unsigned long long n_segments = 0, n_ray_queries = 0, n_cone_queries = 0, n_overflow = 0;
     const bool rt = a.sc.sensor.ray_trace_only || a.sc.opts.force_ray_tracing;
     for (;;) {
         const uint32_t item = wave_grab_item(head);
         if (item >= n) break;
-        const uint32_t w = hq[item];
+        const uint32_t w = uniform(hq[item]);
         const walk_trace_in_t wk = walk_load_trace_in(a.st.walks, a.st.walk_words, w);   // uniform address: broadcast
         const uint_list_t tris{a.st.tris + (size_t)w * kTriListWords, 1u, (a.collect_list & 1u) ? kMaxConeTris : 0u};   // see k_trace
-        const cone_t env = walk_trace_envelope(a.sc, wk);
+        const cone_t env = uniform(walk_trace_envelope(a.sc, wk));
         unsigned long long prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const long long tt0 = a.profile == 2 ? clock64() : 0;
-        const float dist0 = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(dist)]);
-        const uint32_t seg0 = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(ntris)];
-        const uint32_t nray0 = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(n_ray_queries)], ncone0 = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(n_cone_queries)];
+        const long long tt0 = PROF ? clock64() : 0;
+        const uint32_t* tv = a.st.trav + (size_t)w * kTravWords;
+        const float dist0 = uniform(__uint_as_float(tv[WT_TRAV_WORD(dist)]));
+        const uint32_t seg0 = uniform(tv[WT_TRAV_WORD(ntris)]);
+        const uint32_t nray0 = uniform(tv[WT_TRAV_WORD(n_ray_queries)]), ncone0 = uniform(tv[WT_TRAV_WORD(n_cone_queries)]);
         ray_hit_t axis;   // the closest hit of the beam axis, found by k_trace (traverse_axis, wt/bvh.h)
-        axis.tuid = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(tuid)];
-        axis.bx = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(bx)]);
-        axis.by = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(by)]);
-        axis.dist = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(pdist)]);
-        axis.front_face = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(front_face)];
-        const uint32_t short0 = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(overflow)];
-        const trav_result_t tr2 = coop_traverse(a.sc, env, wavenum_to_wavelen_m(wk.k), WT_INF, rt, sh, tris, a.profile == 2 ? prof : nullptr, true, seg0, dist0, nray0, ncone0,
-                                                &axis, !(a.collect_list & 1u) || (a.collect_list & 2u), a.heavy_probe != 0, a.heavy_cache ? short0 : kInvalid, a.heavy_cache ? wk.prev_offset_tuid : kInvalid, a.heavy_cache != 0);
-        if (a.profile == 2 && threadIdx.x == 0) {
+        axis.tuid = uniform(tv[WT_TRAV_WORD(tuid)]);
+        axis.bx = uniform(__uint_as_float(tv[WT_TRAV_WORD(bx)]));
+        axis.by = uniform(__uint_as_float(tv[WT_TRAV_WORD(by)]));
+        axis.dist = uniform(__uint_as_float(tv[WT_TRAV_WORD(pdist)]));
+        axis.front_face = uniform(tv[WT_TRAV_WORD(front_face)]);
+        const uint32_t short0 = uniform(tv[WT_TRAV_WORD(overflow)]);
+        const uint32_t origin0 = uniform(wk.prev_offset_tuid);
+        const trav_result_t tr2 = coop_traverse(a.sc, env, uniform(wavenum_to_wavelen_m(wk.k)), WT_INF, rt, sh, tris, PROF ? prof : nullptr, true, seg0, dist0, nray0, ncone0,
+                                                &axis, !(a.collect_list & 1u) || (a.collect_list & 2u), a.heavy_probe != 0, a.heavy_cache ? short0 : kInvalid, a.heavy_cache ? origin0 : kInvalid, a.heavy_cache != 0);
+        if (PROF && threadIdx.x == 0) {
             prof[3] = (unsigned long long)(clock64() - tt0);
             for (int q = 0; q < 4; ++q) atomicAdd(a.st.counters + kNumCounters + q, prof[q]);
             atomicAdd(a.st.counters + kNumCounters + 5, prof[5]);
@@ -754,15 +757,27 @@ __global__ void __launch_bounds__(64, WTGPU_LB_HEAVY) k_trace_heavy(launch_args_
             for (int q = 8; q < 12; ++q) atomicAdd(a.st.counters + kNumCounters + q, prof[q]);   // (WTGPU_COOP_PROF: batch counts)
             atomicAdd(a.st.counters + kNumCounters + 4, 1ull);
         }
-        if (threadIdx.x == 0) {
-            soa_store(a.st.trav, kTravWords, w, tr2);
-            ctr.segments += 1;
-            ctr.ray_queries += tr2.n_ray_queries;
-            ctr.cone_queries += tr2.n_cone_queries;
-            if (a.collect_list & 1u) ctr.cone_tri_overflow += tr2.overflow;
-        }
+        n_segments += 1;
+        n_ray_queries += tr2.n_ray_queries;
+        n_cone_queries += tr2.n_cone_queries;
+        if (a.collect_list & 1u) n_overflow += tr2.overflow;
+        if (threadIdx.x == 0) soa_store(a.st.trav, kTravWords, w, tr2);
     }
-    if (a.count_stats) flush_counters(a.st.counters, ctr);
+    if (a.count_stats && threadIdx.x == 0) {
+        unsigned long long* g = a.st.counters;
+        if (n_segments) atomicAdd(g + offsetof(bdpt_counters_t, segments) / 8, n_segments);
+        if (n_ray_queries) atomicAdd(g + offsetof(bdpt_counters_t, ray_queries) / 8, n_ray_queries);
+        if (n_cone_queries) atomicAdd(g + offsetof(bdpt_counters_t, cone_queries) / 8, n_cone_queries);
+        if (n_overflow) atomicAdd(g + offsetof(bdpt_counters_t, cone_tri_overflow) / 8, n_overflow);
+    }
+}
+__global__ void __launch_bounds__(64, WTGPU_LB_HEAVY) k_trace_heavy(launch_args_t a) {
+    __shared__ coop_shared_t sh;
+    trace_heavy_body<false>(a, sh);
+}
+__global__ void __launch_bounds__(64, 2) k_trace_heavy_prof(launch_args_t a) {   // WTGPU_PROFILE=2
+    __shared__ coop_shared_t sh;
+    trace_heavy_body<true>(a, sh);
 }
 
 // ---- PMC calibration: a streaming copy with the access width of the SoA state (one dword per lane, fully coalesced) and a known
@@ -840,9 +855,9 @@ __global__ void __launch_bounds__(64) k_query_regions(scene_t sc, const float* c
     if (i >= n) return;
     const float* c = cones + 10 * (size_t)i;
     const vec3 d = normalize(vec3{c[3], c[4], c[5]});
-    const cone_t env = make_cone(vec3{c[0], c[1], c[2]}, d, build_orthogonal_frame(d).t, c[6], c[8], c[7]);
+    const cone_t env = uniform(make_cone(vec3{c[0], c[1], c[2]}, d, build_orthogonal_frame(d).t, c[6], c[8], c[7]));   // one cone per wavefront: scalar registers (wt/coop.h)
     const uint_list_t none{nullptr, 1u, 0u};
-    const trav_result_t tr = coop_traverse(sc, env, c[9], WT_INF, false, sh, none, nullptr, false, 0, 0.f, 0, 0, nullptr, true);
+    const trav_result_t tr = coop_traverse(sc, env, uniform(c[9]), WT_INF, false, sh, none, nullptr, false, 0, 0.f, 0, 0, nullptr, true);
     uint32_t prim = kInvalid;
     gather_out_t ge{0.0, 0u, 0u, 0u}, gf{0.0, 0u, 0u, 0u};
     if (tr.ballistic) {

@@ -86,6 +86,38 @@ WT_D float wave_min(float v) {
     for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
     return v;
 }
+// A value that is the same in every lane of the wavefront — the result of a load from a wave-uniform address, of a shuffle from one lane, of a
+// wave reduction, or of arithmetic on such values — moved to a scalar register (the first lane's copy: bit-identical by definition).  The
+// compiler cannot prove these uniform and would keep 64 copies of each in a vector register; the wave-per-query kernels hold ~100 such values
+// across their loops.  Call it in wave-uniform control flow only (every lane active, every lane holding the same value).
+WT_D int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
+WT_D uint32_t uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+WT_D bool uniform(bool x) { return __builtin_amdgcn_readfirstlane((int)x) != 0; }
+WT_D float uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+WT_D vec3 uniform(vec3 v) { return vec3{uniform(v.x), uniform(v.y), uniform(v.z)}; }
+WT_D range_t uniform(const range_t& r) { return range_t{uniform(r.min), uniform(r.max)}; }
+WT_D cone_t uniform(const cone_t& c) {
+    cone_t u;
+    u.o = uniform(c.o);
+    u.d = uniform(c.d);
+    u.x = uniform(c.x);
+    u.x0 = uniform(c.x0);
+    u.tan_alpha = uniform(c.tan_alpha);
+    u.e = uniform(c.e);
+    u.one_over_e = uniform(c.one_over_e);
+    u.z_apex = uniform(c.z_apex);
+    return u;
+}
+
+// The three vertices of a triangle, without its normal: 36 of the record's 48 bytes (two 16-byte loads and one word) for the tests that use no more.
+WT_D void coop_tri_vertices(const scene_t& sc, uint32_t tuid, vec3& a, vec3& b, vec3& c) {
+    const float4* q = reinterpret_cast<const float4*>(sc.tri_geo + tuid);
+    const float4 q0 = q[0], q1 = q[1];
+    const float q2 = reinterpret_cast<const float*>(q)[8];
+    a = vec3{q0.x, q0.y, q0.z};
+    b = vec3{q0.w, q1.x, q1.y};
+    c = vec3{q1.z, q1.w, q2};
+}
 
 // cone x AABB of child i (bvh8w.cpp:187-230); returns hit + tmin
 WT_D bool cone_child_test(const bvh8_node_t& n, int i, vec3 ro, vec3 rd, vec3 rinvd, bool sx, bool sy, bool sz, float ta, float ix,
@@ -127,8 +159,12 @@ WT_D bool cone_child_test(const bvh8_node_t& n, int i, vec3 ro, vec3 rd, vec3 ri
 //     search slab shrinks after every batch with hits exactly like intersection_record_work_t::search_range;
 //     any_hit = true : the any-hit probe (bvh_cone_any_hit): returns at the first batch with a hit.
 template <bool any_hit>
-WT_D bool coop_cone_query(const scene_t& sc, const cone_t& cone, const range_t& searchrange, float z_scale, coop_shared_t& sh,
-                                       const uint_list_t& tris, cone_hit_t& rec, unsigned long long* prof = nullptr, float min_progress = -WT_INF) {
+WT_D bool coop_cone_query(const scene_t& sc, const cone_t& cone_, const range_t& searchrange_, float z_scale, coop_shared_t& sh,
+                                       const uint_list_t& tris, cone_hit_t& rec, unsigned long long* prof = nullptr, float min_progress_ = -WT_INF) {
+    // the query's arguments are the same in all lanes: kept in scalar registers (uniform(), above), like everything derived from them below
+    const cone_t cone = uniform(cone_);
+    const range_t searchrange = uniform(searchrange_);
+    const float min_progress = uniform(min_progress_);
     const int lane = threadIdx.x & 63;
     const int grp = lane >> 3, sub = lane & 7;
     rec.dist = WT_INF;
@@ -140,10 +176,10 @@ WT_D bool coop_cone_query(const scene_t& sc, const cone_t& cone, const range_t& 
     rec.short_tuid = kInvalid;
     if (sc.n_nodes == 0) return false;
     const vec3 ro = cone.o, rd = cone.d;
-    const vec3 rinvd{1.f / rd.x, 1.f / rd.y, 1.f / rd.z};
+    const vec3 rinvd = uniform(vec3{1.f / rd.x, 1.f / rd.y, 1.f / rd.z});
     const bool sx = __builtin_signbit(rinvd.x), sy = __builtin_signbit(rinvd.y), sz = __builtin_signbit(rinvd.z);
     const float ta = cone.tan_alpha, ix = cone.x0;
-    range_t range = any_hit ? searchrange : cone_search_range(cone, searchrange, rec.dist, z_scale);
+    range_t range = any_hit ? searchrange : uniform(cone_search_range(cone, searchrange, rec.dist, z_scale));
     float slab_max = range.max;   // far end of the current interaction slab (list membership); range.max may be pruned below it
     int s = 1;
     uint32_t leaf_total = 0, nsurv = 0;
@@ -196,23 +232,23 @@ WT_D bool coop_cone_query(const scene_t& sc, const cone_t& cone, const range_t& 
             const unsigned long long mask = __ballot(hit);
             if (!mask) continue;
             if (any_hit) {
-                rec.short_tuid = (uint32_t)__shfl((int)t2, __ffsll((long long)mask) - 1, 64);
+                rec.short_tuid = uniform((uint32_t)__shfl((int)t2, __ffsll((long long)mask) - 1, 64));
                 any = true;
                 break;
             }
-            const float dm = wave_min(d);
+            const float dm = uniform(wave_min(d));
             if (dm < rec.dist) {
                 const unsigned long long m2 = __ballot(hit && d == dm);
                 const int src = __ffsll((long long)m2) - 1;
-                rec.front_face = (uint32_t)__shfl((int)ff, src, 64);
+                rec.front_face = uniform((uint32_t)__shfl((int)ff, src, 64));
                 rec.dist = dm;
                 if (rec.dist - searchrange.min < min_progress) {   // decided: too near to be accepted (see bvh_traverse_cone)
-                    rec.short_tuid = (uint32_t)__shfl((int)t2, src, 64);
+                    rec.short_tuid = uniform((uint32_t)__shfl((int)t2, src, 64));
                     rec.too_short = 1;
                     any = true;
                     break;
                 }
-                range = cone_search_range(cone, searchrange, rec.dist, z_scale);
+                range = uniform(cone_search_range(cone, searchrange, rec.dist, z_scale));
                 slab_max = range.max;
                 compact(slab_max);   // the slab shrank: listed triangles beyond it leave (and make room)
             }
@@ -227,7 +263,7 @@ WT_D bool coop_cone_query(const scene_t& sc, const cone_t& cone, const range_t& 
             const uint32_t newn = total < tris.cap ? total : tris.cap;
             rec.overflow += total - newn;
             rec.ntris = newn;
-            if (rec.overflow > 0) range.max = fminf_(range.max, rec.dist);   // bounded-list regime (traversal pruning only), see bvh.h
+            if (rec.overflow > 0) range.max = uniform(fminf_(range.max, rec.dist));   // bounded-list regime (traversal pruning only), see bvh.h
         }
         nsurv = 0;
         __syncthreads();
@@ -308,8 +344,8 @@ WT_D bool coop_cone_query(const scene_t& sc, const cone_t& cone, const range_t& 
             while (m) {
                 const int src = __ffsll((long long)m) - 1;
                 m &= m - 1;
-                uint32_t c = (uint32_t)__shfl((int)cnt, src, 64);
-                const uint32_t t = (uint32_t)__shfl((int)t0, src, 64);
+                uint32_t c = uniform((uint32_t)__shfl((int)cnt, src, 64));
+                const uint32_t t = uniform((uint32_t)__shfl((int)t0, src, 64));
                 if (c > kCoopLeafTris) c = kCoopLeafTris;   // cannot happen with this builder (leaves hold <= MAX_LEAF triangles)
                 for (uint32_t q = (uint32_t)lane; q < c; q += 64u) sh.tri_buf[leaf_total + q] = t + q;
                 leaf_total += c;
@@ -374,8 +410,9 @@ WT_D bool coop_cone_query(const scene_t& sc, const cone_t& cone, const range_t& 
             uint32_t tuid = 0;
             if (k < leaf_total) {
                 tuid = sh.tri_buf[k];
-                const tri_geo_t tri = sc.tri_geo[tuid];
-                pass = cone_tri_maybe(cone, tri.a, tri.b, tri.c, range);
+                vec3 va, vb, vc;
+                coop_tri_vertices(sc, tuid, va, vb, vc);
+                pass = cone_tri_maybe(cone, va, vb, vc, range);
             }
             const unsigned long long pm = __ballot(pass);
             if (pm) {
@@ -706,7 +743,9 @@ WT_D void coop_split(const scene_t& sc, const cone_t& tcone, const range_t& slab
 // 8 stack entries x 8 children per step, buffered leaves tested 64 triangles per step.  A serial per-lane traversal is a
 // chain of ~30 dependent loads (~1 us each at this occupancy); this one is ~10 steps.  Equal-distance ties (a ray through
 // a shared edge) are resolved towards the lowest buffered triangle instead of the first visited one.
-WT_D bool coop_ray_query(const scene_t& sc, vec3 ro, vec3 rd, const range_t& range, coop_shared_t& sh, ray_hit_t& rec) {
+WT_D bool coop_ray_query(const scene_t& sc, vec3 ro_, vec3 rd_, const range_t& range_, coop_shared_t& sh, ray_hit_t& rec) {
+    const vec3 ro = uniform(ro_), rd = uniform(rd_);   // wave-uniform arguments and state in scalar registers, see uniform()
+    const range_t range = uniform(range_);
     const int lane = threadIdx.x & 63;
     const int grp = lane >> 3, sub = lane & 7;
     rec.dist = WT_INF;
@@ -714,7 +753,7 @@ WT_D bool coop_ray_query(const scene_t& sc, vec3 ro, vec3 rd, const range_t& ran
     rec.bx = rec.by = 0.f;
     rec.front_face = 0;
     if (sc.n_nodes == 0) return false;
-    const vec3 rinvd{1.f / rd.x, 1.f / rd.y, 1.f / rd.z};
+    const vec3 rinvd = uniform(vec3{1.f / rd.x, 1.f / rd.y, 1.f / rd.z});
     const bool sx = __builtin_signbit(rinvd.x), sy = __builtin_signbit(rinvd.y), sz = __builtin_signbit(rinvd.z);
     int s = 1;
     uint32_t leaf_total = 0;
@@ -785,8 +824,8 @@ WT_D bool coop_ray_query(const scene_t& sc, vec3 ro, vec3 rd, const range_t& ran
             while (m) {
                 const int src = __ffsll((long long)m) - 1;
                 m &= m - 1;
-                uint32_t c = (uint32_t)__shfl((int)cnt, src, 64);
-                const uint32_t t = (uint32_t)__shfl((int)t0, src, 64);
+                uint32_t c = uniform((uint32_t)__shfl((int)cnt, src, 64));
+                const uint32_t t = uniform((uint32_t)__shfl((int)t0, src, 64));
                 if (c > kCoopLeafTris) c = kCoopLeafTris;   // cannot happen with this builder (leaves hold <= MAX_LEAF triangles)
                 for (uint32_t q = (uint32_t)lane; q < c; q += 64u) sh.tri_buf[leaf_total + q] = t + q;
                 leaf_total += c;
@@ -815,14 +854,14 @@ WT_D bool coop_ray_query(const scene_t& sc, vec3 ro, vec3 rd, const range_t& ran
             }
             const unsigned long long mask = __ballot(hit);
             if (mask) {
-                const float dm = wave_min(d);
+                const float dm = uniform(wave_min(d));
                 const unsigned long long m2 = __ballot(hit && d == dm);
                 const int src = __ffsll((long long)m2) - 1;
                 rec.dist = dm;
-                rec.tuid = (uint32_t)__shfl((int)tuid, src, 64);
-                rec.bx = __shfl(ht.bx, src, 64);
-                rec.by = __shfl(ht.by, src, 64);
-                rec.front_face = (uint32_t)__shfl((int)ff, src, 64);
+                rec.tuid = uniform((uint32_t)__shfl((int)tuid, src, 64));
+                rec.bx = uniform(__shfl(ht.bx, src, 64));
+                rec.by = uniform(__shfl(ht.by, src, 64));
+                rec.front_face = uniform((uint32_t)__shfl((int)ff, src, 64));
             }
         }
         leaf_total = 0;
@@ -840,11 +879,16 @@ WT_D bool coop_ray_query(const scene_t& sc, vec3 ro, vec3 rd, const range_t& ran
 // axis (`axis`, from the per-lane kernel's hand-over; computed here when nullptr) stands in for the per-segment ray queries, bounds
 // the cone queries and names the triangle under the axis of an overflowed region.  resume: continue with the cone query of segment
 // seg0 at distance dist0 (everything before is settled).
-WT_D trav_result_t coop_traverse(const scene_t& sc, const cone_t& envelope, float lambda_m, float distance, bool force_ray_tracing,
+WT_D trav_result_t coop_traverse(const scene_t& sc, const cone_t& envelope_, float lambda_m_, float distance_, bool force_ray_tracing,
                                               coop_shared_t& sh, const uint_list_t& tris, unsigned long long* prof = nullptr, bool resume = false,
-                                              uint32_t seg0 = 0, float dist0 = 0.f, uint32_t nray0 = 0, uint32_t ncone0 = 0, const ray_hit_t* axis = nullptr,
-                                              bool primary_always = false, bool probe_resumed = true, uint32_t short_tuid = kInvalid,
-                                              uint32_t origin_tuid = kInvalid, bool use_cache = true) {
+                                              uint32_t seg0_ = 0, float dist0 = 0.f, uint32_t nray0 = 0, uint32_t ncone0 = 0, const ray_hit_t* axis = nullptr,
+                                              bool primary_always = false, bool probe_resumed = true, uint32_t short_tuid_ = kInvalid,
+                                              uint32_t origin_tuid_ = kInvalid, bool use_cache = true) {
+    // One walk per wavefront: the envelope, the policy's state and the record are the same in all lanes and live in scalar registers (uniform()).
+    const cone_t envelope = uniform(envelope_);
+    const float lambda_m = uniform(lambda_m_), distance = uniform(distance_);
+    const uint32_t seg0 = uniform(seg0_), origin_tuid = uniform(origin_tuid_);
+    uint32_t short_tuid = uniform(short_tuid_);
 #ifdef WTGPU_COOP_PROF
 #define WT_COOP_PROF(i, t0_)
 #else
@@ -864,13 +908,17 @@ WT_D trav_result_t coop_traverse(const scene_t& sc, const cone_t& envelope, floa
     r.pdist = 0.f;
     r.ntris = 0;
     r.overflow = 0;
-    r.n_ray_queries = resume ? nray0 : 0u;
-    r.n_cone_queries = resume ? ncone0 : 0u;
+    r.n_ray_queries = resume ? uniform(nray0) : 0u;
+    r.n_cone_queries = resume ? uniform(ncone0) : 0u;
     const vec3 ro = envelope.o, rd = envelope.d;
     ray_hit_t ah;
     bool axis_hit;
     if (axis) {
-        ah = *axis;
+        ah.dist = uniform(axis->dist);
+        ah.tuid = uniform(axis->tuid);
+        ah.bx = uniform(axis->bx);
+        ah.by = uniform(axis->by);
+        ah.front_face = uniform(axis->front_face);
         axis_hit = ah.tuid != kInvalid;
     } else {
         r.n_ray_queries++;
@@ -891,18 +939,18 @@ WT_D trav_result_t coop_traverse(const scene_t& sc, const cone_t& envelope, floa
         if (axis_hit) ballistic_hit();
         return r;
     }
-    float dist = resume ? dist0 : 0.f;
+    float dist = resume ? uniform(dist0) : 0.f;
     for (uint32_t seg = resume ? seg0 : 0u;; ++seg) {
-        const float ballistic_dist = max_ballistic_distance(lambda_m, seg, 0.f);
+        const float ballistic_dist = uniform(max_ballistic_distance(lambda_m, seg, 0.f));
         if (!(resume && seg == seg0)) {   // (that segment is settled already; `dist` is past it)
             if (axis_hit && ah.dist <= fminf_(distance, dist + ballistic_dist * kBallisticScale)) {
                 ballistic_hit();
                 return r;
             }
-            dist += ballistic_dist;
+            dist = uniform(dist + ballistic_dist);
             if (ballistic_dist == WT_INF || dist >= distance) return r;
         }
-        const float min_df_prog = cone_axes(envelope, dist).x / 2.f;
+        const float min_df_prog = uniform(cone_axes(envelope, dist).x / 2.f);
         cone_hit_t ch;
         r.n_cone_queries++;
         // A thin-slab any-hit probe first: for wide beams it is far cheaper than letting the full (near-first, 8-wide) query find
@@ -912,7 +960,7 @@ WT_D trav_result_t coop_traverse(const scene_t& sc, const cone_t& envelope, floa
         // meeting a too-near hit, so the full query, which also stops at the first too-near hit, rarely finds one)
         // ... and before the probe the two remembered triangles (see wt::traverse_axis): the one that satisfied the previous probe — or made
         // the per-lane attempt before the hand-over too short — and the one the beam started from.  Same test, same slab as the probe's.
-        const range_t thin{dist, fminf_(distance, dist + min_df_prog)};
+        const range_t thin{dist, uniform(fminf_(distance, dist + min_df_prog))};
         bool near_hit = false;
         for (int c = 0; c < 2 && !near_hit; ++c) {
             const uint32_t cand = c == 0 ? short_tuid : origin_tuid;
@@ -929,7 +977,7 @@ WT_D trav_result_t coop_traverse(const scene_t& sc, const cone_t& envelope, floa
         WT_COOP_PROF(1, tp0)
         if (near_hit) continue;   // too short (see bvh_cone_any_hit)
         const long long tc0 = prof ? clock64() : 0;
-        const float cone_max = axis_hit ? fminf_(distance, cone_axis_bound(envelope, ah.dist)) : distance;
+        const float cone_max = axis_hit ? uniform(fminf_(distance, cone_axis_bound(envelope, ah.dist))) : distance;
         coop_cone(sc, envelope, range_t{dist, cone_max}, kMajorAxisToZScale, sh, tris, ch, prof, min_df_prog);
         WT_COOP_PROF(2, tc0)
         if (ch.too_short) {   // (boundary case of the probe's inclusive slab)

@@ -161,7 +161,12 @@ struct batch_launcher_t {
                     HP_LAUNCH(k_trace_refill, dim3(g0), dim3(kBlock), 0, st_, a, in, first, round);
             }
             rec(r, st_);
-            if (sf <= 1 && dbg_stage >= 3 + 3 * (int)round) HP_LAUNCH(k_trace_heavy, dim3(gh), dim3(64), 0, st_, a);
+            if (sf <= 1 && dbg_stage >= 3 + 3 * (int)round) {
+                if (a.profile == 2)
+                    HP_LAUNCH(k_trace_heavy_prof, dim3(gh), dim3(64), 0, st_, a);
+                else
+                    HP_LAUNCH(k_trace_heavy, dim3(gh), dim3(64), 0, st_, a);
+            }
             rec(r, st_);
             if (path_mode) {
                 if (round > 0) HP_LAUNCH(k_path_fsd, dim3(gh), dim3(64), 0, st_, a, ps, round);

@@ -41,7 +41,7 @@ namespace wtk {
 #define WTGPU_LB_TRACE 3
 #endif
 #ifndef WTGPU_LB_HEAVY
-#define WTGPU_LB_HEAVY 2   // 215 VGPRs, no spills, no scratch frame: as fast as 3 waves with 93 spilled registers, 27 GB per pass less HBM traffic
+#define WTGPU_LB_HEAVY 3   // 142 VGPRs, no spills, no scratch frame, with the wave-uniform state in scalar registers (wt/coop.h: uniform(); before: 236 VGPRs => 2)
 #endif
 #ifndef WTGPU_LB_INTERACT
 #define WTGPU_LB_INTERACT 3   // (round 6, with the bicubic texture path in the kernel: 4 / 3 / 2 waves per SIMD -> 29.1-29.3 / 29.9-30.2 / 30.2 Msamples/s; until round 5: 4)
@@ -368,6 +368,7 @@ __global__ void k_tr_cone(launch_args_t a, uint32_t it);
 __global__ void k_tr_policy(launch_args_t a, uint32_t it);
 __global__ void k_tr_tail(launch_args_t a, uint32_t it);
 __global__ void k_trace_heavy(launch_args_t a);
+__global__ void k_trace_heavy_prof(launch_args_t a);   // the same with the phase clocks of WTGPU_PROFILE=2
 __global__ void k_interact(launch_args_t a, int in, int first_round);
 __global__ void k_classify(launch_args_t a, int in, int first_round);
 __global__ void k_interact_diffuse(launch_args_t a, int in);
