@@ -112,6 +112,19 @@ CAPTURE_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_void_p)
 _lib = None
 
 
+def connect_class_order():
+    """Test hook (wtgpu_test_hooks.h): the length-class keys (tk * key_dim + sk) in the order k_connect_class takes the classes, as the host computes
+    it, and key_dim."""
+    import numpy as np
+    lib = load_library()
+    lib.wtgpu_test_connect_class_order.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    n, dim = C.c_uint32(0), C.c_uint32(0)
+    _check(lib.wtgpu_test_connect_class_order(None, 0, C.byref(n), C.byref(dim)))
+    keys = np.zeros(n.value, np.uint32)
+    _check(lib.wtgpu_test_connect_class_order(keys.ctypes.data, keys.size, C.byref(n), C.byref(dim)))
+    return keys, int(dim.value)
+
+
 def load_library():
     """Loads libwtgpu.so; raises loudly if the HIP extension has not been built (there is no fallback)."""
     global _lib
@@ -765,6 +778,19 @@ class Scene:
         out = (C.c_uint64 * n)()
         _check(load_library().wtgpu_test_profile_counters(self._h, out, n))
         return [int(v) for v in out]
+
+    def connect_class_items(self, slice=0, max_items=1 << 22):
+        """Test hook (wtgpu_test_hooks.h): what the last batch connected by k_connect_class on state slice `slice` left behind — (start of every
+        class in the flattened item space, samples per class, key per class), all in the device's class order, and the samples in that order."""
+        import numpy as np
+        lib = load_library()
+        lib.wtgpu_test_connect_class_items.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        n_keys = connect_class_order()[0].size
+        table = np.zeros(3 * n_keys + 1, np.uint32)
+        items = np.zeros(max_items, np.uint32)
+        n = C.c_uint32(0)
+        _check(lib.wtgpu_test_connect_class_items(self._h, slice, table.ctypes.data, items.ctypes.data, items.size, C.byref(n)))
+        return table[:n_keys + 1].copy(), table[n_keys + 1:2 * n_keys + 1].copy(), table[2 * n_keys + 1:].copy(), items[:n.value].copy()
 
     def counters(self):
         c = Counters()

@@ -1,18 +1,30 @@
-// wave_tracer_amd — subpath connections of plt_bdpt: strategy buckets, connections + MIS, film splat (see wtgpu_kernels.h for the list of kernel translation units).
+// wave_tracer_amd — subpath connections of plt_bdpt: class / strategy buckets, connections + MIS, film splat (see wtgpu_kernels.h for the list of kernel translation units).
 #include "wtgpu_kernels.h"
 
 namespace wtk {
 
-// ---- connections: strategy-major -------------------------------------------------------------------------------------
-// plt_bdpt.cpp:105-146 loops over all (s,t) pairs of a sample.  One thread per sample would leave a wavefront executing the
-// UNION of its 64 samples' pairs (~80 iterations with ~10 lanes' worth of work: subpath lengths are geometric).  Instead:
-//   k_connect_enum  : every sample appends its index to one bucket per valid (s,t) pair (block-aggregated: LDS counts, one global
+// ---- connections ------------------------------------------------------------------------------------------------------------------
+// plt_bdpt.cpp:105-146 loops over all (s,t) pairs of a sample.  One thread per sample, samples taken as they come, would leave a wavefront
+// executing the UNION of its 64 samples' pairs (~80 iterations with ~10 lanes' worth of work: subpath lengths are geometric).  What a wavefront
+// needs is 64 lanes that run the same (s,t) in every iteration.  Two forms give it that (WTGPU_CONNECT_CLASS):
+// class-major (k_connect_class, 1) — two samples whose subpaths have the same lengths (nT, nS) have the same valid strategies (strategy_valid
+// reads nothing else), so the work item is a SAMPLE and the buckets are the length classes:
+//   k_connect_enum  : every sample appends its index ONCE, to the bucket (min(nT, K), min(nS, K)) (block-aggregated: LDS counts, one global
 //                     atomic per bucket and block),
-//   k_connect_scan  : prefix sum over the 19x19 bucket sizes,
-//   k_connect_strat : persistent; 64 consecutive items of the flattened bucket space = 64 samples with the SAME (s,t): uniform
-//                     control flow, coalesced vertex loads; the t>1 fluxes are summed per sample (f64 atomics), t<=1 strategies
-//                     splat into the light image directly,
+//   k_connect_scan  : prefix sum over the 19x19 bucket sizes in the order of descending nT x nS (class_key_rank), every class padded to whole
+//                     wavefronts,
+//   k_connect_class : persistent; a wavefront grabs 64 items of the flattened space = 64 samples of ONE class and runs the class's strategies
+//                     in a row, t outer, s inner: the class, the loop counters and the validity test are wave-uniform; context, vertex stores
+//                     and pool are set up once per sample; all of a sample's vertices are fetched by one wavefront within one item, vertex
+//                     t-1 by consecutive iterations; the t>1 fluxes are summed in the lane (f64, fixed order) and written once; t<=1
+//                     strategies splat into the light image directly.  k_connect_class_open: the classes of the last row / column,
 //   k_connect_splat : one film splat per sample with the summed flux (film.hpp:214-342).
+// strategy-major (k_connect_strat, 0; the A/B reference, and what the staged form below enumerates) — the work item is one strategy of a sample:
+//   k_connect_enum  : every sample appends its index to one bucket per valid (s,t) pair,
+//   k_connect_scan  : prefix sum over the bucket sizes,
+//   k_connect_strat : persistent; 64 consecutive items of the flattened bucket space = 64 samples with the SAME (s,t); the t>1 fluxes are
+//                     summed per sample with f64 atomics.  A sample's ~3.5 vertices are fetched again by each of its ~10 strategies, each in
+//                     another wavefront at another time.
 WT_D bool strategy_valid(const integrator_opts_t& o, int s, int t, int nS, int nT) {
     const int depth = t + s - 2;
     if (t > nT || s > nS) return false;
@@ -41,21 +53,36 @@ WT_D int wave_max_i(int v) {
 // Block-aggregated bucket append: 1024 samples per block count their valid (s,t) pairs per bucket in LDS, reserve one range per
 // bucket with ONE global atomic each, and fill it.  (Wave-aggregated global atomics on the ~30 hot bucket counters serialised in
 // L2: PMC SQ_WAIT_ANY 99 % of this kernel's wave cycles, 9.5 ms per pass.)
-__global__ void __launch_bounds__(kEnumBlock) k_connect_enum(launch_args_t a) {
+__global__ void __launch_bounds__(kEnumBlock) k_connect_enum(launch_args_t a, uint32_t by_class) {
     __shared__ uint32_t s_cnt[kNumKeys], s_base[kNumKeys];
     const uint32_t i = blockIdx.x * kEnumBlock + threadIdx.x;
-    const size_t W2 = 2 * (size_t)a.st.cap;
     for (uint32_t k = threadIdx.x; k < kNumKeys; k += kEnumBlock) s_cnt[k] = 0;
     int nT = -1, nS = -1;
     if (i < a.nb) {
         nT = (int)a.st.walks[(size_t)(i) * a.st.walk_words + WT_WALK_NVERTS_WORD];
         nS = (int)a.st.walks[(size_t)(a.st.cap + i) * a.st.walk_words + WT_WALK_NVERTS_WORD];
+        if (!by_class) {   // (k_connect_class writes every sample's sum)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) a.st.lacc[(size_t)c * a.st.cap + i] = 0.0;
+            for (int c = 0; c < 4; ++c) a.st.lacc[(size_t)c * a.st.cap + i] = 0.0;
+        }
     }
     __syncthreads();
     const int K = (int)kKeyDim - 1;
     const int kT = nT < K ? nT : K, kS = nS < K ? nS : K;
+    if (by_class) {
+        // the sample's length class; EVERY sample of the batch is appended (one without a valid strategy runs none and gets its zero sum)
+        const uint32_t key = (uint32_t)max(kT, 0) * kKeyDim + (uint32_t)max(kS, 0);
+        if (i < a.nb) atomicAdd(&s_cnt[key], 1u);
+        __syncthreads();
+        for (uint32_t k = threadIdx.x; k < kNumKeys; k += kEnumBlock) {
+            const uint32_t c = s_cnt[k];
+            s_base[k] = c ? atomicAdd(a.st.strat_count + k, c) : 0u;
+            s_cnt[k] = 0;
+        }
+        __syncthreads();
+        if (i < a.nb) a.st.strat_items[(size_t)key * a.st.cap + s_base[key] + atomicAdd(&s_cnt[key], 1u)] = i;
+        return;
+    }
     for (int tk = 0; tk <= kT; ++tk)
         for (int sk = 0; sk <= kS; ++sk)
             if (strategy_class_valid(a.sc.opts, sk, tk, nS, nT)) atomicAdd(&s_cnt[(uint32_t)tk * kKeyDim + (uint32_t)sk], 1u);
@@ -73,21 +100,30 @@ __global__ void __launch_bounds__(kEnumBlock) k_connect_enum(launch_args_t a) {
                 a.st.strat_items[(size_t)key * a.st.cap + s_base[key] + atomicAdd(&s_cnt[key], 1u)] = i;
             }
 }
-__global__ void __launch_bounds__(64) k_connect_scan(launch_args_t a) {
+__global__ void __launch_bounds__(64) k_connect_scan(launch_args_t a, uint32_t by_class) {
+    __shared__ uint32_t s_key[kNumKeys];   // class form: the key of every rank
     if (a.st.ext)   // the counters of the staged connections' chunks
         for (uint32_t q = threadIdx.x; q < a.st.ext->n_chunks * kChunkCtlWords; q += 64) a.st.ext->chunk_ctl[q] = 0;
+    if (by_class)
+        for (uint32_t k = threadIdx.x; k < kNumKeys; k += 64) s_key[class_key_rank(k)] = k;
+    __syncthreads();
     if (threadIdx.x == 0) {
         uint32_t acc = 0;
-        for (uint32_t k = 0; k < kNumKeys; ++k) {
+        for (uint32_t r = 0; r < kNumKeys; ++r) {
+            const uint32_t k = by_class ? s_key[r] : r;
             const uint32_t c = a.st.strat_count[k];
-            a.st.strat_prefix[k] = acc;
-            acc += c;
+            a.st.strat_prefix[r] = acc;
+            if (by_class) {
+                a.st.strat_prefix[kClassCount + r] = c;
+                a.st.strat_prefix[kClassKey + r] = k;
+                acc += (c + 63u) & ~63u;   // (at most 63 x kNumKeys idle lanes per batch)
+            } else
+                acc += c;
             a.st.strat_count[k] = 0;   // ready for the next batch
         }
         a.st.strat_prefix[kNumKeys] = acc;
         a.st.ctl[CTL_STRAT_HEAD] = 0;
         a.st.ctl[CTL_STRAT_HEAD_OPEN] = 0;
-
     }
 }
 // OPEN = false: the buckets with one strategy each (all of them while no subpath exceeds 17 vertices).  OPEN = true (k_connect_strat_open): the
@@ -165,7 +201,86 @@ WT_D void connect_strat_body(const launch_args_t& a) {
 }
 __global__ void __launch_bounds__(kBlock, WTGPU_LB_CONNECT) k_connect_strat(launch_args_t a) { connect_strat_body<false>(a); }
 __global__ void __launch_bounds__(kBlock, WTGPU_LB_CONNECT) k_connect_strat_open(launch_args_t a) { connect_strat_body<true>(a); }
-// ---- staged connections (the default; k_connect_strat, one kernel for the whole strategy, stays as the A/B reference: WTGPU_STAGED_CONNECT=0) ---
+// The class form.  OPEN = false: the classes whose subpath lengths ARE their key (all of them while no subpath exceeds 17 vertices): the strategies
+// of an item are a wave-uniform loop.  OPEN = true (k_connect_class_open): the classes of the last row / column, whose samples have subpaths of
+// different lengths >= 18 — trip counts per lane, read from the walks; a kernel of its own so that the common case does not carry them.
+template <bool OPEN>
+WT_D void connect_class_body(const launch_args_t& a) {
+    __shared__ stack_entry_t lds[kLdsStack * kBlock];
+    __shared__ uint32_t s_prefix[kNumKeys + 1], s_count[kNumKeys], s_key[kNumKeys];
+    constexpr int K = (int)kKeyDim - 1;
+    for (uint32_t r = threadIdx.x; r < kNumKeys; r += kBlock) {
+        s_count[r] = a.st.strat_prefix[kClassCount + r];
+        s_key[r] = a.st.strat_prefix[kClassKey + r];
+    }
+    // flattened item space: OPEN = false all classes (wavefronts that grab items of an open one skip them), OPEN = true the open classes only
+    if (!OPEN) {
+        for (uint32_t r = threadIdx.x; r <= kNumKeys; r += kBlock) s_prefix[r] = a.st.strat_prefix[r];
+    } else if (threadIdx.x == 0) {
+        uint32_t acc = 0;
+        for (uint32_t r = 0; r < kNumKeys; ++r) {
+            s_prefix[r] = acc;
+            if (class_key_open(a.st.strat_prefix[kClassKey + r])) acc += (a.st.strat_prefix[kClassCount + r] + 63u) & ~63u;
+        }
+        s_prefix[kNumKeys] = acc;
+    }
+    __syncthreads();
+    const uint32_t total = s_prefix[kNumKeys];
+    const uint32_t lane = threadIdx.x & 63;
+    bdpt_counters_t ctr;
+    memset(&ctr, 0, sizeof(ctr));
+    stack_entry_t spill[kSpillStack];
+    stack_ref_t stack;
+    lds_stack(lds, spill, stack);
+    const fsd_pool_t pool{a.st.fsd_hdr, a.st.fsd_edges, a.st.ctl + CTL_FSD_COUNTER, a.st.fsd_cap, a.st.ctl + CTL_FSD_ECOUNTER, a.st.fsd_ecap};
+    for (;;) {
+        const uint32_t base = wave_grab(a.st.ctl + (OPEN ? CTL_STRAT_HEAD_OPEN : CTL_STRAT_HEAD));
+        if (base >= total) break;
+        // class of this wavefront's 64 items: last rank with prefix <= base (classes start at multiples of 64: one class per grab)
+        uint32_t lo = 0, hi = kNumKeys;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (s_prefix[mid] <= base)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const uint32_t rank = uniform(lo), key = uniform(s_key[rank]);
+        const int tk = (int)(key / kKeyDim), sk = (int)(key % kKeyDim);
+        const uint32_t off = base - uniform(s_prefix[rank]) + lane;
+        if (class_key_open(key) == OPEN && off < uniform(s_count[rank])) {   // (the open classes' items: k_connect_class_open's)
+            const uint32_t i = a.st.strat_items[(size_t)key * a.st.cap + off];
+            const uint64_t j = a.j0 + i;
+            const uint32_t pix = (uint32_t)(j % a.npix);
+            const uint64_t smp = a.sample_begin + j / a.npix;
+            const uint64_t sample_id = ((uint64_t)pix << 32) | (smp & 0xFFFFFFFFull);
+            sample_ctx_t ctx;
+            soa_load(a.st.ctx, kCtxWords, i, ctx);
+            const vertex_store_t svs{a.st.verts, a.st.vert_words, i}, evs{a.st.verts, a.st.vert_words, (size_t)a.st.cap + i};
+            int nT = tk, nS = sk;
+            if constexpr (OPEN) {
+                nT = (int)a.st.walks[(size_t)i * a.st.walk_words + WT_WALK_NVERTS_WORD];
+                nS = (int)a.st.walks[((size_t)a.st.cap + i) * a.st.walk_words + WT_WALK_NVERTS_WORD];
+            }
+            double sum[4] = {0.0, 0.0, 0.0, 0.0};   // the sample's t>1 flux, in the fixed (t, s) order
+            for (int t = 0; t <= nT; ++t)
+                for (int s = 0; s <= nS; ++s)
+                    if (strategy_valid(a.sc.opts, s, t, nS, nT)) {
+                        const stokes_t flux = bdpt_strategy(a.sc, pool, a.film, svs, evs, s, t, ctx, a.seed, sample_id, stack, &ctr, nullptr);
+                        if (t > 1) {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) sum[c] += (double)flux.s[c];
+                        }
+                    }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) a.st.lacc[(size_t)c * a.st.cap + i] = sum[c];
+        }
+    }
+    if (a.count_stats) flush_counters(a.st.counters, ctr);   // once per wavefront
+}
+__global__ void __launch_bounds__(kBlock, WTGPU_LB_CONNECT) k_connect_class(launch_args_t a) { connect_class_body<false>(a); }
+__global__ void __launch_bounds__(kBlock, WTGPU_LB_CONNECT) k_connect_class_open(launch_args_t a) { connect_class_body<true>(a); }
+// ---- staged connections (WTGPU_STAGED_CONNECT=1; the one-kernel forms above are the default) ---
 // A connection is three things with very different shapes: forming the two connecting beams (two vertex loads, two BSDF evaluations, ~200
 // registers), one any-hit ray (a BVH stack, ~90 registers, a run time that varies by two orders of magnitude), and the MIS weight (a stream
 // over both subpaths).  One kernel for all three (k_connect_strat) carries the union of their registers — 256 + a 1.5-KB frame, two wavefronts

@@ -221,18 +221,24 @@ struct batch_launcher_t {
         if (path_mode) {
             HP_LAUNCH(k_path_flush, dim3(kFlushGrid), dim3(kBlock), 0, st_, a, (int)(r.rounds_launched & 1u));
         } else {
-            HP_LAUNCH(k_connect_enum, dim3((nb + kEnumBlock - 1) / kEnumBlock), dim3(kEnumBlock), 0, st_, a);
-            HP_LAUNCH(k_connect_scan, dim3(1), dim3(64), 0, st_, a);
             const bool open = (uint32_t)s->host.opts.max_depth + 2 >= kKeyDim - 1;
             // staged connections (chunked, see upload_impl); subpaths beyond 17 vertices (open-ended strategy buckets: an item there holds several
-            // strategies) keep the one-kernel form
-            if (K.staged_connect && !open) {
+            // strategies) keep a one-kernel form
+            const bool staged = K.staged_connect && !open;
+            // the one-kernel forms: by length class (an item is a sample, k_connect_class) or by strategy (an item is one strategy, k_connect_strat)
+            const uint32_t by_class = !staged && K.connect_class ? 1u : 0u;
+            HP_LAUNCH(k_connect_enum, dim3((nb + kEnumBlock - 1) / kEnumBlock), dim3(kEnumBlock), 0, st_, a, by_class);
+            HP_LAUNCH(k_connect_scan, dim3(1), dim3(64), 0, st_, a, by_class);
+            if (staged) {
                 for (uint32_t c = 0; c < s->n_chunks; ++c) {
                     const uint32_t g = c == 0 ? gf : std::max<uint32_t>(1u, gf / 8u);   // (later chunks are normally empty: small grids, they only loop longer when not)
                     HP_LAUNCH(k_connect_eval, dim3(g), dim3(kBlock), 0, st_, a, c);
                     HP_LAUNCH(k_connect_shadow, dim3(g), dim3(kBlock), 0, st_, a, c);
                     HP_LAUNCH(k_connect_mis, dim3(g), dim3(kBlock), 0, st_, a, c);
                 }
+            } else if (by_class) {
+                HP_LAUNCH(k_connect_class, dim3(gf), dim3(kBlock), 0, st_, a);
+                if (open) HP_LAUNCH(k_connect_class_open, dim3(std::max<uint32_t>(1u, gf / 8u)), dim3(kBlock), 0, st_, a);
             } else {
                 HP_LAUNCH(k_connect_strat, dim3(gf), dim3(kBlock), 0, st_, a);
                 if (open) HP_LAUNCH(k_connect_strat_open, dim3(std::max<uint32_t>(1u, gf / 8u)), dim3(kBlock), 0, st_, a);

@@ -4,7 +4,7 @@
 //   kernels_trace.hip   k_trace_refill, k_trace_heavy (+ the per-query kernels of the traversal parity tests, the PMC calibration copy)
 //   kernels_fsd.hip     k_flux_split, k_flux_tasks, k_interact_c, k_interact_c_hard (Fraunhofer interactions: power sums, rejection sampling)
 //   kernels_path.hip    k_path_* (plt_path)
-//   kernels_connect.hip k_connect_* (strategy buckets, connections, MIS, film splat)
+//   kernels_connect.hip k_connect_* (class / strategy buckets, connections, MIS, film splat)
 //   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
 //   kernels_mask.hip    k_sensor_mask_wave / k_sensor_mask_lane: by-geometry sensor masks (not part of a render)
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
@@ -86,6 +86,21 @@ __host__ __device__ inline bool is_region_marker(uint32_t t) { return t == kGath
 // launching it for nothing cost 35 % of a pass with four streams: a 256-register, 22-KB-LDS grid that waits for free CUs holds up the other
 // streams' dispatches)
 constexpr uint32_t kKeyDim = kMaxVerts + 2, kNumKeys = kKeyDim * kKeyDim;
+// The class form of the connections (k_connect_class) buckets SAMPLES by the same key grid: (min(nT, kKeyDim-1), min(nS, kKeyDim-1)), the lengths of
+// a sample's two subpaths.  Its wavefronts take the classes in the order of descending tk x sk — the number of strategies of a sample of the class,
+// near enough — so that the rare deep classes, hundreds of strategies per item, start first and are not the kernel's tail.  Rank of a key in
+// that order (ties: the smaller key first); the ranks of the kNumKeys keys are a permutation of 0 .. kNumKeys - 1.
+__host__ __device__ constexpr uint32_t class_key_work(uint32_t key) { return (key / kKeyDim) * (key % kKeyDim); }
+__host__ __device__ constexpr uint32_t class_key_rank(uint32_t key) {
+    uint32_t r = 0;
+    for (uint32_t k = 0; k < kNumKeys; ++k)
+        if (class_key_work(k) > class_key_work(key) || (class_key_work(k) == class_key_work(key) && k < key)) ++r;
+    return r;
+}
+__host__ __device__ constexpr bool class_key_open(uint32_t key) { return key / kKeyDim == kKeyDim - 1 || key % kKeyDim == kKeyDim - 1; }
+// strat_prefix in the class form, all by RANK: [0, kNumKeys] start of the class in the flattened item space, every class padded to whole
+// wavefronts (64 items of a grab are then 64 samples of ONE class); [kClassCount + r] its samples; [kClassKey + r] its key
+constexpr uint32_t kClassCount = kNumKeys + 1, kClassKey = kClassCount + kNumKeys, kClassTableWords = kClassKey + kNumKeys;
 
 struct device_state_t {
     uint64_t cap = 0;   // samples per batch
@@ -113,9 +128,9 @@ struct device_state_t {
     fsd_edge_t* fsd_edges = nullptr;
     uint32_t fsd_cap = 0;
     uint32_t fsd_ecap = 0;            // segment records of all apertures of a batch (bump allocator)
-    uint32_t* strat_items = nullptr;    // [kNumKeys][cap] sample indices bucketed by connection strategy (s,t)
+    uint32_t* strat_items = nullptr;    // [kNumKeys][cap] sample indices bucketed by connection strategy (s,t) (class form: by the subpath lengths (nT, nS))
     uint32_t* strat_count = nullptr;    // [kNumKeys]
-    uint32_t* strat_prefix = nullptr;   // [kNumKeys + 1]
+    uint32_t* strat_prefix = nullptr;   // [kClassTableWords]: [kNumKeys + 1] prefix sums by key (class form: by rank, then the classes' sizes and keys, see kClassCount)
     double* lacc = nullptr;             // [4][cap] per-sample sum of the t>1 strategies' fluxes
     unsigned long long* counters = nullptr;   // bdpt_counters_t + 2 (shared by all slices)
     const struct bdpt_ext_t* ext = nullptr;   // more plt_bdpt state behind one pointer (device memory; the launch block must stay below 1 KB, see path_state_t)
@@ -391,10 +406,12 @@ __global__ void k_path_interact(launch_args_t a, const path_state_t* __restrict_
 __global__ void k_path_interact_b(launch_args_t a, const path_state_t* __restrict__ ps, int in, uint32_t round);
 __global__ void k_path_nee(launch_args_t a, const path_state_t* __restrict__ ps, uint32_t round);
 __global__ void k_path_flush(launch_args_t a, int in);
-__global__ void k_connect_enum(launch_args_t a);
-__global__ void k_connect_scan(launch_args_t a);
+__global__ void k_connect_enum(launch_args_t a, uint32_t by_class);
+__global__ void k_connect_scan(launch_args_t a, uint32_t by_class);
 __global__ void k_connect_strat(launch_args_t a);
 __global__ void k_connect_strat_open(launch_args_t a);
+__global__ void k_connect_class(launch_args_t a);
+__global__ void k_connect_class_open(launch_args_t a);
 __global__ void k_connect_eval(launch_args_t a, uint32_t chunk);
 __global__ void k_connect_shadow(launch_args_t a, uint32_t chunk);
 __global__ void k_connect_mis(launch_args_t a, uint32_t chunk);

@@ -58,6 +58,7 @@ const knob_t kKnobs[] = {
     {"WTGPU_SORTED_INTERACT", K(sorted_interact), KNOB_U32, 0, 0, kU32, "pass A: 0 k_interact (one kernel, every walk); 1 k_classify + one kernel per material class; 2 k_classify + k_interact_sorted"},
     {"WTGPU_COOP_IO", K(coop_io), KNOB_U32, 0, 0, kU32, "1: pass A with wave-cooperative record transfers (k_interact_coop)"},
     {"WTGPU_STAGED_CONNECT", K(staged_connect), KNOB_U32, 0, 0, kU32, "connections: 0 k_connect_strat (one kernel per strategy item); 1 k_connect_eval -> k_connect_shadow -> k_connect_mis, in chunks"},
+    {"WTGPU_CONNECT_CLASS", K(connect_class), KNOB_U32, 1, 0, kU32, "connections (the one-kernel form): 0 k_connect_strat (an item is one strategy of a sample); 1 k_connect_class (an item is a sample, bucketed by the lengths of its subpaths, all of its strategies in a row; DESIGN.md §4)"},
     {"WTGPU_TILED_SPLAT", K(tiled_splat), KNOB_U32, 1, 0, kU32, "0: the plain per-sample splat kernel"},
     {"WTGPU_TRACE_STAGED", K(trace_staged), KNOB_U32, 1, 0, kU32, "1: the traversal in stages (k_tr_axis / k_tr_cone / k_tr_policy / k_tr_tail) ..."},
     {"WTGPU_TRACE_STAGES", K(trace_stages), KNOB_U32, 3, 1, 16, "... with this many cone stages before the tail ..."},

@@ -140,6 +140,41 @@ int wtgpu_test_source_queries(wtgpu_scene* s, void* stream_, const uint32_t* d_q
     return WTGPU_OK;
 }
 
+int wtgpu_test_connect_class_order(uint32_t* keys, uint32_t cap, uint32_t* n_keys, uint32_t* key_dim) {
+    if (!n_keys || !key_dim) return fail(WTGPU_ERR_INVALID, "wtgpu_test_connect_class_order: null argument");
+    *n_keys = kNumKeys;
+    *key_dim = kKeyDim;
+    if (!keys || cap < kNumKeys) return WTGPU_OK;   // (the sizes only)
+    for (uint32_t r = 0; r < kNumKeys; ++r) keys[r] = 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < kNumKeys; ++k) {
+        const uint32_t r = class_key_rank(k);
+        if (r < kNumKeys) keys[r] = k;
+    }
+    return WTGPU_OK;
+}
+
+int wtgpu_test_connect_class_items(wtgpu_scene* s, uint32_t slice, uint32_t* table, uint32_t* items, uint32_t items_cap, uint32_t* n_items) {
+    if (!s || !s->uploaded || !table || !items || !n_items || slice >= s->slices.size()) return fail(WTGPU_ERR_INVALID, "wtgpu_test_connect_class_items: uploaded scene, a slice of it");
+    if (s->host.opts.integrator != INTEGRATOR_BDPT) return fail(WTGPU_ERR_INVALID, "wtgpu_test_connect_class_items: plt_bdpt scenes");
+    device_guard_t guard(s->device);
+    {
+        const int rc = drain_all(s);
+        if (rc) return rc;
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    const device_state_t& st = s->slices[slice];
+    HIP_CHECK(hipMemcpy(table, st.strat_prefix, kClassTableWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint64_t n = 0;
+    for (uint32_t r = 0; r < kNumKeys; ++r) {
+        const uint32_t c = table[kClassCount + r], key = table[kClassKey + r];
+        if (key >= kNumKeys || c > st.cap || n + c > items_cap) return fail(WTGPU_ERR_INVALID, "wtgpu_test_connect_class_items: not a class table (was the batch connected by k_connect_class?) or items_cap too small");
+        if (c) HIP_CHECK(hipMemcpy(items + n, st.strat_items + (size_t)key * st.cap, c * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        n += c;
+    }
+    *n_items = (uint32_t)n;
+    return WTGPU_OK;
+}
+
 int wtgpu_calibrate_copy(uint64_t n_dwords, int repeats) {
     uint32_t *in = nullptr, *out = nullptr;
     HIP_CHECK(hipMalloc((void**)&in, n_dwords * 4));

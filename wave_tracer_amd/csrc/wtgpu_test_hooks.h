@@ -43,6 +43,16 @@ int wtgpu_test_bsdf_queries(wtgpu_scene* s, void* stream, const uint32_t* d_quer
  * outside the table, an emitter index >= the scene's count or a tuid >= its triangle count returns WTGPU_ERR_INVALID and launches nothing.
  * The CPU checker's counterpart: oracle/oracle.cpp: oracle_source_queries. */
 int wtgpu_test_source_queries(wtgpu_scene* s, void* stream, const uint32_t* d_queries, uint32_t n, uint32_t* d_out);
+/* The class form of the connections (k_connect_class, WTGPU_CONNECT_CLASS=1).  N = n_keys = key_dim x key_dim length classes, key = tk * key_dim + sk
+ * (the capped subpath lengths of a class).
+ * wtgpu_test_connect_class_order: N and key_dim; with cap >= N also the keys in the order the kernel's wavefronts take the classes, descending
+ *   tk x sk, as the host computes it (wtgpu_kernels.h: class_key_rank).
+ * wtgpu_test_connect_class_items: what the LAST batch connected on state slice `slice` left behind.  table: 3 N + 1 words, all by rank — [0, N]
+ *   start of the class in the flattened item space (classes padded to multiples of 64), [N + 1 + r] its samples, [2 N + 1 + r] its key (the
+ *   device's order); items: the samples (indices into the batch) of all classes in that order, unpadded; n_items: how many.  Waits for
+ *   everything in flight. */
+int wtgpu_test_connect_class_order(uint32_t* keys, uint32_t cap, uint32_t* n_keys, uint32_t* key_dim);
+int wtgpu_test_connect_class_items(wtgpu_scene* s, uint32_t slice, uint32_t* table, uint32_t* items, uint32_t items_cap, uint32_t* n_items);
 #ifdef __cplusplus
 }
 #endif

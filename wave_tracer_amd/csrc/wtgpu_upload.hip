@@ -201,7 +201,7 @@ static int alloc_slice(wtgpu_scene* s, uint32_t k, uint64_t batch_cap, unsigned 
     if ((rc = dmalloc(s, &st.fsd_edges, (size_t)st.fsd_ecap))) return rc;
     if ((rc = dmalloc(s, &st.strat_items, path_mode ? 1 : (size_t)kNumKeys * st.cap))) return rc;
     if ((rc = dmalloc(s, &st.strat_count, (size_t)kNumKeys))) return rc;
-    if ((rc = dmalloc(s, &st.strat_prefix, (size_t)kNumKeys + 1))) return rc;
+    if ((rc = dmalloc(s, &st.strat_prefix, (size_t)kClassTableWords))) return rc;
     if ((rc = dmalloc(s, &st.lacc, 4 * (size_t)st.cap))) return rc;
     HIP_CHECK(hipMemset(st.strat_count, 0, kNumKeys * sizeof(uint32_t)));
     HIP_CHECK(hipStreamCreateWithFlags(&s->streams[k], hipStreamNonBlocking));
