@@ -179,7 +179,7 @@ def test_async_renders_pipeline_and_join(built):
 
 
 def test_tiled_film_splat_equals_the_per_sample_splat(built, monkeypatch):
-    """k_connect_splat_tiled (one block per 128-element row segment, footprints accumulated in an LDS tile, one global add per tile entry) against
+    """k_connect_splat_tiled (one block per 64-element row segment, footprints accumulated in an LDS tile, one global add per tile entry) against
     the per-sample splat kernel (WTGPU_TILED_SPLAT=0): the same films up to the order of the f64 sums — intensity and Stokes films, widths that
     are not multiples of the block, several samples per element and batch, batches that start in the middle of the film."""
     import torch
@@ -196,6 +196,27 @@ def test_tiled_film_splat_equals_the_per_sample_splat(built, monkeypatch):
         assert out["0"][0].sum() > 0 and out["0"][1].sum() > 0
         for a, b in zip(out["0"], out["1"]):
             assert np.allclose(a, b, rtol=1e-9, atol=1e-30), name
+
+
+def test_two_renders_of_one_batch_give_the_same_value_film(built):
+    """k_connect_splat_tiled adds the tiles that meet in a film element in a FIXED order: one wavefront per 64-element row segment, its blocks in six
+    launches by (row % 3, segment % 2) (wtgpu_kernels.h: kSplatPhases).  So two renders of the same single batch give the same value and weight films bit
+    for bit — before, the last bit of a few elements depended on which block came first.  Shapes: 1, 2, 3 and 4 segments per row (odd and even), heights
+    0, 1 and 2 mod 3, intensity and Stokes films, two samples per element.  (The light image is not this kernel's: it is splatted by the connections.)"""
+    from wave_tracer_amd import Scene, render
+    shapes = set()
+    for name, kw in (("furnace", dict(res=40, lut=(32, 32))), ("cornell_box", dict(res=100, mesh_detail=0)), ("cornell_box", dict(res=150, mesh_detail=0)),
+                     ("cornell_box", dict(res=200, mesh_detail=0)), ("bidir_room", dict(res=136, mesh_detail=0, polarimetric=1))):
+        sc = Scene(name, **kw)
+        sc.upload(0, 2 * sc.width * sc.height)
+        shapes.add(((sc.width + 63) // 64, sc.height % 3))
+        a, b = [render(sc, 2, seed=41) for _ in range(2)]
+        sc.close()
+        assert np.asarray(a[0]).sum() > 0 and np.asarray(a[1]).sum() > 0
+        for x, y, film in zip(a[:2], b[:2], ("value", "weight")):
+            x, y = np.asarray(x), np.asarray(y)
+            assert np.array_equal(x, y), (name, kw["res"], film, int((x != y).sum()))
+    assert {s for s, _ in shapes} >= {1, 2, 3, 4} and {h for _, h in shapes} == {0, 1, 2}, shapes
 
 
 def test_batches_enqueued_in_two_parts_render_the_same(built, monkeypatch):

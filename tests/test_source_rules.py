@@ -149,3 +149,23 @@ def test_every_knob_a_tool_or_test_sets_is_in_the_knob_table():
                     unknown.append(f"{os.path.relpath(path, ROOT)}:{i + 1}: {name}")
     assert len(used & knobs) >= 10, "the pattern no longer finds the knobs the tests set: update this test"
     assert not unknown, "set into an environment, read by nothing:\n" + "\n".join(unknown)
+
+
+# ---- the work-item vocabulary ---------------------------------------------------------------------------------------------------------------------
+def test_the_work_item_vocabulary_is_written_once():
+    """What turns a queue item into a sample is a helper of wtgpu_kernels.h (the section next to walk_ident / queue_walk), not a copy per kernel
+    form: the sample id and the Fraunhofer pool aggregate each stand ONCE in the kernel sources, and the connection kernels look their bucket up
+    through bucket_of."""
+    text = {p: open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, "kernels_*.hip")) + [os.path.join(CSRC, "wtgpu_kernels.h")])}
+    assert len(text) >= 11, "the pattern no longer matches the sources: update this test"
+    all_text = "\n".join(text.values())
+    sample_ids = re.findall(r"\(\s*\(uint64_t\)\s*pix\s*<<\s*32\s*\)", all_text)
+    assert len(sample_ids) == 1, f"the sample-id expression occurs {len(sample_ids)} times: use sample_id_of"
+    # the slice's pool, however its six fields are spelled (through a.st.ctl or a local ctl); kernels_test.hip's pool of a test probe is another one
+    pools = re.findall(r"fsd_pool_t\s*\w*\s*\{[^{};]*(?:fsd_hdr|fsd_edges|fsd_cap|CTL_FSD_COUNTER|CTL_FSD_ECOUNTER|fsd_ecap)[^{};]*\}", all_text)
+    assert len(pools) == 1, f"the fsd_pool_t aggregate is built {len(pools)} times: use fsd_pool_of"
+    assert re.search(r"fsd_pool_t\{a\.st\.fsd_hdr, a\.st\.fsd_edges, a\.st\.ctl \+ CTL_FSD_COUNTER, a\.st\.fsd_cap, a\.st\.ctl \+ CTL_FSD_ECOUNTER, a\.st\.fsd_ecap\}", pools[0])
+    hdr = text[os.path.join(CSRC, "wtgpu_kernels.h")]
+    assert "<< 32" in hdr[hdr.index("sample_id_of("):hdr.index("fsd_pool_of(")] and "fsd_pool_t{a.st.fsd_hdr" in hdr
+    assert "while (hi - lo > 1)" not in text[os.path.join(CSRC, "kernels_connect.hip")], "a bucket lookup written out: use bucket_of"
+    assert "while (hi - lo > 1)" in hdr

@@ -69,23 +69,18 @@ __global__ void __launch_bounds__(kEnumBlock) k_connect_enum(launch_args_t a, ui
     __syncthreads();
     const int K = (int)kKeyDim - 1;
     const int kT = nT < K ? nT : K, kS = nS < K ? nS : K;
-    if (by_class) {
-        // the sample's length class; EVERY sample of the batch is appended (one without a valid strategy runs none and gets its zero sum)
-        const uint32_t key = (uint32_t)max(kT, 0) * kKeyDim + (uint32_t)max(kS, 0);
-        if (i < a.nb) atomicAdd(&s_cnt[key], 1u);
-        __syncthreads();
-        for (uint32_t k = threadIdx.x; k < kNumKeys; k += kEnumBlock) {
-            const uint32_t c = s_cnt[k];
-            s_base[k] = c ? atomicAdd(a.st.strat_count + k, c) : 0u;
-            s_cnt[k] = 0;
+    // the keys of this sample.  Class form: its length class, ONE key — EVERY sample of the batch is appended (one without a valid strategy runs
+    // none and gets its zero sum).  Strategy form: the buckets that hold a valid strategy of it.  (A thread behind the batch has none: kT = kS = -1.)
+    auto each_key = [&](auto&& f) __attribute__((always_inline)) {
+        if (by_class) {
+            if (i < a.nb) f((uint32_t)max(kT, 0) * kKeyDim + (uint32_t)max(kS, 0));
+            return;
         }
-        __syncthreads();
-        if (i < a.nb) a.st.strat_items[(size_t)key * a.st.cap + s_base[key] + atomicAdd(&s_cnt[key], 1u)] = i;
-        return;
-    }
-    for (int tk = 0; tk <= kT; ++tk)
-        for (int sk = 0; sk <= kS; ++sk)
-            if (strategy_class_valid(a.sc.opts, sk, tk, nS, nT)) atomicAdd(&s_cnt[(uint32_t)tk * kKeyDim + (uint32_t)sk], 1u);
+        for (int tk = 0; tk <= kT; ++tk)
+            for (int sk = 0; sk <= kS; ++sk)
+                if (strategy_class_valid(a.sc.opts, sk, tk, nS, nT)) f((uint32_t)tk * kKeyDim + (uint32_t)sk);
+    };
+    each_key([&](uint32_t key) { atomicAdd(&s_cnt[key], 1u); });
     __syncthreads();
     for (uint32_t k = threadIdx.x; k < kNumKeys; k += kEnumBlock) {
         const uint32_t c = s_cnt[k];
@@ -93,12 +88,7 @@ __global__ void __launch_bounds__(kEnumBlock) k_connect_enum(launch_args_t a, ui
         s_cnt[k] = 0;
     }
     __syncthreads();
-    for (int tk = 0; tk <= kT; ++tk)
-        for (int sk = 0; sk <= kS; ++sk)
-            if (strategy_class_valid(a.sc.opts, sk, tk, nS, nT)) {
-                const uint32_t key = (uint32_t)tk * kKeyDim + (uint32_t)sk;
-                a.st.strat_items[(size_t)key * a.st.cap + s_base[key] + atomicAdd(&s_cnt[key], 1u)] = i;
-            }
+    each_key([&](uint32_t key) { a.st.strat_items[(size_t)key * a.st.cap + s_base[key] + atomicAdd(&s_cnt[key], 1u)] = i; });
 }
 __global__ void __launch_bounds__(64) k_connect_scan(launch_args_t a, uint32_t by_class) {
     __shared__ uint32_t s_key[kNumKeys];   // class form: the key of every rank
@@ -152,31 +142,20 @@ WT_D void connect_strat_body(const launch_args_t& a) {
     stack_entry_t spill[kSpillStack];
     stack_ref_t stack;
     lds_stack(lds, spill, stack);
-    const fsd_pool_t pool{a.st.fsd_hdr, a.st.fsd_edges, a.st.ctl + CTL_FSD_COUNTER, a.st.fsd_cap, a.st.ctl + CTL_FSD_ECOUNTER, a.st.fsd_ecap};
+    const fsd_pool_t pool = fsd_pool_of(a);
     for (;;) {
-        const uint32_t idx = wave_grab(a.st.ctl + (OPEN ? CTL_STRAT_HEAD_OPEN : CTL_STRAT_HEAD)) + (threadIdx.x & 63);
-        if (idx - (threadIdx.x & 63) >= total) break;
+        const uint32_t base = wave_grab(a.st.ctl + (OPEN ? CTL_STRAT_HEAD_OPEN : CTL_STRAT_HEAD));
+        const uint32_t idx = base + (threadIdx.x & 63);   // (in front of the break: behind it this kernel spills 263 registers instead of 204, 0.5 % of a pass in this form)
+        if (base >= total) break;
         if (idx < total) {
-            // bucket of this item: last key with prefix <= idx
-            uint32_t lo = 0, hi = kNumKeys;
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (s_prefix[mid] <= idx)
-                    lo = mid;
-                else
-                    hi = mid;
-            }
-            const uint32_t key = lo;
+            const uint32_t key = bucket_of(s_prefix, idx);
             const int tk = (int)(key / kKeyDim), sk = (int)(key % kKeyDim);
             if (!OPEN && (tk == K || sk == K)) continue;   // (k_connect_strat_open's)
             const uint32_t i = a.st.strat_items[(size_t)key * a.st.cap + (idx - s_prefix[key])];
-            const uint64_t j = a.j0 + i;
-            const uint32_t pix = (uint32_t)(j % a.npix);
-            const uint64_t smp = a.sample_begin + j / a.npix;
-            const uint64_t sample_id = ((uint64_t)pix << 32) | (smp & 0xFFFFFFFFull);
+            const uint64_t sample_id = sample_id_of(a, i);
             sample_ctx_t ctx;
             soa_load(a.st.ctx, kCtxWords, i, ctx);
-            const vertex_store_t svs{a.st.verts, a.st.vert_words, i}, evs{a.st.verts, a.st.vert_words, (size_t)a.st.cap + i};
+            const vertex_store_t svs = sensor_vertices(a, i), evs = emitter_vertices(a, i);
             auto one = [&](int s, int t) __attribute__((always_inline)) {
                 const stokes_t flux = bdpt_strategy(a.sc, pool, a.film, svs, evs, s, t, ctx, a.seed, sample_id, stack, &ctr, nullptr);
                 if (t > 1) {
@@ -208,7 +187,6 @@ template <bool OPEN>
 WT_D void connect_class_body(const launch_args_t& a) {
     __shared__ stack_entry_t lds[kLdsStack * kBlock];
     __shared__ uint32_t s_prefix[kNumKeys + 1], s_count[kNumKeys], s_key[kNumKeys];
-    constexpr int K = (int)kKeyDim - 1;
     for (uint32_t r = threadIdx.x; r < kNumKeys; r += kBlock) {
         s_count[r] = a.st.strat_prefix[kClassCount + r];
         s_key[r] = a.st.strat_prefix[kClassKey + r];
@@ -232,31 +210,20 @@ WT_D void connect_class_body(const launch_args_t& a) {
     stack_entry_t spill[kSpillStack];
     stack_ref_t stack;
     lds_stack(lds, spill, stack);
-    const fsd_pool_t pool{a.st.fsd_hdr, a.st.fsd_edges, a.st.ctl + CTL_FSD_COUNTER, a.st.fsd_cap, a.st.ctl + CTL_FSD_ECOUNTER, a.st.fsd_ecap};
+    const fsd_pool_t pool = fsd_pool_of(a);
     for (;;) {
         const uint32_t base = wave_grab(a.st.ctl + (OPEN ? CTL_STRAT_HEAD_OPEN : CTL_STRAT_HEAD));
         if (base >= total) break;
-        // class of this wavefront's 64 items: last rank with prefix <= base (classes start at multiples of 64: one class per grab)
-        uint32_t lo = 0, hi = kNumKeys;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (s_prefix[mid] <= base)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        const uint32_t rank = uniform(lo), key = uniform(s_key[rank]);
+        // class of this wavefront's 64 items (classes start at multiples of 64: one class per grab)
+        const uint32_t rank = uniform(bucket_of(s_prefix, base)), key = uniform(s_key[rank]);
         const int tk = (int)(key / kKeyDim), sk = (int)(key % kKeyDim);
         const uint32_t off = base - uniform(s_prefix[rank]) + lane;
         if (class_key_open(key) == OPEN && off < uniform(s_count[rank])) {   // (the open classes' items: k_connect_class_open's)
             const uint32_t i = a.st.strat_items[(size_t)key * a.st.cap + off];
-            const uint64_t j = a.j0 + i;
-            const uint32_t pix = (uint32_t)(j % a.npix);
-            const uint64_t smp = a.sample_begin + j / a.npix;
-            const uint64_t sample_id = ((uint64_t)pix << 32) | (smp & 0xFFFFFFFFull);
+            const uint64_t sample_id = sample_id_of(a, i);
             sample_ctx_t ctx;
             soa_load(a.st.ctx, kCtxWords, i, ctx);
-            const vertex_store_t svs{a.st.verts, a.st.vert_words, i}, evs{a.st.verts, a.st.vert_words, (size_t)a.st.cap + i};
+            const vertex_store_t svs = sensor_vertices(a, i), evs = emitter_vertices(a, i);
             int nT = tk, nS = sk;
             if constexpr (OPEN) {
                 nT = (int)a.st.walks[(size_t)i * a.st.walk_words + WT_WALK_NVERTS_WORD];
@@ -331,44 +298,26 @@ __global__ void __launch_bounds__(kBlock, WTGPU_LB_EVAL) k_connect_eval(launch_a
     bdpt_counters_t ctr;
     ctr.connections = ctr.shadow_rays = 0;
     const stack_ref_t no_stack = make_stack_ref(nullptr, 0, 0, 0, nullptr);   // (bdpt_connect<true> traces nothing)
-    const fsd_pool_t pool{a.st.fsd_hdr, a.st.fsd_edges, a.st.ctl + CTL_FSD_COUNTER, a.st.fsd_cap, a.st.ctl + CTL_FSD_ECOUNTER, a.st.fsd_ecap};
+    const fsd_pool_t pool = fsd_pool_of(a);
     for (;;) {
-        const uint32_t off = wave_grab(cctl + CHUNK_EVAL_HEAD) + (threadIdx.x & 63);
-        if (off - (threadIdx.x & 63) >= span) break;
+        const uint32_t base = wave_grab(cctl + CHUNK_EVAL_HEAD);
+        if (base >= span) break;
+        const uint32_t off = base + (threadIdx.x & 63);
         if (off < span) {
             const uint32_t idx = (uint32_t)begin + off;
-            // bucket of this item: last key with prefix <= idx
-            uint32_t lo = 0, hi = kNumKeys;
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (s_prefix[mid] <= idx)
-                    lo = mid;
-                else
-                    hi = mid;
-            }
-            const uint32_t key = lo;
+            const uint32_t key = bucket_of(s_prefix, idx);
             const int t = (int)(key / kKeyDim), s = (int)(key % kKeyDim);
             const uint32_t i = a.st.strat_items[(size_t)key * a.st.cap + (idx - s_prefix[key])];
-            const uint64_t j = a.j0 + i;
-            const uint32_t pix = (uint32_t)(j % a.npix);
-            const uint64_t smp = a.sample_begin + j / a.npix;
-            const uint64_t sample_id = ((uint64_t)pix << 32) | (smp & 0xFFFFFFFFull);
-            const vertex_store_t svs{a.st.verts, a.st.vert_words, i}, evs{a.st.verts, a.st.vert_words, (size_t)a.st.cap + i};
+            const uint64_t sample_id = sample_id_of(a, i);
+            const vertex_store_t svs = sensor_vertices(a, i), evs = emitter_vertices(a, i);
             connect_ret_t cr;
             bdpt_connect<true>(a.sc, pool, svs, evs, s, t, a.seed, sample_id, no_stack, cr, &ctr, nullptr);
             pending_append(a, cctl, cr.L.s[0] > 0.f, i, s, t, cr);
         }
     }
     if (a.count_stats) {
-        unsigned long long vc = ctr.connections, vr = ctr.shadow_rays;
-        for (int off = 32; off > 0; off >>= 1) {
-            vc += __shfl_down(vc, off, 64);
-            vr += __shfl_down(vr, off, 64);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            if (vc) atomicAdd(a.st.counters + offsetof(bdpt_counters_t, connections) / sizeof(unsigned long long), vc);
-            if (vr) atomicAdd(a.st.counters + offsetof(bdpt_counters_t, shadow_rays) / sizeof(unsigned long long), vr);
-        }
+        flush_counter(a, WT_COUNTER_SLOT(connections), ctr.connections);
+        flush_counter(a, WT_COUNTER_SLOT(shadow_rays), ctr.shadow_rays);
     }
 }
 
@@ -382,8 +331,9 @@ __global__ void __launch_bounds__(kBlock, 4) k_connect_shadow(launch_args_t a, u
     const uint32_t n = min(cctl[CHUNK_PEND_COUNT], x.pend_cap);
     if (n == 0) return;
     for (;;) {
-        const uint32_t idx = wave_grab(cctl + CHUNK_PEND_HEAD) + (threadIdx.x & 63);
-        if (idx - (threadIdx.x & 63) >= n) break;
+        const uint32_t base = wave_grab(cctl + CHUNK_PEND_HEAD);
+        if (base >= n) break;
+        const uint32_t idx = base + (threadIdx.x & 63);
         bool alive = false;
         if (idx < n) {
             const conn_pending_t& r = x.pend[idx];
@@ -399,16 +349,16 @@ __global__ void __launch_bounds__(kBlock, 4) k_connect_shadow(launch_args_t a, u
 #endif
 __global__ void __launch_bounds__(kBlock, WTGPU_LB_MIS) k_connect_mis(launch_args_t a, uint32_t chunk) {
     const bdpt_ext_t& x = *a.st.ext;
-    uint32_t* ctl = a.st.ctl;
     uint32_t* cctl = x.chunk_ctl + (size_t)chunk * kChunkCtlWords;
     const uint32_t n = cctl[CHUNK_SURV_COUNT];
     if (n == 0) return;
-    const fsd_pool_t pool{a.st.fsd_hdr, a.st.fsd_edges, ctl + CTL_FSD_COUNTER, a.st.fsd_cap, ctl + CTL_FSD_ECOUNTER, a.st.fsd_ecap};
+    const fsd_pool_t pool = fsd_pool_of(a);
     bdpt_counters_t ctr;
     ctr.light_splats = 0;
     for (;;) {
-        const uint32_t k = wave_grab(cctl + CHUNK_MIS_HEAD) + (threadIdx.x & 63);
-        if (k - (threadIdx.x & 63) >= n) break;
+        const uint32_t base = wave_grab(cctl + CHUNK_MIS_HEAD);
+        if (base >= n) break;
+        const uint32_t k = base + (threadIdx.x & 63);
         if (k < n) {   // (no divergent `continue` in front of the loop header's grab: wave_grab0 assumes a converged wavefront)
             const conn_pending_t& r = x.pend[x.surv[k]];
             const uint32_t i = r.i, st = r.st;
@@ -416,13 +366,10 @@ __global__ void __launch_bounds__(kBlock, WTGPU_LB_MIS) k_connect_mis(launch_arg
             stokes_t L;
     #pragma unroll
             for (int c = 0; c < 4; ++c) L.s[c] = r.L[c];
-            const uint64_t j = a.j0 + i;
-            const uint32_t pix = (uint32_t)(j % a.npix);
-            const uint64_t smp = a.sample_begin + j / a.npix;
-            const uint64_t sample_id = ((uint64_t)pix << 32) | (smp & 0xFFFFFFFFull);
+            const uint64_t sample_id = sample_id_of(a, i);
             sample_ctx_t ctx;
             soa_load(a.st.ctx, kCtxWords, i, ctx);
-            const vertex_store_t svs{a.st.verts, a.st.vert_words, i}, evs{a.st.verts, a.st.vert_words, (size_t)a.st.cap + i};
+            const vertex_store_t svs = sensor_vertices(a, i), evs = emitter_vertices(a, i);
             vertex_nb_t tv;
             sensor_element_t element;
             bool has_element = false;
@@ -435,11 +382,7 @@ __global__ void __launch_bounds__(kBlock, WTGPU_LB_MIS) k_connect_mis(launch_arg
             }
         }
     }
-    if (a.count_stats) {
-        unsigned long long v = ctr.light_splats;
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd(a.st.counters + offsetof(bdpt_counters_t, light_splats) / sizeof(unsigned long long), v);
-    }
+    if (a.count_stats) flush_counter(a, WT_COUNTER_SLOT(light_splats), ctr.light_splats);
 }
 
 __global__ void __launch_bounds__(kBlock) k_connect_splat(launch_args_t a) {
@@ -453,22 +396,26 @@ __global__ void __launch_bounds__(kBlock) k_connect_splat(launch_args_t a) {
     film_splat(a.sc, a.film, ctx.element, L, ctx.k);
 }
 
-// The same splat for batches that cover (most of) the film: one block per 128-element row segment accumulates the footprints of its
-// elements' samples in an LDS tile (3 rows x 130 columns x (planes + 1) f64, plane-major) and adds the tile to the film once.  Per sample the
+// The same splat for batches that cover (most of) the film: one block per 64-element row segment accumulates the footprints of its
+// elements' samples in an LDS tile (3 rows x 66 columns x (planes + 1) f64, plane-major) and adds the tile to the film once.  Per sample the
 // plain kernel issues 9 x (planes + 1) f64 atomics on addresses its neighbours in the wavefront hit too — 117 for the Stokes film of the
 // polarimetric workload, where it took 19.7 ms of a 204-ms batch (run r4t) — the tile turns them into LDS atomics and one global add per tile
-// entry.  Same weights, same products, f64 sums in another order.  Reconstruction-filter radius <= 1 (the host launches the plain kernel
+// entry.  Same weights, same products, f64 sums in another order — a FIXED one: a film element gets the sums of up to six tiles (three rows x two
+// neighbouring segments), and where a bright element lies next to a dark one these do not add up exactly, so the last bit of the film depended on
+// which block came first (two renders of one batch differed in a few elements by one ulp: tests/test_gpu_heavy_uniform.py).  Hence one WAVEFRONT
+// per block — the order inside a tile is the program's — and the blocks in kSplatPhases launches, one after the other on the batch's stream, by
+// (row % 3, segment % 2): no two blocks of a launch touch the same film element.  Reconstruction-filter radius <= 1 (the host launches the plain kernel
 // otherwise); a sample whose element is not where the block expects it (never, for the sensors built so far) goes to the film directly.
-__global__ void __launch_bounds__(kBlock) k_connect_splat_tiled(launch_args_t a) {
+__global__ void __launch_bounds__(kSplatBlock) k_connect_splat_tiled(launch_args_t a, uint32_t phase) {
     extern __shared__ double tile[];   // [planes + 1][3][kSplatCols]
     const sensor_t& sn = a.sc.sensor;
     const uint32_t W = a.film.width, H = a.film.height;
     const uint32_t S = film_stokes(sn), P = sn.channels * S, PL = P + 1;
-    const uint32_t bpr = (W + kBlock - 1) / kBlock;
-    const uint32_t row = blockIdx.x / bpr, x0 = (blockIdx.x % bpr) * kBlock;
-    const int r = sn.rf_radius;
+    // this launch's blocks: rows phase / 2, + 3, ...; of each, the segments phase % 2, + 2, ...  (wtgpu_kernels.h: kSplatPhases)
+    const uint32_t spr = splat_phase_segments(phase, splat_segments(W));
+    const uint32_t row = splat_block_row(phase, blockIdx.x, spr), x0 = splat_block_segment(phase, blockIdx.x, spr) * kSplatBlock;
     const uint32_t n_px = 3 * kSplatCols;
-    for (uint32_t q = threadIdx.x; q < n_px * PL; q += kBlock) tile[q] = 0.0;
+    for (uint32_t q = threadIdx.x; q < n_px * PL; q += kSplatBlock) tile[q] = 0.0;
     __syncthreads();
     const uint32_t x = x0 + threadIdx.x;
     if (x < W && row < H) {
@@ -481,43 +428,20 @@ __global__ void __launch_bounds__(kBlock) k_connect_splat_tiled(launch_args_t a)
             stokes_t L;
 #pragma unroll
             for (int c = 0; c < 4; ++c) L.s[c] = (float)a.st.lacc[(size_t)c * a.st.cap + i];
-            // (what follows is film_splat, wt/film.h, with the tile in place of the film)
-            const rfilter_weights_t rw = film_rfilter_weights(sn, ctx.element.offset);
-            float val[16];
-            for (uint32_t c = 0; c < sn.channels; ++c) {
-                const float f = spectrum_f(a.sc, sn.response_spec[c], ctx.k);
-                bool ok = true;
-                for (uint32_t q = 0; q < S; ++q) {
-                    val[c * S + q] = L.s[q] * f;
-                    ok = ok && finitef(val[c * S + q]);
-                }
-                ok = ok && val[c * S] >= 0.f;
-                if (!ok)
-                    for (uint32_t q = 0; q < S; ++q) val[c * S + q] = 0.f;
-            }
-            for (int dy = -r; dy <= r; ++dy) {
-                const int y = (int)ctx.element.y + dy;
-                if (y < 0 || y >= (int)H) continue;
-                for (int dx = -r; dx <= r; ++dx) {
-                    const int xx = (int)ctx.element.x + dx;
-                    if (xx < 0 || xx >= (int)W) continue;
-                    const float w = fmaxf_(0.f, rw.wx[dx + r] * rw.wy[dy + r]) * rw.recp_total;
-                    const int ty = y - ((int)row - 1), tx = xx - ((int)x0 - 1);
-                    if (ty >= 0 && ty < 3 && tx >= 0 && tx < (int)kSplatCols) {
-                        const uint32_t q = (uint32_t)ty * kSplatCols + (uint32_t)tx;
-                        unsafeAtomicAdd(&tile[q], (double)w);
-                        for (uint32_t c = 0; c < P; ++c) unsafeAtomicAdd(&tile[(size_t)(1 + c) * n_px + q], (double)(w * val[c]));
-                    } else {
-                        const size_t pix = (size_t)y * W + xx;
-                        film_add(&a.film.weight[pix], (double)w);
-                        for (uint32_t c = 0; c < P; ++c) film_add(&a.film.value[pix * P + c], (double)(w * val[c]));
-                    }
-                }
-            }
+            // film_splat (wt/film.h) with the tile in place of the film
+            film_splat_footprint(a.sc, W, H, ctx.element, L, ctx.k, [&](int xx, int y, float w, const float* val, uint32_t) {
+                const int ty = y - ((int)row - 1), tx = xx - ((int)x0 - 1);
+                if (ty >= 0 && ty < 3 && tx >= 0 && tx < (int)kSplatCols) {
+                    const uint32_t q = (uint32_t)ty * kSplatCols + (uint32_t)tx;
+                    unsafeAtomicAdd(&tile[q], (double)w);
+                    for (uint32_t c = 0; c < P; ++c) unsafeAtomicAdd(&tile[(size_t)(1 + c) * n_px + q], (double)(w * val[c]));
+                } else
+                    film_splat_add(a.film, xx, y, w, val, P);
+            });
         }
     }
     __syncthreads();
-    for (uint32_t q = threadIdx.x; q < n_px; q += kBlock) {
+    for (uint32_t q = threadIdx.x; q < n_px; q += kSplatBlock) {
         const int y = (int)row - 1 + (int)(q / kSplatCols), xx = (int)x0 - 1 + (int)(q % kSplatCols);
         if (y < 0 || y >= (int)H || xx < 0 || xx >= (int)W) continue;
         const size_t pix = (size_t)y * W + xx;

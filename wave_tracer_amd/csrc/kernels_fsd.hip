@@ -24,7 +24,7 @@ __global__ void __launch_bounds__(64, 3) k_flux_split(launch_args_t a) {
         bool need = false;
         if (base + (uint32_t)lane < n) {
             w_mine = a.st.intc_queue[base + lane];
-            need = is_region_marker(a.st.trav[(size_t)w_mine * kTravWords + WT_TRAV_WORD(tuid)]);
+            need = is_region_marker(WT_TRAV_U(a, w_mine, tuid));
         }
         unsigned long long m = __ballot(need);
         while (m) {
@@ -33,15 +33,14 @@ __global__ void __launch_bounds__(64, 3) k_flux_split(launch_args_t a) {
             const uint32_t w = (uint32_t)__shfl((int)w_mine, src, 64);   // block-uniform
             const walk_trace_in_t wk = walk_load_trace_in(a.st.walks, a.st.walk_words, w);
             const cone_t tcone = walk_trace_envelope(a.sc, wk);
-            const float beam_dist = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(dist)]);
-            const float region_depth = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(region_depth)]);
+            const float beam_dist = WT_TRAV_F(a, w, dist), region_depth = WT_TRAV_F(a, w, region_depth);
             if (threadIdx.x == 0) a.st.facc[w] = 0.0;
             coop_split(a.sc, tcone, range_t{beam_dist, beam_dist + region_depth}, sh, a.flux_task_tris, [&](int32_t ptr) {
                 const uint32_t idx = atomicAdd(ctl + CTL_FTASK_COUNT, 1u);
                 if (idx < a.st.ftask_cap)
                     a.st.ftasks[idx] = make_uint2(w, (uint32_t)ptr);
                 else
-                    atomicAdd(a.st.counters + offsetof(bdpt_counters_t, fsd_pool_overflow) / sizeof(unsigned long long), 1ull);   // reported; cannot happen below 4M tasks per batch
+                    atomicAdd(a.st.counters + WT_COUNTER_SLOT(fsd_pool_overflow), 1ull);   // reported; cannot happen below 4M tasks per batch
             });
             __syncthreads();
         }
@@ -52,7 +51,6 @@ __global__ void __launch_bounds__(64, WTGPU_LB_FLUX) k_flux_tasks(launch_args_t 
     coop_set_dropped_counter(sh, a.st.counters + kDroppedSlot);
     uint32_t* ctl = a.st.ctl;
     const uint32_t n = min(ctl[CTL_FTASK_COUNT], a.st.ftask_cap);
-    const size_t W2 = 2 * (size_t)a.st.cap;
     for (;;) {
         const uint32_t item = wave_grab_item(ctl + CTL_FTASK_HEAD);
         if (item >= n) break;
@@ -60,9 +58,8 @@ __global__ void __launch_bounds__(64, WTGPU_LB_FLUX) k_flux_tasks(launch_args_t 
         const uint32_t w = task.x;
         walk_t wk;
         soa_load(a.st.walks, a.st.walk_words, w, wk);   // uniform address: broadcast
-        const float beam_dist = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(dist)]);
-        const float region_depth = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(region_depth)]);
-        const bool want_front = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(front_face)] != 0;
+        const float beam_dist = WT_TRAV_F(a, w, dist), region_depth = WT_TRAV_F(a, w, region_depth);
+        const bool want_front = WT_TRAV_U(a, w, front_face) != 0;
         const range_t izr{beam_dist, beam_dist + region_depth};
         const vec3 sd3 = beam_footprint(wk.beam, beam_dist) / kBeamEnvelope;
         const cone_t tcone = walk_trace_envelope(a.sc, wk);
@@ -110,8 +107,7 @@ WT_D void interact_c_body(const launch_args_t& a, int in) {
     const int tid = threadIdx.x, lane = threadIdx.x & 63;
     bdpt_counters_t ctr;
     memset(&ctr, 0, sizeof(ctr));
-    const size_t W2 = 2 * (size_t)a.st.cap;
-    const fsd_pool_t pool{a.st.fsd_hdr, a.st.fsd_edges, ctl + CTL_FSD_COUNTER, a.st.fsd_cap, ctl + CTL_FSD_ECOUNTER, a.st.fsd_ecap};
+    const fsd_pool_t pool = fsd_pool_of(a);
     for (;;) {
         const long long pl0 = a.profile == 3 ? clock64() : 0;
         uint32_t item = 0;
@@ -126,11 +122,9 @@ WT_D void interact_c_body(const launch_args_t& a, int in) {
         const uint32_t w = queue_in[item];
         uint32_t i, stream;
         walk_ident(a, w, i, stream);
-        const uint64_t j = a.j0 + i;
-        const uint32_t pix = (uint32_t)(j % a.npix);
-        const uint64_t sample_id = ((uint64_t)pix << 32) | ((a.sample_begin + j / a.npix) & 0xFFFFFFFFull);
+        const uint64_t sample_id = sample_id_of(a, i);
         const uint32_t rng_draws = a.st.walks[(size_t)w * a.st.walk_words + WT_WALK_WORD(rng_draws)];
-        const uint32_t slot = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(by)];   // left by pass B
+        const uint32_t slot = WT_TRAV_U(a, w, by);   // left by pass B
         fsd_aperture_t ap = pool.hdr[slot];
         const fsd_edges_ref_t ed = fsd_pool_edges(pool, slot);
         const long long pc0 = a.profile == 3 ? clock64() : 0;
@@ -138,10 +132,9 @@ WT_D void interact_c_body(const launch_args_t& a, int in) {
             // ---- intercepted power of the whole region (same z-slab, cone and facing as the reference's list-based sum)
             const walk_trace_in_t wk = walk_load_trace_in(a.st.walks, a.st.walk_words, w);   // uniform address: broadcast
             cone_t benv = wk.env;   // the beam's own envelope (not offset for tracing)
-            const float tr_dist = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(dist)]);
-            const float tr_depth = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(region_depth)]);
-            const uint32_t tr_tuid = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(tuid)], tr_ntris = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(ntris)];
-            const bool tr_front = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(front_face)] != 0;
+            const float tr_dist = WT_TRAV_F(a, w, dist), tr_depth = WT_TRAV_F(a, w, region_depth);
+            const uint32_t tr_tuid = WT_TRAV_U(a, w, tuid), tr_ntris = WT_TRAV_U(a, w, ntris);
+            const bool tr_front = WT_TRAV_U(a, w, front_face) != 0;
             const range_t izr{tr_dist, tr_dist + tr_depth};
             const vec2 axes = cone_axes(benv, tr_dist);
             const vec2 sigma{axes.x / kBeamEnvelope, axes.y / kBeamEnvelope};
@@ -248,7 +241,7 @@ WT_D void interact_c_body(const launch_args_t& a, int in) {
             defer.fs = fsd_finalize(ap, acc, vec2{rx, ry}, rf);
             defer.end_draws = fsd_draws_after(base, acc ? t_acc : max_tries - 1u);
             const uint_list_t tris{a.st.tris + (size_t)w * kTriListWords, 1u, kMaxConeTris};
-            const vertex_store_t vs{a.st.verts, a.st.vert_words, w};
+            const vertex_store_t vs = walk_vertices(a, w);
             stack_ref_t stack = make_stack_ref(lds, 1, 8, 8, nullptr);
             cont = bdpt_walk_step<2>(a.sc, wk, tr, tris, vs, pool, a.seed, sample_id, stream, &ctr, &stack, &defer);
             wk.active = cont ? 1u : 0u;

@@ -9,22 +9,12 @@ namespace wtk {
 __global__ void __launch_bounds__(kBlock) k_path_generate(launch_args_t a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i == 0) {
-        uint32_t* ctl = a.st.ctl;
-        ctl[CTL_COUNT0] = a.nb;
-        ctl[CTL_COUNT1] = 0;
-        ctl[CTL_BACK0] = ctl[CTL_BACK1] = 0;
-        ctl[CTL_UTD_COUNT0] = ctl[CTL_UTD_COUNT1] = ctl[CTL_FSDQ_COUNT0] = ctl[CTL_FSDQ_COUNT1] = ctl[CTL_FSDQ_HEAD] = ctl[CTL_NEEQ_COUNT] = ctl[CTL_NEEQ_HEAD] = 0;
-        ctl[CTL_HEAD_TRACE] = ctl[CTL_HEAD_INTERACT] = ctl[CTL_HEAVY_COUNT] = ctl[CTL_HEAVY_HEAD] = ctl[CTL_FSD_COUNTER] = ctl[CTL_ROUNDS] = 0;
-        ctl[CTL_TPOL_COUNT0] = ctl[CTL_TPOL_COUNT1] = ctl[CTL_TPOL_HEAD] = ctl[CTL_TCONE_COUNT0] = ctl[CTL_TCONE_COUNT1] = ctl[CTL_TCONE_HEAD] = 0;   // the staged trace kernels' queues
-        ctl[CTL_INTB_COUNT] = ctl[CTL_INTB_HEAD] = ctl[CTL_GATHER_COUNT] = ctl[CTL_GATHER_HEAD] = ctl[CTL_INTC_COUNT] = ctl[CTL_INTC_HEAD] = 0;
-        ctl[CTL_FTASK_COUNT] = ctl[CTL_FTASK_HEAD] = ctl[CTL_FSPLIT_HEAD] = ctl[CTL_EPOOL_COUNT] = ctl[CTL_FSD_ECOUNTER] = 0;
-        ctl[CTL_INTD_COUNT] = ctl[CTL_INTD_HEAD] = 0;
+        ctl_reset_batch(a.st.ctl);
+        a.st.ctl[CTL_COUNT0] = a.nb;
     }
     if (i >= a.nb) return;
-    const uint64_t j = a.j0 + i;
-    const uint32_t pix = (uint32_t)(j % a.npix);
-    const uint64_t s = a.sample_begin + j / a.npix;
-    const uint64_t sample_id = ((uint64_t)pix << 32) | (s & 0xFFFFFFFFull);
+    uint32_t pix;
+    const uint64_t sample_id = sample_id_of(a, i, pix);
     path_walk_t pw;
     path_generate(a.sc, a.seed, sample_id, pix % a.sc.sensor.width, pix / a.sc.sensor.width, pw);
     soa_store(a.st.walks, a.st.walk_words, i, pw);
@@ -57,13 +47,14 @@ __global__ void __launch_bounds__(64, 3) k_path_fsd(launch_args_t a, const path_
     constexpr int G = WTGPU_FSD_GROUP, NG = 64 / G;
     const uint32_t group = (threadIdx.x & 63u) / (uint32_t)G;
     for (;;) {
-        const uint32_t item = wave_grab0(ctl + CTL_FSDQ_HEAD, (uint32_t)NG) + group;   // NG walks per wavefront, G lanes each
-        if (item - group >= n) break;
+        const uint32_t base = wave_grab0(ctl + CTL_FSDQ_HEAD, (uint32_t)NG);   // NG walks per wavefront, G lanes each
+        if (base >= n) break;
+        const uint32_t item = base + group;
         uint32_t w = 0;
         bool have = item < n;
         if (have) {
             w = P.fsdq[qin][item];
-            have = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(empty)] == 0;   // (an empty record: the step ends before do_fsd, plt_path_detail.hpp:577-581)
+            have = WT_TRAV_U(a, w, empty) == 0;   // (an empty record: the step ends before do_fsd, plt_path_detail.hpp:577-581)
         }
         // (the lanes of a group read the same words: one record per group; fields the sum does not use are never loaded)
         path_walk_t pw;
@@ -71,10 +62,7 @@ __global__ void __launch_bounds__(64, 3) k_path_fsd(launch_args_t a, const path_
         vec3 interaction_wp{0.f, 0.f, 0.f};
         if (have) {
             soa_load(a.st.walks, a.st.walk_words, w, pw);
-            const vec3 origin{__uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(origin.x)]), __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(origin.y)]),
-                              __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(origin.z)])};
-            const float dist = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(dist)]);
-            interaction_wp = origin + dist * pw.w.beam.env.d;
+            interaction_wp = trav_origin(a, w) + WT_TRAV_F(a, w, dist) * pw.w.beam.env.d;
         }
         const float f = coop_do_fsd<G>(a.sc, pw.prev_beam.env, path_geo_prev(pw.w), interaction_wp, pw.ap, prev_pool + pw.ap.edge_offset, pw.w.beam.k, stack, &ctr, have);
         if (have && (threadIdx.x & (uint32_t)(G - 1)) == 0) P.fsd_f[w] = f;
@@ -100,12 +88,9 @@ __global__ void __launch_bounds__(64, 2) k_path_edges(launch_args_t a, const pat
         if (item >= n) break;
         const uint32_t w = a.st.gather_queue[item];
         const walk_trace_in_t wk = walk_load_trace_in(a.st.walks, a.st.walk_words, w);   // uniform address: broadcast
-        const uint32_t tr_ballistic = a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(ballistic)];
-        const float dist = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(dist)]);
-        const float depth = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(region_depth)]);
-        const vec3 origin{__uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(origin.x)]), __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(origin.y)]),
-                          __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(origin.z)])};
-        const bool ballistic = tr_ballistic || cone_is_ray(wk.env);
+        const float dist = WT_TRAV_F(a, w, dist), depth = WT_TRAV_F(a, w, region_depth);
+        const vec3 origin = trav_origin(a, w);
+        const bool ballistic = WT_TRAV_U(a, w, ballistic) || cone_is_ray(wk.env);
         cone_t cone = wk.env;
         range_t slab{dist, dist + depth};
         bool any = true;
@@ -126,21 +111,11 @@ __global__ void __launch_bounds__(64, 2) k_path_edges(launch_args_t a, const pat
             const gather_out_t g = coop_gather(a.sc, cone, slab, cone, cone_frame(cone), slab, vec2{1.f, 1.f}, false, sh, false, true, nullptr, 1, &eg);
             __syncthreads();
             // (every id list goes into the round's edge pool: the walk's triangle-list slot is read again as triangles by PASS 1)
-            const bool bitmap = a.sc.n_edges <= kCoopEdgeBits;
-            n_edges = bitmap ? coop_edge_count(a.sc, eg) : g.n_edges;
-            dropped = bitmap ? 0u : g.edge_overflow;
-            off = wave_grab0(ctl + CTL_EPOOL_COUNT, n_edges);
-            if (off + n_edges > a.st.epool_cap) {   // pool exhausted (8M ids per round): reported
-                dropped += n_edges;
-                n_edges = 0;
-            } else if (bitmap)
-                coop_edge_write(a.sc, eg, a.st.epool + off, n_edges);
-            else
-                for (uint32_t j = threadIdx.x; j < n_edges; j += 64) a.st.epool[off + j] = eg.edge_ids[j];
+            off = edges_to_pool(a, g, eg, n_edges, dropped);
         }
         if (threadIdx.x == 0) {
             P.gather_info[w] = make_uint2(off, n_edges);
-            if (dropped && a.count_stats) atomicAdd(a.st.counters + offsetof(bdpt_counters_t, edge_overflow) / sizeof(unsigned long long), (unsigned long long)dropped);
+            if (dropped && a.count_stats) atomicAdd(a.st.counters + WT_COUNTER_SLOT(edge_overflow), (unsigned long long)dropped);
         }
         __syncthreads();
     }
@@ -152,11 +127,7 @@ WT_D void path_interact_body(const launch_args_t& a, const path_state_t& P, int 
     __shared__ stack_entry_t lds[kLdsStack * kBlock];
     uint32_t* ctl = a.st.ctl;
     const uint32_t n = PASS ? ctl[CTL_GATHER_COUNT] : queue_count(ctl, in);
-    if (!PASS && blockIdx.x == 0 && threadIdx.x == 0) {
-        ctl[CTL_HEAVY_COUNT] = 0;   // for the next round's k_trace
-        ctl[CTL_HEAVY_HEAD] = 0;
-        ctl[CTL_HEAD_TRACE] = 0;
-    }
+    if (!PASS && blockIdx.x == 0 && threadIdx.x == 0) interact_round_begin(ctl);
     bdpt_counters_t ctr;
     memset(&ctr, 0, sizeof(ctr));
     stack_entry_t spill[kSpillStack];
@@ -166,16 +137,14 @@ WT_D void path_interact_body(const launch_args_t& a, const path_state_t& P, int 
     const utd_pool_t pool{P.utd[round & 1u], ctl + CTL_UTD_COUNT0 + (round & 1u), P.utd_cap};
     const utd_edge_rec_t* prev_pool = P.utd[(round + 1u) & 1u];
     for (;;) {
-        const uint32_t qi = wave_grab(ctl + (PASS ? CTL_INTB_HEAD : CTL_HEAD_INTERACT)) + (threadIdx.x & 63);
-        if (qi - (threadIdx.x & 63) >= n) break;
+        const uint32_t base = wave_grab(ctl + (PASS ? CTL_INTB_HEAD : CTL_HEAD_INTERACT));
+        if (base >= n) break;
+        const uint32_t qi = base + (threadIdx.x & 63);
         bool cont = false, carries_fsd = false, nee = false, gather = false;
         uint32_t w = 0;
         if (qi < n) {
             w = PASS ? a.st.gather_queue[qi] : queue_walk(a, ctl, in, qi, first_round);
-            const uint64_t j = a.j0 + w;
-            const uint32_t pix = (uint32_t)(j % a.npix);
-            const uint64_t s = a.sample_begin + j / a.npix;
-            const uint64_t sample_id = ((uint64_t)pix << 32) | (s & 0xFFFFFFFFull);
+            const uint64_t sample_id = sample_id_of(a, w);   // (one walk per sample)
             path_walk_t pw;
             soa_load(a.st.walks, a.st.walk_words, w, pw);
             trav_result_t tr;
@@ -237,8 +206,9 @@ __global__ void __launch_bounds__(64, 3) k_path_nee(launch_args_t a, const path_
     constexpr int G = WTGPU_FSD_GROUP, NG = 64 / G;
     const uint32_t group = (threadIdx.x & 63u) / (uint32_t)G;
     for (;;) {
-        const uint32_t item = wave_grab0(ctl + CTL_NEEQ_HEAD, (uint32_t)NG) + group;   // NG walks per wavefront, G lanes each
-        if (item - group >= n) break;
+        const uint32_t base = wave_grab0(ctl + CTL_NEEQ_HEAD, (uint32_t)NG);   // NG walks per wavefront, G lanes each
+        if (base >= n) break;
+        const uint32_t item = base + group;
         const bool have = item < n;
         const uint32_t w = have ? P.neeq[item] : 0u;
         // what the coherent sum reads of the walk's record (the whole record — two beams — only in the lane that splats)
@@ -275,7 +245,6 @@ __global__ void __launch_bounds__(64, 3) k_path_nee(launch_args_t a, const path_
 // walks still active after the last round (iteration cap): backward transport splats what they gathered
 __global__ void __launch_bounds__(kBlock) k_path_flush(launch_args_t a, int in) {
     const uint32_t n = queue_count(a.st.ctl, in);
-    const size_t W2 = 2 * (size_t)a.st.cap;
     for (uint32_t qi = blockIdx.x * kBlock + threadIdx.x; qi < n; qi += kFlushGrid * kBlock) {
         const uint32_t w = queue_walk(a, a.st.ctl, in, qi, 0);
         path_walk_t pw;

@@ -7,25 +7,15 @@ namespace wtk {
 __global__ void __launch_bounds__(kBlock) k_generate(launch_args_t a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i == 0) {
-        uint32_t* ctl = a.st.ctl;
-        ctl[CTL_COUNT0] = 2 * a.nb;
-        ctl[CTL_COUNT1] = 0;
-        ctl[CTL_BACK0] = ctl[CTL_BACK1] = 0;
-        ctl[CTL_HEAD_TRACE] = ctl[CTL_HEAD_INTERACT] = ctl[CTL_HEAVY_COUNT] = ctl[CTL_HEAVY_HEAD] = ctl[CTL_FSD_COUNTER] = ctl[CTL_ROUNDS] = 0;
-        ctl[CTL_TPOL_COUNT0] = ctl[CTL_TPOL_COUNT1] = ctl[CTL_TPOL_HEAD] = ctl[CTL_TCONE_COUNT0] = ctl[CTL_TCONE_COUNT1] = ctl[CTL_TCONE_HEAD] = 0;   // the staged trace kernels' queues
-        ctl[CTL_INTB_COUNT] = ctl[CTL_INTB_HEAD] = ctl[CTL_GATHER_COUNT] = ctl[CTL_GATHER_HEAD] = ctl[CTL_INTC_COUNT] = ctl[CTL_INTC_HEAD] = 0;
-        ctl[CTL_FTASK_COUNT] = ctl[CTL_FTASK_HEAD] = ctl[CTL_FSPLIT_HEAD] = ctl[CTL_EPOOL_COUNT] = ctl[CTL_FSD_ECOUNTER] = 0;
-        ctl[CTL_INTD_COUNT] = ctl[CTL_INTD_HEAD] = 0;
+        ctl_reset_batch(a.st.ctl);
+        a.st.ctl[CTL_COUNT0] = 2 * a.nb;
     }
     if (i >= a.nb) return;
-    const uint64_t j = a.j0 + i;
-    const uint32_t pix = (uint32_t)(j % a.npix);
-    const uint64_t s = a.sample_begin + j / a.npix;
-    const uint64_t sample_id = ((uint64_t)pix << 32) | (s & 0xFFFFFFFFull);
-    const size_t W2 = 2 * (size_t)a.st.cap;
+    uint32_t pix;
+    const uint64_t sample_id = sample_id_of(a, i, pix);
     sample_ctx_t ctx;
     walk_t sw, ew;
-    const vertex_store_t svs{a.st.verts, a.st.vert_words, i}, evs{a.st.verts, a.st.vert_words, (size_t)a.st.cap + i};
+    const vertex_store_t svs = sensor_vertices(a, i), evs = emitter_vertices(a, i);
     bdpt_generate(a.sc, a.seed, sample_id, pix % a.sc.sensor.width, pix / a.sc.sensor.width, ctx, sw, ew, svs, evs);
     soa_store(a.st.ctx, kCtxWords, i, ctx);
     soa_store(a.st.walks, a.st.walk_words, i, sw);
@@ -46,20 +36,16 @@ WT_D void interact_body(const launch_args_t& a, int in, int first_round) {
     uint32_t* io = s_io + (COOP ? (threadIdx.x >> 6) * kIoRows * io_pitch<(int)kVertexWords>() : 0);
     uint32_t* ctl = a.st.ctl;
     const uint32_t n = PASS_B ? ctl[CTL_INTB_COUNT] : queue_count(ctl, in);
-    if (!PASS_B && blockIdx.x == 0 && threadIdx.x == 0) {
-        ctl[CTL_HEAVY_COUNT] = 0;   // for the next round's k_trace
-        ctl[CTL_HEAVY_HEAD] = 0;
-        ctl[CTL_HEAD_TRACE] = 0;
-    }
+    if (!PASS_B && blockIdx.x == 0 && threadIdx.x == 0) interact_round_begin(ctl);
     bdpt_counters_t ctr;
     memset(&ctr, 0, sizeof(ctr));
-    const size_t W2 = 2 * (size_t)a.st.cap;
-    const fsd_pool_t pool{a.st.fsd_hdr, a.st.fsd_edges, ctl + CTL_FSD_COUNTER, a.st.fsd_cap, ctl + CTL_FSD_ECOUNTER, a.st.fsd_ecap};
+    const fsd_pool_t pool = fsd_pool_of(a);
     // (Taking 4 x 64 / 16 x 64 queue items per atomic on the queue's head, to see whether the hot-address atomics of the persistent loops hold
     // the kernel up: exclusive time of k_interact 95.4 -> 100.9 / 163.6 ms per three steps, run r5j — they do not; larger grabs only unbalance the tail.)
     for (;;) {
-        const uint32_t qi = wave_grab(ctl + (PASS_B ? CTL_INTB_HEAD : CTL_HEAD_INTERACT)) + (threadIdx.x & 63);
-        if (qi - (threadIdx.x & 63) >= n) break;
+        const uint32_t base = wave_grab(ctl + (PASS_B ? CTL_INTB_HEAD : CTL_HEAD_INTERACT));
+        if (base >= n) break;
+        const uint32_t qi = base + (threadIdx.x & 63);
         bool cont = false;
         uint32_t w = 0;
         fsd_defer_t defer;
@@ -89,10 +75,7 @@ WT_D void interact_body(const launch_args_t& a, int in, int first_round) {
         if (valid) {
             uint32_t i, stream;
             walk_ident(a, w, i, stream);
-            const uint64_t j = a.j0 + i;
-            const uint32_t pix = (uint32_t)(j % a.npix);
-            const uint64_t s = a.sample_begin + j / a.npix;
-            const uint64_t sample_id = ((uint64_t)pix << 32) | (s & 0xFFFFFFFFull);
+            const uint64_t sample_id = sample_id_of(a, i);
             if constexpr (!COOP) {
                 soa_load(a.st.walks, a.st.walk_words, w, wk);
                 soa_load(a.st.trav, kTravWords, w, tr);
@@ -113,7 +96,7 @@ WT_D void interact_body(const launch_args_t& a, int in, int first_round) {
             }
             const long long pb0 = PASS_B && a.profile == 3 ? clock64() : 0;
             if (!queued_for_c) cont = bdpt_walk_step<PASS_B ? 2 : 1>(a.sc, wk, tr, tris, vs, pool, a.seed, sample_id, stream, &ctr, nullptr, &defer);
-            if (PASS_B && defer.to_sampling_pass) a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(by)] = defer.slot;
+            if (PASS_B && defer.to_sampling_pass) WT_TRAV_U(a, w, by) = defer.slot;
             if (PASS_B && a.profile == 3) {   // pass-B cost by the number of gathered scene edges
                 const int bin = defer.has_gather ? 32 - __clz((int)defer.gather_n_edges) : 0;   // 0: no gather / none
                 atomicAdd(a.st.counters + kNumCounters + 56 + bin, 1ull);
@@ -150,16 +133,13 @@ WT_D void interact_body(const launch_args_t& a, int in, int first_round) {
 __global__ void __launch_bounds__(kBlock) k_classify(launch_args_t a, int in, int first_round) {
     uint32_t* ctl = a.st.ctl;
     const uint32_t n = queue_count(ctl, in);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ctl[CTL_HEAVY_COUNT] = 0;   // for the next round's k_trace
-        ctl[CTL_HEAVY_HEAD] = 0;
-        ctl[CTL_HEAD_TRACE] = 0;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) interact_round_begin(ctl);
     const bdpt_ext_t& x = *a.st.ext;
     const size_t W2 = 2 * (size_t)a.st.cap;
     for (;;) {
-        const uint32_t qi = wave_grab(ctl + CTL_HEAD_INTERACT) + (threadIdx.x & 63);
-        if (qi - (threadIdx.x & 63) >= n) break;
+        const uint32_t base = wave_grab(ctl + CTL_HEAD_INTERACT);
+        if (base >= n) break;
+        const uint32_t qi = base + (threadIdx.x & 63);
         uint32_t cls = WCLS_END, w = 0;
         bool need_gather = false;
         if (qi < n) {
@@ -173,11 +153,10 @@ __global__ void __launch_bounds__(kBlock) k_classify(launch_args_t a, int in, in
             primary_hit_t ph;
             cls = bdpt_classify(a.sc, d, beam_ray, tr, tris, x.tri_class, ph);
             if (cls < kNumWalkClasses) {
-                uint32_t* tv = a.st.trav + (size_t)w * kTravWords;
-                tv[WT_TRAV_WORD(tuid)] = ph.tuid;
-                tv[WT_TRAV_WORD(bx)] = __float_as_uint(ph.bx);
-                tv[WT_TRAV_WORD(by)] = __float_as_uint(ph.by);
-                tv[WT_TRAV_WORD(pdist)] = __float_as_uint(ph.dist);
+                WT_TRAV_U(a, w, tuid) = ph.tuid;
+                WT_TRAV_U(a, w, bx) = __float_as_uint(ph.bx);
+                WT_TRAV_U(a, w, by) = __float_as_uint(ph.by);
+                WT_TRAV_U(a, w, pdist) = __float_as_uint(ph.dist);
             }
             // a region that did not fit the bounded list (or whose list holds more than kMaxEdgeIds / 3 triangles): its edge set comes from k_edges
             need_gather = cls == WCLS_NO_PRIMARY && !tr.ballistic && a.sc.opts.FSD && (tr.overflow > 0 || tr.ntris > kMaxEdgeIds / 3 || !(a.collect_list & 1u));
@@ -197,38 +176,28 @@ WT_D void interact_cls_body(const launch_args_t& a, int in) {
     bdpt_counters_t ctr;
     ctr.surface_interactions = ctr.vertices = 0;
     for (;;) {
-        const uint32_t qi = wave_grab(ctl + CTL_CLS_HEAD0 + cls) + (threadIdx.x & 63);
-        if (qi - (threadIdx.x & 63) >= n) break;
+        const uint32_t base = wave_grab(ctl + CTL_CLS_HEAD0 + cls);
+        if (base >= n) break;
+        const uint32_t qi = base + (threadIdx.x & 63);
         bool cont = false;
         uint32_t w = 0;
         if (qi < n) {
             w = queue[qi];
             uint32_t i, stream;
             walk_ident(a, w, i, stream);
-            const uint64_t j = a.j0 + i;
-            const uint32_t pix = (uint32_t)(j % a.npix);
-            const uint64_t s = a.sample_begin + j / a.npix;
-            const uint64_t sample_id = ((uint64_t)pix << 32) | (s & 0xFFFFFFFFull);
-            const uint32_t* tv = a.st.trav + (size_t)w * kTravWords;
-            const vec3 origin{__uint_as_float(tv[WT_TRAV_WORD(origin.x)]), __uint_as_float(tv[WT_TRAV_WORD(origin.y)]), __uint_as_float(tv[WT_TRAV_WORD(origin.z)])};
-            const float beam_dist = __uint_as_float(tv[WT_TRAV_WORD(dist)]);
-            const primary_hit_t ph{tv[WT_TRAV_WORD(tuid)], __uint_as_float(tv[WT_TRAV_WORD(pdist)]), __uint_as_float(tv[WT_TRAV_WORD(bx)]), __uint_as_float(tv[WT_TRAV_WORD(by)])};
+            const uint64_t sample_id = sample_id_of(a, i);
+            const vec3 origin = trav_origin(a, w);
+            const float beam_dist = WT_TRAV_F(a, w, dist);
+            const primary_hit_t ph{WT_TRAV_U(a, w, tuid), WT_TRAV_F(a, w, pdist), WT_TRAV_F(a, w, bx), WT_TRAV_F(a, w, by)};
             const walk_rec_t wr{a.st.walks + (size_t)w * a.st.walk_words};
-            const vertex_store_t vs{a.st.verts, a.st.vert_words, w};
+            const vertex_store_t vs = walk_vertices(a, w);
             cont = bdpt_surface_step<CLS>(a.sc, wr, origin, beam_dist, ph, vs, a.seed, sample_id, stream, &ctr);
         }
         queue_append(a, ctl, 1 - in, cont, w);
     }
     if (a.count_stats) {
-        unsigned long long vsi = ctr.surface_interactions, vv = ctr.vertices;
-        for (int off = 32; off > 0; off >>= 1) {
-            vsi += __shfl_down(vsi, off, 64);
-            vv += __shfl_down(vv, off, 64);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            if (vsi) atomicAdd(a.st.counters + offsetof(bdpt_counters_t, surface_interactions) / sizeof(unsigned long long), vsi);
-            if (vv) atomicAdd(a.st.counters + offsetof(bdpt_counters_t, vertices) / sizeof(unsigned long long), vv);
-        }
+        flush_counter(a, WT_COUNTER_SLOT(surface_interactions), ctr.surface_interactions);
+        flush_counter(a, WT_COUNTER_SLOT(vertices), ctr.vertices);
     }
 }
 #ifndef WTGPU_LB_CLS
@@ -274,32 +243,20 @@ __global__ void __launch_bounds__(64, 3) k_edges(launch_args_t a) {
     coop_set_dropped_counter(sh, a.st.counters + kDroppedSlot);
     uint32_t* ctl = a.st.ctl;
     const uint32_t n = ctl[CTL_GATHER_COUNT];
-    const size_t W2 = 2 * (size_t)a.st.cap;
-    const fsd_pool_t pool{a.st.fsd_hdr, a.st.fsd_edges, ctl + CTL_FSD_COUNTER, a.st.fsd_cap, ctl + CTL_FSD_ECOUNTER, a.st.fsd_ecap};
+    const fsd_pool_t pool = fsd_pool_of(a);
     for (;;) {
         const uint32_t item = wave_grab_item(ctl + CTL_GATHER_HEAD);
         if (item >= n) break;
         const uint32_t w = a.st.gather_queue[item];
         walk_t wk;
         soa_load(a.st.walks, a.st.walk_words, w, wk);   // uniform address: broadcast
-        const float beam_dist = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(dist)]);
-        const float region_depth = __uint_as_float(a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(region_depth)]);
+        const float beam_dist = WT_TRAV_F(a, w, dist), region_depth = WT_TRAV_F(a, w, region_depth);
         const range_t izr{beam_dist, beam_dist + region_depth};
         const cone_t tcone = walk_trace_envelope(a.sc, wk);
         const gather_out_t g = coop_gather(a.sc, tcone, izr, wk.beam.env, cone_frame(wk.beam.env), izr, vec2{1.f, 1.f}, false, sh, false, true, nullptr, 1, &eg);
         __syncthreads();
-        // sorted ids -> the round's edge pool: any number of them in bitmap mode, the sorted 96-entry list for scenes with more than 32768 classified
-        // edges.  (Until round 4 that list went into the walk's triangle-list slot, which a later pass may still read as triangles.)
-        const bool bitmap = a.sc.n_edges <= kCoopEdgeBits;
-        uint32_t n_edges = bitmap ? coop_edge_count(a.sc, eg) : g.n_edges, dropped = bitmap ? 0u : g.edge_overflow, off = 0;
-        off = wave_grab0(ctl + CTL_EPOOL_COUNT, n_edges);
-        if (off + n_edges > a.st.epool_cap) {   // pool exhausted (8M ids per round): reported, cannot happen in the shipped scenes
-            dropped += n_edges;
-            n_edges = 0;
-        } else if (bitmap)
-            coop_edge_write(a.sc, eg, a.st.epool + off, n_edges);
-        else
-            for (uint32_t j = threadIdx.x; j < n_edges; j += 64) a.st.epool[off + j] = eg.edge_ids[j];
+        uint32_t n_edges, dropped;
+        const uint32_t off = edges_to_pool(a, g, eg, n_edges, dropped);   // sorted ids -> the round's edge pool
         // Regions with many edges: the aperture is built right here, by the whole wavefront (wt/coop_fsd.h), instead of by one lane of
         // pass B; walks whose aperture has segments go straight to the pass-C queue.
         uint32_t marker = kGatherMarker, slot = 0;
@@ -317,19 +274,19 @@ __global__ void __launch_bounds__(64, 3) k_edges(launch_args_t a) {
                     pool.hdr[slot] = ap;
                     if (marker == kApertureMarker) a.st.intc_queue[atomicAdd(ctl + CTL_INTC_COUNT, 1u)] = w;
                     if (a.count_stats) {
-                        if (dropped) atomicAdd(a.st.counters + offsetof(bdpt_counters_t, edge_overflow) / sizeof(unsigned long long), (unsigned long long)dropped);
-                        if (ap.overflow) atomicAdd(a.st.counters + offsetof(bdpt_counters_t, fsd_edge_overflow) / sizeof(unsigned long long), (unsigned long long)ap.overflow);
-                        if (!ok) atomicAdd(a.st.counters + offsetof(bdpt_counters_t, fsd_pool_overflow) / sizeof(unsigned long long), 1ull);
+                        if (dropped) atomicAdd(a.st.counters + WT_COUNTER_SLOT(edge_overflow), (unsigned long long)dropped);
+                        if (ap.overflow) atomicAdd(a.st.counters + WT_COUNTER_SLOT(fsd_edge_overflow), (unsigned long long)ap.overflow);
+                        if (!ok) atomicAdd(a.st.counters + WT_COUNTER_SLOT(fsd_pool_overflow), 1ull);
                     }
                 }
             }
         }
         if (threadIdx.x == 0) {
-            a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(tuid)] = marker;
-            a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(by)] = slot;
-            a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(bx)] = off;
-            a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(n_ray_queries)] = n_edges;
-            a.st.trav[(size_t)w * kTravWords + WT_TRAV_WORD(n_cone_queries)] = dropped;
+            WT_TRAV_U(a, w, tuid) = marker;
+            WT_TRAV_U(a, w, by) = slot;
+            WT_TRAV_U(a, w, bx) = off;
+            WT_TRAV_U(a, w, n_ray_queries) = n_edges;
+            WT_TRAV_U(a, w, n_cone_queries) = dropped;
             if (a.profile) {
                 atomicAdd(a.st.counters + kNumCounters + 5, 1ull);
                 atomicAdd(a.st.counters + kNumCounters + 6, (unsigned long long)n_edges);

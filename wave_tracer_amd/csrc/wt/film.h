@@ -66,8 +66,10 @@ WT_HD rfilter_weights_t film_rfilter_weights(const sensor_t& s, vec2 o) {
     return w;
 }
 
-// film_t::splat + film_storage_t::write_block: primary image (value, weight)
-WT_HD void film_splat(const scene_t& sc, const film_t& film, const sensor_element_t& el, const stokes_t& sample, float k) {
+// film_t::splat: the per-channel values of a sample and its reconstruction-filter footprint on a width x height film; every element of the
+// footprint goes to sink(x, y, w, val, P) — w its filter weight, val[P] the sample's values, plane by plane
+template <class Sink>
+WT_HD void film_splat_footprint(const scene_t& sc, uint32_t width, uint32_t height, const sensor_element_t& el, const stokes_t& sample, float k, Sink&& sink) {
     const sensor_t& s = sc.sensor;
     const int r = s.rf_radius;
     const uint32_t S = film_stokes(s), P = s.channels * S;
@@ -87,16 +89,23 @@ WT_HD void film_splat(const scene_t& sc, const film_t& film, const sensor_elemen
     }
     for (int dy = -r; dy <= r; ++dy) {
         const int y = (int)el.y + dy;
-        if (y < 0 || y >= (int)film.height) continue;
+        if (y < 0 || y >= (int)height) continue;
         for (int dx = -r; dx <= r; ++dx) {
             const int x = (int)el.x + dx;
-            if (x < 0 || x >= (int)film.width) continue;
-            const float w = fmaxf_(0.f, rw.wx[dx + r] * rw.wy[dy + r]) * rw.recp_total;
-            const size_t pix = (size_t)y * film.width + x;
-            film_add(&film.weight[pix], (double)w);
-            for (uint32_t c = 0; c < P; ++c) film_add(&film.value[pix * P + c], (double)(w * val[c]));
+            if (x < 0 || x >= (int)width) continue;
+            sink(x, y, fmaxf_(0.f, rw.wx[dx + r] * rw.wy[dy + r]) * rw.recp_total, val, P);
         }
     }
+}
+// one element of a footprint into the film
+WT_HD void film_splat_add(const film_t& film, int x, int y, float w, const float* val, uint32_t P) {
+    const size_t pix = (size_t)y * film.width + x;
+    film_add(&film.weight[pix], (double)w);
+    for (uint32_t c = 0; c < P; ++c) film_add(&film.value[pix * P + c], (double)(w * val[c]));
+}
+// film_t::splat + film_storage_t::write_block: primary image (value, weight)
+WT_HD void film_splat(const scene_t& sc, const film_t& film, const sensor_element_t& el, const stokes_t& sample, float k) {
+    film_splat_footprint(sc, film.width, film.height, el, sample, k, [&](int x, int y, float w, const float* val, uint32_t P) { film_splat_add(film, x, y, w, val, P); });
 }
 // film_t::splat_direct + film_storage_t::write_light_splat: light image
 WT_HD void film_splat_direct(const scene_t& sc, const film_t& film, const sensor_element_t& el, const stokes_t& sample, float k) {

@@ -245,9 +245,13 @@ struct batch_launcher_t {
             }
             // (the tiled splat pays off when the batch holds most of the film's elements: it visits every row segment of the film)
             const uint32_t fw = a.film.width, fh = a.film.height, planes = film_planes(s->host.sensor);
-            if (K.tiled_splat && s->host.sensor.rf_radius <= 1 && planes <= 16 && (uint64_t)nb * 2u >= (uint64_t)a.npix)
-                HP_LAUNCH(k_connect_splat_tiled, dim3(fh * ((fw + kBlock - 1) / kBlock)), dim3(kBlock), 3 * kSplatCols * (planes + 1) * sizeof(double), st_, a);
-            else
+            if (K.tiled_splat && s->host.sensor.rf_radius <= 1 && planes <= 16 && (uint64_t)nb * 2u >= (uint64_t)a.npix) {
+                // one launch per (row % 3, segment % 2): the tiles that meet in a film element are added in a fixed order (kernels_connect.hip)
+                for (uint32_t phase = 0; phase < kSplatPhases; ++phase) {
+                    const uint32_t rows = splat_phase_rows(phase, fh), segs = splat_phase_segments(phase, splat_segments(fw));
+                    if (rows * segs) HP_LAUNCH(k_connect_splat_tiled, dim3(rows * segs), dim3(kSplatBlock), 3 * kSplatCols * (planes + 1) * sizeof(double), st_, a, phase);
+                }
+            } else
                 HP_LAUNCH(k_connect_splat, dim3((nb + kBlock - 1) / kBlock), dim3(kBlock), 0, st_, a);
         }
         HIP_CHECK(hipGetLastError());

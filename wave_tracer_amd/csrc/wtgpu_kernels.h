@@ -1,10 +1,13 @@
 // wave_tracer_amd — what the kernel translation units (kernels_*.hip) and the host side (wtgpu*.hip, wtgpu_host.h) share: the slice state, the launch block,
-// the device-side queue helpers and the kernels' declarations.  The kernels of one batch, in launch order:
-//   kernels_walk.hip    k_generate, k_interact (pass A, by material class), k_edges, k_interact_b (pass B)
-//   kernels_trace.hip   k_trace_refill, k_trace_heavy (+ the per-query kernels of the traversal parity tests, the PMC calibration copy)
+// the device-side queue helpers, the work-item vocabulary of the render kernels (queue item -> sample id, pool, vertex stores, bucket, counters,
+// traversal-record words) and the kernels' declarations.  The kernels of one batch, in launch order:
+//   kernels_walk.hip    k_generate, k_interact (pass A; k_interact_coop: with cooperative record I/O; k_classify + k_interact_sorted / _diffuse /
+//                       _dielectric / _spm / _any: by material class), k_edges, k_interact_b (pass B), k_light_rounds (a batch's thin last rounds)
+//   kernels_trace.hip   k_trace_refill (body: kernels_trace_refill.h, which k_light_rounds runs too), the staged k_tr_axis / _cone / _policy / _tail,
+//                       k_trace_heavy (+ the per-query kernels of the traversal parity tests, the PMC calibration copy)
 //   kernels_fsd.hip     k_flux_split, k_flux_tasks, k_interact_c, k_interact_c_hard (Fraunhofer interactions: power sums, rejection sampling)
-//   kernels_path.hip    k_path_* (plt_path)
-//   kernels_connect.hip k_connect_* (class / strategy buckets, connections, MIS, film splat)
+//   kernels_path.hip    k_path_generate, _fsd, _interact, _edges, _interact_b, _nee, _flush (plt_path)
+//   kernels_connect.hip k_connect_enum, _scan, _class / _strat (+ _open), the staged _eval / _shadow / _mis, _splat / _splat_tiled
 //   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
 //   kernels_mask.hip    k_sensor_mask_wave / k_sensor_mask_lane: by-geometry sensor masks (not part of a render)
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
@@ -301,6 +304,100 @@ WT_D void queue_append(const launch_args_t& a, uint32_t* ctl, int out, bool pred
     if (back) a.st.queue[out][2 * (size_t)a.st.cap - 1 - (base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)))] = w;
 }
 
+// ---- the work-item vocabulary of the walk, path and connection kernels ------------------------------------------------------------------------
+// What every kernel form does with a queue item before its own logic starts, written once: straight-line code, called from INSIDE the persistent
+// loops (the `for (;;)`, the grab and the `break` stay written out in each kernel, see wave_grab0).
+// sample i of the batch -> the id its random streams are keyed by; `pix`: its sensor element
+WT_D uint64_t sample_id_of(const launch_args_t& a, uint32_t i, uint32_t& pix) {
+    const uint64_t j = a.j0 + i;
+    pix = (uint32_t)(j % a.npix);
+    const uint64_t smp = a.sample_begin + j / a.npix;
+    return ((uint64_t)pix << 32) | (smp & 0xFFFFFFFFull);
+}
+WT_D uint64_t sample_id_of(const launch_args_t& a, uint32_t i) {
+    uint32_t pix;
+    return sample_id_of(a, i, pix);
+}
+WT_D fsd_pool_t fsd_pool_of(const launch_args_t& a) {
+    return fsd_pool_t{a.st.fsd_hdr, a.st.fsd_edges, a.st.ctl + CTL_FSD_COUNTER, a.st.fsd_cap, a.st.ctl + CTL_FSD_ECOUNTER, a.st.fsd_ecap};
+}
+// the vertex array of walk w; of sample i's sensor / emitter subpath
+WT_D vertex_store_t walk_vertices(const launch_args_t& a, size_t w) { return vertex_store_t{a.st.verts, a.st.vert_words, w}; }
+WT_D vertex_store_t sensor_vertices(const launch_args_t& a, uint32_t i) { return walk_vertices(a, i); }
+WT_D vertex_store_t emitter_vertices(const launch_args_t& a, uint32_t i) { return walk_vertices(a, (size_t)a.st.cap + i); }
+// Item idx of a flattened bucket space -> its bucket: the LAST key of [0, n) whose prefix is <= idx (prefix[0] = 0; empty buckets share their
+// successor's prefix and are never the last).  Class form: the table is by rank and every class starts at a multiple of 64, so the 64 items of
+// a grab have the bucket of the first.  (always_inline: left to itself the compiler made it a CALL in k_connect_strat, the table a flat pointer.)
+__host__ __device__ constexpr __attribute__((always_inline)) uint32_t bucket_of(const uint32_t* prefix, uint32_t idx, uint32_t n = kNumKeys) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (prefix[mid] <= idx)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+namespace bucket_of_check {
+constexpr uint32_t front[] = {0, 0, 0, 3, 5};          // keys 0, 1 empty; 2: [0,3); 3: [3,5)
+constexpr uint32_t middle[] = {0, 2, 2, 2, 5};         // 0: [0,2); 1, 2 empty; 3: [2,5)
+constexpr uint32_t back[] = {0, 3, 5, 5, 5};           // 0: [0,3); 1: [3,5); 2, 3 empty
+constexpr uint32_t ranks[] = {0, 64, 64, 192, 256};    // class form: 64 items, none, 128, 64
+static_assert(bucket_of(front, 0, 4) == 2 && bucket_of(front, 2, 4) == 2 && bucket_of(front, 3, 4) == 3 && bucket_of(front, 4, 4) == 3, "empty buckets at the front");
+static_assert(bucket_of(middle, 0, 4) == 0 && bucket_of(middle, 1, 4) == 0 && bucket_of(middle, 2, 4) == 3 && bucket_of(middle, 4, 4) == 3, "empty buckets in the middle");
+static_assert(bucket_of(back, 0, 4) == 0 && bucket_of(back, 2, 4) == 0 && bucket_of(back, 3, 4) == 1 && bucket_of(back, 4, 4) == 1, "empty buckets at the end");
+static_assert(bucket_of(ranks, 0, 4) == 0 && bucket_of(ranks, 64, 4) == 2 && bucket_of(ranks, 128, 4) == 2 && bucket_of(ranks, 192, 4) == 3, "classes start at multiples of 64");
+static_assert(bucket_of(front, 0, 1) == 0, "one key");
+}   // namespace bucket_of_check
+// index of a counter in st.counters; one counter summed over the wavefront, added by lane 0.  (Kernels that touch two or three counters zero and
+// flush those alone: flush_counters over all of them costs registers.)
+#define WT_COUNTER_SLOT(field) (offsetof(bdpt_counters_t, field) / sizeof(unsigned long long))
+WT_D void flush_counter(const launch_args_t& a, size_t slot, unsigned long long v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(a.st.counters + slot, v);
+}
+// one word of walk w's traversal record, as it is / as a float (macros: `field` is a member of trav_result_t, not an expression; WT_TRAV_U is an
+// lvalue: `WT_TRAV_U(a, w, tuid) = marker`)
+WT_D uint32_t& trav_word(const launch_args_t& a, uint32_t w, size_t word) { return a.st.trav[(size_t)w * kTravWords + word]; }
+#define WT_TRAV_U(a, w, field) trav_word(a, w, WT_TRAV_WORD(field))
+#define WT_TRAV_F(a, w, field) __uint_as_float(WT_TRAV_U(a, w, field))
+WT_D vec3 trav_origin(const launch_args_t& a, uint32_t w) { return vec3{WT_TRAV_F(a, w, origin.x), WT_TRAV_F(a, w, origin.y), WT_TRAV_F(a, w, origin.z)}; }
+// The classified-edge ids coop_gather left behind (g, eg) -> a block of the round's edge pool, sorted: any number of them in bitmap mode, the sorted
+// 96-entry list for scenes with more than kCoopEdgeBits classified edges.  (Until round 4 that list went into the walk's triangle-list slot, which a
+// later pass may still read as triangles.)  Returns the block's offset; n_edges: ids written, dropped: ids lost.  One wavefront, all lanes.
+WT_D uint32_t edges_to_pool(const launch_args_t& a, const gather_out_t& g, coop_edges_t& eg, uint32_t& n_edges, uint32_t& dropped) {
+    const bool bitmap = a.sc.n_edges <= kCoopEdgeBits;
+    n_edges = bitmap ? coop_edge_count(a.sc, eg) : g.n_edges;
+    dropped = bitmap ? 0u : g.edge_overflow;
+    const uint32_t off = wave_grab0(a.st.ctl + CTL_EPOOL_COUNT, n_edges);
+    if (off + n_edges > a.st.epool_cap) {   // pool exhausted (8M ids per round): reported, cannot happen in the shipped scenes
+        dropped += n_edges;
+        n_edges = 0;
+    } else if (bitmap)
+        coop_edge_write(a.sc, eg, a.st.epool + off, n_edges);
+    else
+        for (uint32_t j = threadIdx.x; j < n_edges; j += 64) a.st.epool[off + j] = eg.edge_ids[j];
+    return off;
+}
+// a batch begins: every queue empty, every head and bump allocator at 0 (the generate kernels then set CTL_COUNT0, the first round's queue)
+WT_D void ctl_reset_batch(uint32_t* ctl) {
+    ctl[CTL_COUNT1] = 0;
+    ctl[CTL_BACK0] = ctl[CTL_BACK1] = 0;
+    ctl[CTL_UTD_COUNT0] = ctl[CTL_UTD_COUNT1] = ctl[CTL_FSDQ_COUNT0] = ctl[CTL_FSDQ_COUNT1] = ctl[CTL_FSDQ_HEAD] = ctl[CTL_NEEQ_COUNT] = ctl[CTL_NEEQ_HEAD] = 0;   // plt_path's
+    ctl[CTL_HEAD_TRACE] = ctl[CTL_HEAD_INTERACT] = ctl[CTL_HEAVY_COUNT] = ctl[CTL_HEAVY_HEAD] = ctl[CTL_FSD_COUNTER] = ctl[CTL_ROUNDS] = 0;
+    ctl[CTL_TPOL_COUNT0] = ctl[CTL_TPOL_COUNT1] = ctl[CTL_TPOL_HEAD] = ctl[CTL_TCONE_COUNT0] = ctl[CTL_TCONE_COUNT1] = ctl[CTL_TCONE_HEAD] = 0;   // the staged trace kernels' queues
+    ctl[CTL_INTB_COUNT] = ctl[CTL_INTB_HEAD] = ctl[CTL_GATHER_COUNT] = ctl[CTL_GATHER_HEAD] = ctl[CTL_INTC_COUNT] = ctl[CTL_INTC_HEAD] = 0;
+    ctl[CTL_FTASK_COUNT] = ctl[CTL_FTASK_HEAD] = ctl[CTL_FSPLIT_HEAD] = ctl[CTL_EPOOL_COUNT] = ctl[CTL_FSD_ECOUNTER] = 0;
+    ctl[CTL_INTD_COUNT] = ctl[CTL_INTD_HEAD] = 0;
+}
+// pass A of a round begins (one lane of the grid): the trace queues are ready for the NEXT round's k_trace
+WT_D void interact_round_begin(uint32_t* ctl) {
+    ctl[CTL_HEAVY_COUNT] = 0;
+    ctl[CTL_HEAVY_HEAD] = 0;
+    ctl[CTL_HEAD_TRACE] = 0;
+}
+
 // ---- wave-cooperative record transfer -------------------------------------------------------------------------------------------------------
 // The per-walk records are record-major in memory (one contiguous record per walk) and the walks a wavefront holds are scattered over the batch.
 // A lane that loads its own record word by word makes every load INSTRUCTION touch 64 different cache lines for 4 bytes each (57 instructions x
@@ -371,7 +468,36 @@ WT_D void wave_store_records(uint32_t* base, size_t stride, uint32_t idx, uint32
 // ---- kernels (definitions: kernels_*.hip)
 constexpr uint32_t kFlushGrid = 64;          // k_path_flush
 constexpr int kEnumBlock = 1024;             // k_connect_enum
-constexpr uint32_t kSplatCols = kBlock + 2;  // k_connect_splat_tiled: columns of its LDS tile
+constexpr uint32_t kSplatBlock = 64, kSplatCols = kSplatBlock + 2;  // k_connect_splat_tiled: elements of a row segment (one wavefront), columns of its LDS tile
+// ... and the launches its blocks are spread over: phase = 2 x (row % 3) + (segment % 2).  A block's tile reaches one row up and down and one
+// column left and right, so two blocks of one phase — at least three rows or two segments apart — never touch the same film element, and the up to
+// six tiles that meet in an element are added in the order of the phases.  Grid of a phase: splat_phase_rows x splat_phase_segments blocks.
+constexpr uint32_t kSplatPhases = 6;
+__host__ __device__ constexpr uint32_t splat_segments(uint32_t width) { return (width + kSplatBlock - 1) / kSplatBlock; }
+__host__ __device__ constexpr uint32_t splat_phase_rows(uint32_t phase, uint32_t height) { return (height + 2u - phase / 2u) / 3u; }        // rows phase / 2, + 3, ... below height
+__host__ __device__ constexpr uint32_t splat_phase_segments(uint32_t phase, uint32_t segs) { return (segs + 1u - (phase & 1u)) / 2u; }    // segments phase % 2, + 2, ... below segs
+__host__ __device__ constexpr uint32_t splat_block_row(uint32_t phase, uint32_t block, uint32_t phase_segs) { return phase / 2u + 3u * (block / phase_segs); }
+__host__ __device__ constexpr uint32_t splat_block_segment(uint32_t phase, uint32_t block, uint32_t phase_segs) { return (phase & 1u) + 2u * (block % phase_segs); }
+// every (row, segment) of a height x segs film belongs to exactly one block of exactly one phase, and no grid reaches outside the film
+__host__ __device__ constexpr bool splat_phases_cover(uint32_t height, uint32_t segs) {
+    uint32_t seen[8 * 8] = {};
+    for (uint32_t phase = 0; phase < kSplatPhases; ++phase) {
+        const uint32_t ps = splat_phase_segments(phase, segs), n = splat_phase_rows(phase, height) * ps;
+        for (uint32_t b = 0; b < n; ++b) {
+            const uint32_t r = splat_block_row(phase, b, ps), s = splat_block_segment(phase, b, ps);
+            if (r >= height || s >= segs || r % 3u != phase / 2u || s % 2u != (phase & 1u)) return false;
+            ++seen[r * 8 + s];
+        }
+    }
+    for (uint32_t r = 0; r < height; ++r)
+        for (uint32_t s = 0; s < segs; ++s)
+            if (seen[r * 8 + s] != 1) return false;
+    return true;
+}
+static_assert(splat_phases_cover(1, 1) && splat_phases_cover(2, 1) && splat_phases_cover(3, 2) && splat_phases_cover(4, 2) && splat_phases_cover(5, 3) && splat_phases_cover(6, 4) &&
+              splat_phases_cover(7, 5) && splat_phases_cover(8, 8) && splat_phases_cover(7, 1) && splat_phases_cover(1, 6),
+              "heights 0, 1, 2 mod 3; even and odd segment counts");
+static_assert(splat_segments(1) == 1 && splat_segments(64) == 1 && splat_segments(65) == 2 && splat_segments(1440) == 23 && splat_segments(1920) == 30, "segments of a row");
 #ifndef WTGPU_HARD_BLOCK
 #define WTGPU_HARD_BLOCK 256
 #endif
@@ -416,7 +542,7 @@ __global__ void k_connect_eval(launch_args_t a, uint32_t chunk);
 __global__ void k_connect_shadow(launch_args_t a, uint32_t chunk);
 __global__ void k_connect_mis(launch_args_t a, uint32_t chunk);
 __global__ void k_connect_splat(launch_args_t a);
-__global__ void k_connect_splat_tiled(launch_args_t a);
+__global__ void k_connect_splat_tiled(launch_args_t a, uint32_t phase);
 __global__ void k_calib_copy(const uint32_t* in, uint32_t* out, size_t n);
 __global__ void k_trace_rays(scene_t sc, const float* rays, uint32_t n, float* dist, uint32_t* tuid, float* bary, uint32_t* front);
 __global__ void k_traverse_cones(scene_t sc, const float* cones, uint32_t n, uint32_t cap, float* dist, uint32_t* flags, uint32_t* ntris, uint32_t* out_tris,
