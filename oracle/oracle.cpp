@@ -29,6 +29,7 @@
 #include "../wave_tracer_amd/csrc/wt/path.h"
 #include "../wave_tracer_amd/csrc/wt/diffraction_probe.h"
 #include "../wave_tracer_amd/csrc/wt/bsdf_probe.h"
+#include "../wave_tracer_amd/csrc/wt/flux_probe.h"
 #include "../wave_tracer_amd/csrc/wt/sources_probe.h"
 
 using namespace wt;
@@ -706,6 +707,37 @@ int oracle_query_regions(const void* scene_host, const float* cones, uint32_t n,
     return 0;
 }
 
+// The triangle ids of the unbounded record of oracle_query_regions (`list`, after the final-slab filter) with the region they were summed over, for
+// the f64 restatement of the sum (oracle/flux64.cpp: ref_region_sum).  ids: n x cap (kInvalid padded; a region of more than cap triangles keeps
+// its count and the first cap ids); rec: n x 16 floats = envelope o, d, x, tan_alpha, x0; izr min, max; sigma; front_face (0 / 1).  A ballistic or
+// empty query has no triangles.
+int oracle_region_triangles(const void* scene_host, const float* cones, uint32_t n, uint32_t cap, uint32_t* out_ntris, uint32_t* out_ids, float* out_rec) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    stack_entry_t st[kOracleStack];
+    const stack_ref_t stack = make_flat_stack(st, kOracleStack);
+    std::vector<uint32_t> tl(1u << 21);
+    std::vector<float> dl(1u << 21);
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* c = cones + 10 * (size_t)i;
+        const vec3 d = normalize(vec3{c[3], c[4], c[5]});
+        const cone_t env = make_cone(vec3{c[0], c[1], c[2]}, d, build_orthogonal_frame(d).t, c[6], c[8], c[7]);
+        const uint_list_t tris{tl.data(), 1, (uint32_t)tl.size(), g_region_filter ? dl.data() : nullptr};
+        const trav_result_t tr = traverse(sc, env, c[9], WT_INF, false, stack, tris);
+        out_ntris[i] = 0;
+        for (uint32_t j = 0; j < cap; ++j) out_ids[(size_t)i * cap + j] = kInvalid;
+        float* r = out_rec + 16 * (size_t)i;
+        for (int j = 0; j < 16; ++j) r[j] = 0.f;
+        if (tr.ballistic || tr.empty) continue;
+        const vec2 ax = cone_axes(env, tr.dist);
+        const float rec[16] = {env.o.x, env.o.y, env.o.z, env.d.x, env.d.y, env.d.z, env.x.x, env.x.y, env.x.z, env.tan_alpha, env.x0,
+                               tr.dist, tr.dist + tr.region_depth, ax.x / kBeamEnvelope, ax.y / kBeamEnvelope, tr.front_face ? 1.f : 0.f};
+        memcpy(r, rec, sizeof(rec));
+        out_ntris[i] = tr.ntris;
+        for (uint32_t j = 0; j < tr.ntris && j < cap; ++j) out_ids[(size_t)i * cap + j] = tl[j];
+    }
+    return 0;
+}
+
 // The sequential Fraunhofer aperture per query (wt/diffraction_probe.h: probe_fsd_sequential, the semantics of bdpt_walk_step) with the
 // layouts of wtgpu_test_fsd_apertures: hdr n x kFsdProbeWords words, segs n x pool_cap segment records (each query its own pool).
 int oracle_fsd_apertures(const void* scene_host, const float* cones, const float* sk, const uint32_t* ids, const uint32_t* n_ids, uint32_t n, uint32_t id_cap,
@@ -781,6 +813,15 @@ int oracle_source_queries(const void* scene_host, const uint32_t* queries, uint3
     for (uint32_t q = 0; q < n; ++q)
         if (!source_probe_query_ok(sc, queries + (size_t)q * kSourceProbeQueryWords)) return 1;
     for (uint32_t q = 0; q < n; ++q) probe_source(sc, queries + (size_t)q * kSourceProbeQueryWords, out + (size_t)q * kSourceProbeWords);
+    return 0;
+}
+// The region power integral per query (wt/flux_probe.h: probe_flux) with the layouts of wtgpu_test_flux_queries: n x kFluxProbeQueryWords query
+// words, n x kFluxProbeWords output words.  1: an op or tuid out of range (nothing is run).
+int oracle_flux_queries(const void* scene_host, const uint32_t* queries, uint32_t n, uint32_t* out) {
+    const scene_t& sc = *static_cast<const scene_t*>(scene_host);
+    for (uint32_t q = 0; q < n; ++q)
+        if (!flux_probe_query_ok(sc, queries + (size_t)q * kFluxProbeQueryWords)) return 1;
+    for (uint32_t q = 0; q < n; ++q) probe_flux(sc, queries + (size_t)q * kFluxProbeQueryWords, out + (size_t)q * kFluxProbeWords);
     return 0;
 }
 // The baked records the f64 restatement of the source layer reads (tests/sources_probe.py): an emitter (emitter_t, sizeof bytes), the sensor

@@ -177,6 +177,7 @@ def load_library():
     lib.wtgpu_test_profile_counters.argtypes = [vp, vp, u32]
     lib.wtgpu_test_bsdf_queries.argtypes = [vp, vp, vp, u32, i32, vp]
     lib.wtgpu_test_source_queries.argtypes = [vp, vp, vp, u32, vp]
+    lib.wtgpu_test_flux_queries.argtypes = [vp, vp, vp, u32, vp]
     lib.wtgpu_scene_shape_id.argtypes = [vp, u32, C.POINTER(C.c_char_p)]
     lib.wtgpu_scene_sensor_mask_spec.argtypes = [vp, C.POINTER(SensorMaskSpec)]
     lib.wtgpu_sensor_mask.argtypes = [vp, vp, vp, u32, u64, vp]
@@ -487,6 +488,21 @@ class Scene:
         d_q = torch.from_numpy(q.view(np.int32)).to(dev)
         out = torch.zeros((n, 80), dtype=torch.int32, device=dev)
         _check(load_library().wtgpu_test_source_queries(self._h, None, d_q.data_ptr(), n, out.data_ptr()))
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy().view(np.uint32)
+
+    def flux_queries(self, queries):
+        """Test hook (wtgpu_test_hooks.h): the region power integral per query.  queries [n,20] u32 (wt/flux_probe.h) -> out [n,36] u32 (f32 bits
+        except the discrete words).  An op or tuid out of range raises (WTGPU_ERR_INVALID)."""
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.device)
+        q = np.ascontiguousarray(queries, dtype=np.uint32)
+        n = q.shape[0]
+        assert q.shape == (n, 20)
+        d_q = torch.from_numpy(q.view(np.int32)).to(dev)
+        out = torch.zeros((n, 36), dtype=torch.int32, device=dev)
+        _check(load_library().wtgpu_test_flux_queries(self._h, None, d_q.data_ptr(), n, out.data_ptr()))
         torch.cuda.synchronize(dev)
         return out.cpu().numpy().view(np.uint32)
 

@@ -1,9 +1,10 @@
 // wave_tracer_amd — test entry points of the wave-cooperative diffraction kernels (wtgpu_test_hooks.h; see wtgpu_kernels.h for the list of kernel
 // translation units).  Each runs the cooperative form and the sequential form it replaces on the same explicit queries (wt/diffraction_probe.h:
 // layouts), one query at a time; the material layer's queries run in the generic or the class form (wt/bsdf_probe.h); the emitter / sensor /
-// wavenumber layer's one op per query (wt/sources_probe.h).  No render kernel is compiled here.
+// wavenumber layer's one op per query (wt/sources_probe.h), the region power integral's likewise (wt/flux_probe.h).  No render kernel is compiled here.
 #include "wt/bsdf_probe.h"
 #include "wt/diffraction_probe.h"
+#include "wt/flux_probe.h"
 #include "wt/sources_probe.h"
 #include "wtgpu_kernels.h"
 
@@ -94,6 +95,13 @@ __global__ void __launch_bounds__(64) k_test_sources(scene_t sc, const uint32_t*
     probe_source(sc, queries + (size_t)q * kSourceProbeQueryWords, out + (size_t)q * kSourceProbeWords);
 }
 
+// One lane per query of the region power integral (wt/flux_probe.h).
+__global__ void __launch_bounds__(64) k_test_flux(scene_t sc, const uint32_t* queries, uint32_t n, uint32_t* out) {
+    const uint32_t q = blockIdx.x * 64 + threadIdx.x;
+    if (q >= n) return;
+    probe_flux(sc, queries + (size_t)q * kFluxProbeQueryWords, out + (size_t)q * kFluxProbeWords);
+}
+
 int test_fsd_apertures(const scene_t& sc, hipStream_t stream, const float* d_cones, const float* d_sk, const uint32_t* d_ids, const uint32_t* d_n_ids,
                        uint32_t n, uint32_t id_cap, uint32_t pool_cap, uint32_t mode, uint32_t* d_hdr, float* d_segs) {
     if (n == 0) return 0;
@@ -128,6 +136,12 @@ int test_bsdf_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_q
 int test_source_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_queries, uint32_t n, uint32_t* d_out) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_test_sources, dim3((n + 63) / 64), dim3(64), 0, stream, sc, d_queries, n, d_out);
+    return (int)hipGetLastError();
+}
+
+int test_flux_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_queries, uint32_t n, uint32_t* d_out) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_test_flux, dim3((n + 63) / 64), dim3(64), 0, stream, sc, d_queries, n, d_out);
     return (int)hipGetLastError();
 }
 

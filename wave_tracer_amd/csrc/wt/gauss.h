@@ -10,8 +10,10 @@
 //      I = (1/2pi) * Sum_edges  Int_{phi_p}^{phi_q} ( 1 - exp(-h^2 / (2 cos^2 phi)) ) dphi ,
 // (h = distance of the edge's line from the origin, phi measured from the line's normal) with 8-point Gauss-Legendre rules: one in phi
 // on |phi| <= pi/4, and — round 5 — log-graded pieces in u = ln(h tan phi) beyond, where the integrand has a boundary layer of width ~h
-// (gauss_edge_side).  Deterministic; agrees with a double-precision quadrature of the same integral to 4e-6 over random triangles of every
-// scale, edges through the beam axis included (tests/test_kat.py::test_gaussian_triangle_integral; round 4's rule: 1.2e-3 on such edges).
+// (gauss_edge_side).  Deterministic.  Measured against an adaptive double-precision quadrature (oracle/flux64.cpp; tests/test_flux_probe.py on
+// the host, tests/test_gpu_flux.py on the device, worst absolute errors in tests/golden/flux_measured.json): 4.0e-7 on the host and 4.1e-7 on
+// the device over 12,800 random triangles of scales 0.01 .. 8 sigma centred 0 .. 5 sigma off the axis, 5.8e-8 on edges through or 1e-4 .. 0.1
+// sigma from the beam axis (round 4's rule: 1.2e-3 on such edges), 2.0e-6 over 1,600 triangles of scale 50 sigma.
 #pragma once
 #include "core.h"
 

@@ -556,6 +556,7 @@ int test_utd_sums(const scene_t& sc, hipStream_t stream, const float* d_queries,
                   uint32_t utd_cap, uint32_t* d_recs, uint32_t* d_hdr, uint32_t* d_edges);
 int test_bsdf_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_queries, uint32_t n, int form, uint32_t* d_out);
 int test_source_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_queries, uint32_t n, uint32_t* d_out);
+int test_flux_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_queries, uint32_t n, uint32_t* d_out);
 // kernels_mask.hip: by-geometry sensor masks (wtgpu_sensor_mask / wtgpu_sensor_mask_host).  shape_matches: one byte per shape, 1 = the id matches
 // the mask's regex.  The launch returns a hipError_t.
 int sensor_mask_launch(const scene_t& sc, hipStream_t stream, const uint8_t* d_shape_matches, uint32_t samples, uint64_t seed, float* d_out);

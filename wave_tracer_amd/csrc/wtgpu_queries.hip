@@ -1,6 +1,7 @@
 // wave_tracer_amd — entry points that are neither a render nor read a film (wtgpu_film.hip): ray / cone / region queries, by-geometry sensor
 // masks, the probes of the kernel tests (wtgpu_test_hooks.h), the PMC calibration copy.
 #include "wtgpu_host.h"
+#include "wt/flux_probe.h"
 #include "wt/sources_probe.h"
 
 extern "C" {
@@ -137,6 +138,22 @@ int wtgpu_test_source_queries(wtgpu_scene* s, void* stream_, const uint32_t* d_q
         if (!source_probe_query_ok(s->host, q.data() + (size_t)i * kSourceProbeQueryWords))
             return fail(WTGPU_ERR_INVALID, "wtgpu_test_source_queries: query " + std::to_string(i) + ": op, emitter index or tuid out of range");
     HIP_CHECK((hipError_t)test_source_queries(s->dev, stream, d_queries, n, d_out));
+    return WTGPU_OK;
+}
+
+int wtgpu_test_flux_queries(wtgpu_scene* s, void* stream_, const uint32_t* d_queries, uint32_t n, uint32_t* d_out) {
+    if (!s || !s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    if (n == 0) return WTGPU_OK;
+    if (!d_queries || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    device_guard_t guard(s->device);
+    std::vector<uint32_t> q((size_t)n * kFluxProbeQueryWords);
+    HIP_CHECK(hipMemcpyAsync(q.data(), d_queries, q.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (uint32_t i = 0; i < n; ++i)
+        if (!flux_probe_query_ok(s->host, q.data() + (size_t)i * kFluxProbeQueryWords))
+            return fail(WTGPU_ERR_INVALID, "wtgpu_test_flux_queries: query " + std::to_string(i) + ": op or tuid out of range");
+    HIP_CHECK((hipError_t)test_flux_queries(s->dev, stream, d_queries, n, d_out));
     return WTGPU_OK;
 }
 

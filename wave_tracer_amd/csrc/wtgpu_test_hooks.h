@@ -43,6 +43,11 @@ int wtgpu_test_bsdf_queries(wtgpu_scene* s, void* stream, const uint32_t* d_quer
  * outside the table, an emitter index >= the scene's count or a tuid >= its triangle count returns WTGPU_ERR_INVALID and launches nothing.
  * The CPU checker's counterpart: oracle/oracle.cpp: oracle_source_queries. */
 int wtgpu_test_source_queries(wtgpu_scene* s, void* stream, const uint32_t* d_queries, uint32_t n, uint32_t* d_out);
+/* Per-query entry point of the region power integral (kernels_test.hip: k_test_flux; layouts: wt/flux_probe.h): n queries of 20 words, n x 36
+ * output words, device pointers.  The queries are read back and checked first (this call waits for `stream`): an op outside the table or a
+ * tuid >= the scene's triangle count returns WTGPU_ERR_INVALID and launches nothing.  The CPU checker's counterpart: oracle/oracle.cpp:
+ * oracle_flux_queries. */
+int wtgpu_test_flux_queries(wtgpu_scene* s, void* stream, const uint32_t* d_queries, uint32_t n, uint32_t* d_out);
 /* The class form of the connections (k_connect_class, WTGPU_CONNECT_CLASS=1).  N = n_keys = key_dim x key_dim length classes, key = tk * key_dim + sk
  * (the capped subpath lengths of a class).
  * wtgpu_test_connect_class_order: N and key_dim; with cap >= N also the keys in the order the kernel's wavefronts take the classes, descending
