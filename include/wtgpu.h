@@ -351,6 +351,52 @@ int wtgpu_film_compare_host(const wtgpu_scene* scene, const double* a_value, con
                             const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec,
                             const float* mask, uint32_t n_threads, wtgpu_film_compare* out, float* diff);
 
+/* Polarisation view of a polarimetric film (stokes == 4): degrees and angles of polarisation, the film through an analyser, Stokes sums and the
+ * false-colour polarisation picture, all derived from the four developed components together without the film leaving the device.
+ *   planes   the film's channels (plane c: the Stokes vector (I, Q, U, V) of the developed values of film planes c * 4 + s, bit for bit
+ *            wtgpu_develop's, widened to f64), plus one with flag 2 LUMINANCE (3-channel films only): the vector .2126 S_r + .7152 S_g + .0722 S_b,
+ *            component by component in f64, added left to right and NOT clamped at 0 (linear in S, unlike the tonemap's luminance).
+ *   values   lin = sqrt(Q Q + U U), pol = sqrt((Q Q + U U) + V V), dolp = lin / I, dop = pol / I, docp = V / I, analyser = (I + Q c2 + U s2) / 2 with
+ *            c2 = cos 2 theta, s2 = sin 2 theta of the analyser's angle, aolp = atan2(U, Q) / 2 in (-pi/2, pi/2] and chi = atan2(V, lin) / 2, in f64 with
+ *            + - x / and sqrt only; the arc tangent is the library's own polynomial (absolute error below 1.2e-11 rad; a zero of either sign counts as
+ *            +0, aolp = 0 where lin == 0), so that device and host agree on every value bit for bit.  Each is rounded to f32 once.
+ *   members  all pixels, or with a mask ([height][width] f32) those where mask > 0.
+ *   classes  a member is, per plane, non-finite (any of I, Q, U, V is NaN or infinite: counted in n_nonfinite, every map value the quiet NaN
+ *            0x7fc00000), dark (finite and not I > 0: counted in n_dark; dolp, dop, docp, aolp, chi are 0, analyser is computed) or lit; only lit
+ *            pixels enter the sums and the maximum, and a lit pixel is counted in n_over iff (Q Q + U U) + V V > I I (more polarised than bright: noise).
+ *   record   n members and the three counts; max_dop = max dop over the lit pixels and argmax, the row-major index of the pixel that has it, the
+ *            lowest on a tie — 0 and UINT64_MAX where no pixel is lit; six f64 sums over the lit pixels, of I, Q, U, V, lin and pol, each in the
+ *            fixed order of the film statistics' sum, so device and host agree on every field bit for bit.
+ *   maps     optional: [height][width][planes][k] f32, the k maps chosen by the bits of `maps` in the order 1 DOLP, 2 DOP, 4 DOCP, 8 AOLP, 16 CHI,
+ *            32 ANALYSER; 0 for a pixel the mask excludes.
+ *   picture  optional: the false-colour view of plane `picture_plane`, [height][width][3] — [height][width][4] with the mask as the fourth
+ *            component, as wtgpu_tonemap_device appends it — in `format` (0 f32, 1 8-bit, 2 16-bit codes; NaN = code 0): hue = aolp / pi + 1/2,
+ *            saturation = clamp01(dolp x sat_gain), value = clamp01(op(I)) with the operator, gamma and dB range of `tonemap` (its mode and table are
+ *            not used), HSV -> RGB by the sextant formula in f32; hue and saturation are 0 for a pixel that is not lit.  Every pixel is shown.
+ * Errors (WTGPU_ERR_INVALID with a message): a film that is not polarimetric, LUMINANCE on a film that is not 3-channel, unknown flag or map bits,
+ * c2, s2 or sat_gain that is not finite, sat_gain < 0, picture_plane >= planes, an unknown format or operator (the `function` operator is refused as
+ * the tonemap calls refuse it).  A zeroed spec is valid: no luminance, no maps, a linear picture of plane 0 without saturation. */
+typedef struct wtgpu_film_polar_spec {
+    uint32_t flags /* 2 LUMINANCE */, maps /* 1 DOLP, 2 DOP, 4 DOCP, 8 AOLP, 16 CHI, 32 ANALYSER */, picture_plane, format /* 0 f32, 1 u8, 2 u16 */;
+    double c2, s2;
+    float sat_gain, pad;
+    wtgpu_tonemap tonemap;
+} wtgpu_film_polar_spec;
+typedef struct wtgpu_film_polar {
+    uint64_t n, n_nonfinite, n_dark, n_over, argmax;
+    double max_dop, sum_i, sum_q, sum_u, sum_v, sum_lin, sum_pol;
+} wtgpu_film_polar;
+/* On the device, on `stream`: one pass over d_value / d_weight / d_light (as wtgpu_render fills them) that develops in registers and writes d_maps
+ * and d_picture (DEVICE, each may be NULL) on its way, then a small kernel and the copy of the records, for which the call waits: out[planes] is
+ * HOST memory.  d_mask: DEVICE, may be NULL.  Needs an uploaded scene (WTGPU_ERR_INVALID otherwise); its scratch memory is allocated at the first
+ * call and freed with the scene; touches neither films nor counters. */
+int wtgpu_film_polar_device(wtgpu_scene* scene, void* stream, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                            const wtgpu_film_polar_spec* spec, const float* d_mask, wtgpu_film_polar* out, float* d_maps, void* d_picture);
+/* The same on `n_threads` host threads (0: all cores) from HOST films; maps, picture: HOST, may be NULL; the result does not depend on n_threads.
+ * No device needed.  The picture is bit for bit the device's with the linear operator (the others call libm: within one code). */
+int wtgpu_film_polar_host(const wtgpu_scene* scene, const double* value, const double* weight, const double* light, uint64_t spe,
+                          const wtgpu_film_polar_spec* spec, const float* mask, uint32_t n_threads, wtgpu_film_polar* out, float* maps, void* picture);
+
 void wtgpu_scene_destroy(wtgpu_scene* scene);
 const char* wtgpu_last_error(void);
 const char* wtgpu_scene_stats_json(const wtgpu_scene* scene);

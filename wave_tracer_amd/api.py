@@ -69,6 +69,21 @@ class FilmCompare(C.Structure):      # wtgpu_film_compare
     _fields_ = FILM_COMPARE_FIELDS
 
 
+class FilmPolarSpec(C.Structure):    # wtgpu_film_polar_spec
+    _fields_ = [("flags", C.c_uint32), ("maps", C.c_uint32), ("picture_plane", C.c_uint32), ("format", C.c_uint32), ("c2", C.c_double), ("s2", C.c_double),
+                ("sat_gain", C.c_float), ("pad", C.c_float), ("tonemap", Tonemap)]
+
+
+FILM_POLAR_FIELDS = [("n", C.c_uint64), ("n_nonfinite", C.c_uint64), ("n_dark", C.c_uint64), ("n_over", C.c_uint64), ("argmax", C.c_uint64),
+                     ("max_dop", C.c_double), ("sum_i", C.c_double), ("sum_q", C.c_double), ("sum_u", C.c_double), ("sum_v", C.c_double),
+                     ("sum_lin", C.c_double), ("sum_pol", C.c_double)]
+
+
+class FilmPolar(C.Structure):        # wtgpu_film_polar
+    _fields_ = FILM_POLAR_FIELDS
+
+
+FILM_POLAR_MAPS = ["dolp", "dop", "docp", "aolp", "chi", "analyser"]      # bit i of wtgpu_film_polar_spec.maps, and the order of the maps in memory
 FILM_STATS_SCALES = ["linear", "dB"]
 FILM_STATS_ABS, FILM_STATS_LUMINANCE = 1, 2
 FILM_STATS_MAX_BINS = 4096
@@ -105,7 +120,7 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host",
            "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host",
            "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host",
-           "wtgpu_film_compare_device", "wtgpu_film_compare_host"]
+           "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
 CAPTURE_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_void_p)
 
@@ -191,6 +206,8 @@ def load_library():
     lib.wtgpu_film_stats_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(FilmStatsSpec), vp, u32, vp, vp]
     lib.wtgpu_film_compare_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmCompareSpec), vp, vp, vp]
     lib.wtgpu_film_compare_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmCompareSpec), vp, u32, vp, vp]
+    lib.wtgpu_film_polar_device.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(FilmPolarSpec), vp, vp, vp, vp]
+    lib.wtgpu_film_polar_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(FilmPolarSpec), vp, u32, vp, vp, vp]
     lib.wtgpu_calibrate_copy.argtypes = [u64, i32]
     lib.wtgpu_get_counters.argtypes = [vp, C.POINTER(Counters)]
     lib.wtgpu_reset_counters.argtypes = [vp]
@@ -788,6 +805,77 @@ class Scene:
         out = self._film_compare(call, stokes_component, abs, luminance, eps)
         out.update(d)
         return out
+
+    # ---- the polarisation view of a Stokes film (wtgpu_film_polar_*; csrc/wt/film_polar.h) ----
+    def _film_polar(self, what, call, luminance, maps, analyser, c2s2, picture, picture_plane, tm, fmt, sat_gain, masked):
+        """What film_polar_device / film_polar_host share: the spec, the records as a dict, the values derived from the sums, the maps by name.
+        call(spec, records, maps_shape_or_None, picture_shape_or_None) runs the pass and returns (maps array or None, picture or None)."""
+        import numpy as np
+        names = [maps] if isinstance(maps, str) else list(maps)
+        for m in names:
+            if m not in FILM_POLAR_MAPS:
+                raise ValueError(f"{what}: maps of {FILM_POLAR_MAPS} expected, got {m!r}")
+        if fmt not in TONEMAP_FORMATS:
+            raise ValueError(f"{what}: fmt f32, u8 or u16 expected, got {fmt!r}")
+        names = [m for m in FILM_POLAR_MAPS if m in names]
+        planes = self.spectral_channels + (1 if luminance else 0)
+        c2, s2 = (math.cos(2.0 * analyser), math.sin(2.0 * analyser)) if c2s2 is None else c2s2
+        st_tm, _ = self._tonemap_struct(dict(tm or {"op": "linear"}, table=None))
+        spec = FilmPolarSpec(FILM_STATS_LUMINANCE if luminance else 0, sum(1 << FILM_POLAR_MAPS.index(m) for m in names), int(picture_plane), TONEMAP_FORMATS[fmt],
+                             float(c2), float(s2), float(sat_gain), 0.0, st_tm)
+        rec = (FilmPolar * max(planes, 1))()
+        got_maps, got_picture = call(spec, rec, (self.height, self.width, planes, len(names)) if names else None,
+                                     (self.height, self.width, 4 if masked else 3) if picture else None)
+        out = {name: np.array([getattr(r, name) for r in rec][:planes], dtype=np.uint64 if t is C.c_uint64 else np.float64) for name, t in FILM_POLAR_FIELDS}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["dop_total"] = np.sqrt(out["sum_q"] ** 2 + out["sum_u"] ** 2 + out["sum_v"] ** 2) / out["sum_i"]
+            out["aolp_total"] = 0.5 * np.arctan2(out["sum_u"], out["sum_q"])
+            out["mean_dolp"] = out["sum_lin"] / out["sum_i"]
+            out["mean_dop"] = out["sum_pol"] / out["sum_i"]
+        out["maps"] = {m: got_maps[..., k] for k, m in enumerate(names)}
+        out["picture"] = got_picture
+        return out
+
+    def film_polar_device(self, value, weight, light, spe, *, luminance=False, maps=(), analyser=0.0, c2s2=None, mask=None, picture=False, picture_plane=0, tm=None,
+                          fmt="f32", sat_gain=1.0, stream=None):
+        """The polarisation view of a polarimetric film where it is (wtgpu_film_polar_device): value / weight / light are the torch f64 films on the
+        scene's device, mask an H x W f32 tensor there (pixels with mask > 0 count) or None.  One record per channel, plus the Stokes vector of the
+        BT.709 luminance of an RGB film with luminance=True.  Returns a dict of numpy arrays indexed by plane: n, n_nonfinite, n_dark, n_over, argmax
+        (uint64; the row-major pixel of max_dop, 2^64 - 1 where no pixel is lit), max_dop, sum_i, sum_q, sum_u, sum_v, sum_lin, sum_pol (float64; over
+        the lit pixels: finite, I > 0) and, derived here from the sums, dop_total = sqrt(sum_q^2 + sum_u^2 + sum_v^2) / sum_i, aolp_total =
+        atan2(sum_u, sum_q) / 2, mean_dolp = sum_lin / sum_i and mean_dop = sum_pol / sum_i (NaN where there is nothing to divide by).
+        maps: names of dolp, dop, docp, aolp, chi, analyser -> "maps": {name: torch f32 tensor H x W x planes on the device}, 0 where the mask excludes;
+        analyser: the analyser's angle theta in radians (c2s2 = (cos 2 theta, sin 2 theta) overrides it).  picture=True adds "picture": the false-colour
+        view of plane picture_plane (hue: the angle of linear polarisation, saturation: dolp x sat_gain, value: the intensity through the operator of
+        tm = {op, gamma, db_range}), a torch tensor H x W x 3 (x 4 with a mask) of float32 / uint8 / int16 as tonemap_device's."""
+        import torch
+        dev = self._device_films("film_polar_device", value, weight, light, mask)
+        st = self._stream_arg(stream, dev)
+
+        def call(spec, rec, maps_shape, picture_shape):
+            m = None if maps_shape is None else torch.empty(maps_shape, dtype=torch.float32, device=dev)
+            p = None if picture_shape is None else torch.empty(picture_shape, dtype={"f32": torch.float32, "u8": torch.uint8, "u16": torch.int16}[fmt], device=dev)
+            _check(load_library().wtgpu_film_polar_device(self._h, st, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe), C.byref(spec),
+                                                          None if mask is None else mask.data_ptr(), C.cast(rec, C.c_void_p),
+                                                          None if m is None else m.data_ptr(), None if p is None else p.data_ptr()))
+            return m, p
+        return self._film_polar("film_polar_device", call, luminance, maps, analyser, c2s2, picture, picture_plane, tm, fmt, sat_gain, mask is not None)
+
+    def film_polar_host(self, value, weight, light, spe, *, luminance=False, maps=(), analyser=0.0, c2s2=None, mask=None, picture=False, picture_plane=0, tm=None,
+                        fmt="f32", sat_gain=1.0, threads=0):
+        """film_polar_device's twin on host threads from numpy films (wtgpu_film_polar_host; threads 0 = all cores): the same dict, every field and every
+        map bit for bit the device's, the maps and the picture numpy arrays (the picture of float32 / uint8 / uint16).  No device needed."""
+        import numpy as np
+        v, w, l, m = self._host_films("film_polar_host", value, weight, light, mask)
+
+        def call(spec, rec, maps_shape, picture_shape):
+            mp = None if maps_shape is None else np.zeros(maps_shape, dtype=np.float32)
+            p = None if picture_shape is None else np.zeros(picture_shape, dtype={"f32": np.float32, "u8": np.uint8, "u16": np.uint16}[fmt])
+            _check(load_library().wtgpu_film_polar_host(self._h, v.ctypes.data, w.ctypes.data, l.ctypes.data, int(spe), C.byref(spec),
+                                                        None if m is None else m.ctypes.data, int(threads), C.cast(rec, C.c_void_p),
+                                                        None if mp is None else mp.ctypes.data, None if p is None else p.ctypes.data))
+            return mp, p
+        return self._film_polar("film_polar_host", call, luminance, maps, analyser, c2s2, picture, picture_plane, tm, fmt, sat_gain, m is not None)
 
     def profile_counters(self, n=8):
         """Test hook (wtgpu_test_hooks.h): the first n WTGPU_PROFILE scratch counters, accumulated since upload."""

@@ -1,9 +1,10 @@
 // wave_tracer_amd — the entry points that read films: develop, the tonemap spec / device / host calls (kernels_develop.hip), film statistics
-// (kernels_stats.hip) and film comparison (kernels_compare.hip); what they check of a film and keep with the scene between calls.
+// (kernels_stats.hip), film comparison (kernels_compare.hip) and the polarisation view (kernels_polar.hip); what they check of a film and keep with the scene between calls.
 #include "wtgpu_host.h"
 #include "wt/tonemap.h"
 #include "wt/film_stats.h"
 #include "wt/film_compare.h"
+#include "wt/film_polar.h"
 
 // The film a call reads, the Stokes component and the FS_* flags it asks for -> planes: the planes per call (channels, + 1 with FS_LUMINANCE).
 // `what` opens the message.
@@ -295,6 +296,84 @@ int wtgpu_film_compare_host(const wtgpu_scene* s, const double* a_value, const d
     try {
         film_compare_host(s->host.sensor, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec->stokes_component, spec->flags, spec->eps, mask, n_threads,
                           out, diff);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+
+// ---- the polarisation view of a Stokes film (kernels_polar.hip; wt/film_polar.h) ------------------------------------------------------------
+static_assert(sizeof(wtgpu_film_polar) == sizeof(film_polar_rec_t), "the kernels' record is wtgpu_film_polar");
+// what a spec says by itself and against the scene's film; planes: records per call; a: what the kernels are told
+static int film_polar_check(const wtgpu_scene* s, const wtgpu_film_polar_spec* spec, uint32_t& planes, film_polar_args_t& a) {
+    const sensor_t& sn = s->host.sensor;
+    if (film_stokes(sn) != 4) return fail(WTGPU_ERR_INVALID, "film_polar: a polarimetric film expected (this one has " + std::to_string(film_stokes(sn)) + " Stokes component)");
+    if (sn.channels != 1 && sn.channels != 3) return fail(WTGPU_ERR_INVALID, "film_polar: a film of 1 or 3 channels expected");
+    if (spec->flags & ~(uint32_t)FP_LUMINANCE) return fail(WTGPU_ERR_INVALID, "film_polar: flag 2 (LUMINANCE) expected");
+    if ((spec->flags & FP_LUMINANCE) && sn.channels != 3) return fail(WTGPU_ERR_INVALID, "film_polar: LUMINANCE needs a 3-channel film (this one has " + std::to_string(sn.channels) + ")");
+    if (spec->maps >> kFpMaps) return fail(WTGPU_ERR_INVALID, "film_polar: map bits 1 (DOLP), 2 (DOP), 4 (DOCP), 8 (AOLP), 16 (CHI) and 32 (ANALYSER) expected");
+    if (!std::isfinite(spec->c2) || !std::isfinite(spec->s2)) return fail(WTGPU_ERR_INVALID, "film_polar: finite c2 and s2 expected");
+    if (!std::isfinite(spec->sat_gain) || spec->sat_gain < 0.f) return fail(WTGPU_ERR_INVALID, "film_polar: a finite sat_gain >= 0 expected");
+    planes = sn.channels + ((spec->flags & FP_LUMINANCE) ? 1u : 0u);
+    if (spec->picture_plane >= planes)
+        return fail(WTGPU_ERR_INVALID, "film_polar: picture_plane " + std::to_string(spec->picture_plane) + " out of range (the call has " + std::to_string(planes) + ")");
+    if (spec->format > TM_U16) return fail(WTGPU_ERR_INVALID, "film_polar: format 0 (f32), 1 (u8) or 2 (u16) expected");
+    const wtgpu_tonemap& tm = spec->tonemap;
+    if (tm.op == TM_FUNCTION) return fail(WTGPU_ERR_INVALID, "film_polar: the 'function' operator is not supported (the expression is read from the scene file, not evaluated)");
+    if (tm.op < TM_LINEAR || tm.op > TM_FUNCTION) return fail(WTGPU_ERR_INVALID, "film_polar: operator 0 (linear), 1 (gamma), 2 (sRGB) or 3 (dB) expected");
+    if (tm.op == TM_GAMMA && !(tm.gamma > 0.f)) return fail(WTGPU_ERR_INVALID, "film_polar: 'gamma' must be positive");
+    if (tm.op == TM_DB && !(tm.db_max - tm.db_min > 0.f)) return fail(WTGPU_ERR_INVALID, "film_polar: expected valid 'db' range to be provided");
+    a = film_polar_args_t{};
+    a.c2 = spec->c2, a.s2 = spec->s2;
+    a.maps = spec->maps;
+    for (uint32_t m = 0; m < kFpMaps; ++m) a.n_maps += spec->maps >> m & 1u;
+    a.picture_plane = spec->picture_plane, a.format = spec->format;
+    a.sat_gain = spec->sat_gain;
+    a.tm.op = tm.op;
+    a.tm.mode = TM_NORMAL;
+    a.tm.inv_gamma = tm.op == TM_GAMMA ? 1.f / tm.gamma : 1.f;
+    a.tm.db_min = tm.db_min;
+    a.tm.db_len = tm.db_max - tm.db_min;
+    return WTGPU_OK;
+}
+constexpr size_t kFpRecBytes = kFsMaxPlanes * sizeof(film_polar_rec_t);
+static_assert(kFpRecBytes % 32 == 0, "the wavefronts' records (32 bytes each) follow the records in one block");
+
+int wtgpu_film_polar_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                            const wtgpu_film_polar_spec* spec, const float* d_mask, wtgpu_film_polar* out, float* d_maps, void* d_picture) {
+    if (!s || !d_value || !d_weight || !d_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    uint32_t planes = 0;
+    film_polar_args_t a{};
+    if (const int rc = film_polar_check(s, spec, planes, a)) return rc;
+    if (d_maps && a.n_maps == 0) return fail(WTGPU_ERR_INVALID, "film_polar: d_maps without a map bit");
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    const sensor_t& sn = s->host.sensor;
+    const uint64_t npix = (uint64_t)sn.width * sn.height;
+    if (npix == 0) return fail(WTGPU_ERR_INVALID, "film_polar: the film has no pixels");
+    device_guard_t guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // first use: the records with the wavefronts' records behind them, the pinned copy of the former, the chunk sums (all levels, kFsMaxPlanes
+    // planes of kFpSums sums)
+    film_scratch_t& f = s->fp;
+    if (const int rc = film_scratch_alloc(s, f, kFpRecBytes + film_polar_wave_bytes(npix, s->n_cus), kFpRecBytes, (size_t)kFsMaxPlanes * kFpSums * fs_scratch_len(npix)))
+        return rc;
+    // The call waits for its own result below, so the block is free again when it returns.
+    const int e = film_polar_launch(sn, stream, s->n_cus, d_value, d_weight, d_light, spe, spec->flags, a, s->knobs.film_polar_staged, d_mask, f.d_block, f.d_sums, f.d_block + kFpRecBytes, d_maps, d_picture);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_polar: ") + hipGetErrorString((hipError_t)e));
+    HIP_CHECK(hipMemcpyAsync(f.h_block, f.d_block, planes * sizeof(film_polar_rec_t), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    std::memcpy(out, f.h_block, planes * sizeof(wtgpu_film_polar));
+    return WTGPU_OK;
+}
+int wtgpu_film_polar_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_film_polar_spec* spec,
+                          const float* mask, uint32_t n_threads, wtgpu_film_polar* out, float* maps, void* picture) {
+    if (!s || !value || !weight || !light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    uint32_t planes = 0;
+    film_polar_args_t a{};
+    if (const int rc = film_polar_check(s, spec, planes, a)) return rc;
+    if (maps && a.n_maps == 0) return fail(WTGPU_ERR_INVALID, "film_polar: maps without a map bit");
+    try {
+        film_polar_host(s->host.sensor, value, weight, light, spe, spec->flags, a, mask, n_threads, out, maps, picture);
     } catch (const std::exception& e) {
         return fail(WTGPU_ERR_INVALID, e.what());
     }

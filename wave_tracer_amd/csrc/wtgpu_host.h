@@ -58,7 +58,7 @@ struct chunk_rec_t {
 };
 
 // What a film feature (wtgpu_film.hip) keeps with the scene from its first call on: its results on the device (the statistics: records, histogram
-// and edge table; the comparison: records, then the wavefronts' records), their head pinned on the host, and the chunk sums of every level of the
+// and edge table; the comparison and the polarisation view: records, then the wavefronts' records), their head pinned on the host, and the chunk sums of every level of the
 // fixed summation order (wt/film_stats.h: fs_scratch_len).
 struct film_scratch_t {
     unsigned char* d_block = nullptr;
@@ -118,7 +118,7 @@ struct wtgpu_scene {
     float* d_tm_table = nullptr;         // wtgpu_tonemap_device: the colour table of the last call (kMaxTonemapTable entries), staged the same way
     float* h_tm_table = nullptr;
     hipEvent_t ev_tm = nullptr;
-    film_scratch_t fs, fc;               // wtgpu_film_stats_device, wtgpu_film_compare_device
+    film_scratch_t fs, fc, fp;           // wtgpu_film_stats_device, wtgpu_film_compare_device, wtgpu_film_polar_device
     // WTGPU_TRACE_AB (diagnostic, tests/test_gpu_traversal.py): accumulated over the replayed rounds — milliseconds of k_trace_refill / k_trace_sm on the
     // same queue, words of their outputs that differ (traversal records + triangle lists + heavy-queue checksums), walks replayed
     double ab_ms[2] = {0, 0};

@@ -13,7 +13,8 @@
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
 //   kernels_compare.hip k_film_compare / k_film_compare_finish: difference statistics of two films (not part of a render)
-//   kernels_film.h      what the last three share on the device and in their host twins: chunk geometry, level reduction, grid, dispatch, host threads
+//   kernels_polar.hip   k_film_polar / k_film_polar_finish: polarisation maps, Stokes sums and false-colour picture of a Stokes film (not part of a render)
+//   kernels_film.h      what the last four share on the device and in their host twins: chunk geometry, level reduction, grid, dispatch, host threads
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -34,6 +35,7 @@
 using namespace wt;
 namespace wt {
 struct tonemap_args_t;   // wt/tonemap.h (kernels_develop.hip and the entry points that launch it)
+struct film_polar_args_t;   // wt/film_polar.h (kernels_polar.hip and its entry points)
 }
 
 namespace wtk {
@@ -591,6 +593,17 @@ int film_compare_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, 
 void film_compare_host(const sensor_t& sn, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
                        const double* b_weight, const double* b_light, uint64_t spe_b, uint32_t s, uint32_t flags, double eps, const float* mask, uint32_t n_threads,
                        void* out_rec, float* diff);
+// kernels_polar.hip: the polarisation view of a Stokes film (wtgpu_film_polar_device / wtgpu_film_polar_host; wt/film_polar.h).  Films of a polarimetric
+// sensor as wtgpu_render fills them; flags: FP_LUMINANCE; a: the analyser, the maps' bits and the picture's plane, format and operator.  d_rec:
+// film_polar_rec_t per plane; d_sums: kFsMaxPlanes x kFpSums x fs_scratch_len(pixels) doubles; d_wave: film_polar_wave_bytes(pixels, n_cus) bytes — none of
+// them has to be cleared; d_maps: null or [height][width][planes][a.n_maps] f32; d_picture: null or [height][width][3, or 4 with a mask] in a.format.
+// staged: the measured alternative (WTGPU_FILM_POLAR_STAGED).  Two kernels on `stream`; the launch returns a hipError_t.
+size_t film_polar_wave_bytes(uint64_t npix, uint32_t n_cus);
+int film_polar_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                      uint32_t flags, const film_polar_args_t& a, uint32_t staged, const float* d_mask, void* d_rec, double* d_sums, void* d_wave, float* d_maps,
+                      void* d_picture);
+void film_polar_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, uint32_t flags, const film_polar_args_t& a,
+                     const float* mask, uint32_t n_threads, void* out_rec, float* maps, void* picture);
 
 }   // namespace wtk
 using namespace wtk;

@@ -320,6 +320,7 @@ void release_device(wtgpu_scene* s) {
     s->ev_tm = nullptr;
     film_scratch_free(s->fs);
     film_scratch_free(s->fc);
+    film_scratch_free(s->fp);
     s->uploaded = false;
 }
 

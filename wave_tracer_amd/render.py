@@ -69,6 +69,15 @@ def noise_estimate(scene, films_a, films_b, spe, *, mask=None):
     return float(np.sqrt(num / den)) if den > 0 else 0.0
 
 
+def polarisation(scene, films, spe, **kw):
+    """Where and how strongly is the light of a polarimetric film polarised?  films = (value, weight, light), torch tensors on the scene's device
+    (Scene.film_polar_device: the maps and the picture stay there, one record per plane crosses to the host) or numpy arrays
+    (Scene.film_polar_host).  kw: luminance, maps, analyser, mask, picture, picture_plane, tm, fmt, sat_gain.  Returns that call's dict: counts,
+    max_dop / argmax, the Stokes sums with dop_total, aolp_total, mean_dolp, mean_dop, "maps" by name, "picture"."""
+    polar = scene.film_polar_host if isinstance(films[0], np.ndarray) else scene.film_polar_device
+    return polar(*films, spe, **kw)
+
+
 def _render_range_hip(scene, device):
     """render_to_noise's default renderer: the HIP path into fresh films on the scene's GPU (there is no CPU fallback)."""
     import torch
