@@ -397,6 +397,45 @@ int wtgpu_film_polar_device(wtgpu_scene* scene, void* stream, const double* d_va
 int wtgpu_film_polar_host(const wtgpu_scene* scene, const double* value, const double* weight, const double* light, uint64_t spe,
                           const wtgpu_film_polar_spec* spec, const float* mask, uint32_t n_threads, wtgpu_film_polar* out, float* maps, void* picture);
 
+/* Denoising a film from its two half-films A and B (two renders of disjoint sample ranges, as render_to_noise keeps them) without the films leaving
+ * the device: the dual-buffer non-local-means filter of Rousselle, Knaus and Zwicker 2012 — the weights that filter one half are computed from the
+ * other, the per-pixel variance comes from (a - b)^2, and the difference of the two filtered halves estimates the error that is left.
+ *   planes     all P = channels x stokes planes of a pixel are filtered with ONE set of weights (a Stokes vector is filtered as one thing): a_i, b_i are
+ *              the developed values of plane i with spe_a / spe_b, bit for bit wtgpu_develop's.  The guide planes, from which the weights come, are
+ *              Stokes component 0 of each channel.
+ *   variance   e_c = (a_c - b_c)^2 / 2 per guide plane; v_c = the mean of e_c over the 3 x 3 neighbourhood, coordinates clamped to the film.
+ *   weights    of a candidate q = p + (dx, dy), |dx|, |dy| <= window_radius, for the guide buffer y: the mean over the patch of (2 patch_radius + 1)^2
+ *              pixels (coordinates clamped to the film, p's and q's separately) and the guide planes of
+ *                ((y_c(p) - y_c(q))^2 - alpha (v_c(p) + min(v_c(p), v_c(q)))) / (eps + k^2 (v_c(p) + v_c(q)))
+ *              is D; w = 1 where D <= 0, exp(-D) otherwise (the library's own polynomial: relative error below 1e-6; 0 from 2^-126 down), 0 for a NaN.
+ *              There is no cutoff.  A candidate lies inside the film, is valid (every plane of a and of b finite there) and, with a mask
+ *              ([height][width] f32), has mask > 0.
+ *   filter     fa_i(p) = a_i(p) + sum_q w_b(p, q) (a_i(q) - a_i(p)) / sum_q w_b(p, q) with the weights of guide b, fb likewise with the weights of
+ *              guide a; the sums run over the candidates in row-major order of (dy, dx), in f32.
+ *   out        (fa_i + fb_i) / 2;  residual (may be NULL): (fa_i - fb_i) / 2.  Both [height][width][channels][stokes] f32, the layout of
+ *              wtgpu_develop_device's result.  A pixel that is not valid, not in the mask, or has no positive sum of weights (next to a non-finite pixel)
+ *              passes through: out = (a_i + b_i) / 2, residual = (a_i - b_i) / 2.  A NaN is stored as 0x7fc00000.
+ * All arithmetic is f32 + - x / in one fixed order (wt/film_denoise.h) and calls no libm function: device and host agree on every value bit for
+ * bit; a constant film comes back as itself and window_radius 0 gives (a + b) / 2, both bit for bit.
+ * Errors (WTGPU_ERR_INVALID with a message): window_radius > 10, patch_radius > 3, k not finite or <= 0, alpha not finite or < 0, eps not finite
+ * or <= 0, nonzero flags, a film whose channel count is not 1 or 3. */
+typedef struct wtgpu_film_denoise_spec {
+    uint32_t window_radius /* r: 0 .. 10 */, patch_radius /* f: 0 .. 3 */, flags /* none yet: must be 0 */, pad;
+    float k /* 0.45 */, alpha /* 1 */, eps /* 1e-10 */, pad2;
+} wtgpu_film_denoise_spec;
+/* On the device, on `stream`: a_* / b_* are the DEVICE films of the two halves as wtgpu_render fills them (A and B may be the same memory), d_mask
+ * DEVICE or NULL, d_out and d_residual (may be NULL) DEVICE.  Nothing returns to the host, so the call is asynchronous on `stream`.  Needs an
+ * uploaded scene (WTGPU_ERR_INVALID otherwise); its scratch memory (the developed halves, 3 P + 2 channels floats and two bytes per pixel) is allocated
+ * at the first call, shared by all calls — order calls on different streams yourself — and freed with the scene; touches neither films nor counters. */
+int wtgpu_film_denoise_device(wtgpu_scene* scene, void* stream, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                              const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec,
+                              const float* d_mask, float* d_out, float* d_residual);
+/* The same on `n_threads` host threads (0: all cores) from HOST films; mask, residual: HOST, may be NULL; the result does not depend on n_threads.
+ * No device needed.  Naive per pixel and candidate (seconds for a full-size film): the reference the device is held to, not a fast path. */
+int wtgpu_film_denoise_host(const wtgpu_scene* scene, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                            const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec,
+                            const float* mask, uint32_t n_threads, float* out, float* residual);
+
 void wtgpu_scene_destroy(wtgpu_scene* scene);
 const char* wtgpu_last_error(void);
 const char* wtgpu_scene_stats_json(const wtgpu_scene* scene);

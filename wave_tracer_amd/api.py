@@ -83,6 +83,11 @@ class FilmPolar(C.Structure):        # wtgpu_film_polar
     _fields_ = FILM_POLAR_FIELDS
 
 
+class FilmDenoiseSpec(C.Structure):  # wtgpu_film_denoise_spec
+    _fields_ = [("window_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32), ("k", C.c_float), ("alpha", C.c_float),
+                ("eps", C.c_float), ("pad2", C.c_float)]
+
+
 FILM_POLAR_MAPS = ["dolp", "dop", "docp", "aolp", "chi", "analyser"]      # bit i of wtgpu_film_polar_spec.maps, and the order of the maps in memory
 FILM_STATS_SCALES = ["linear", "dB"]
 FILM_STATS_ABS, FILM_STATS_LUMINANCE = 1, 2
@@ -120,7 +125,8 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host",
            "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host",
            "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host",
-           "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host"]
+           "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host",
+           "wtgpu_film_denoise_device", "wtgpu_film_denoise_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
 CAPTURE_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_void_p)
 
@@ -138,6 +144,15 @@ def connect_class_order():
     keys = np.zeros(n.value, np.uint32)
     _check(lib.wtgpu_test_connect_class_order(keys.ctypes.data, keys.size, C.byref(n), C.byref(dim)))
     return keys, int(dim.value)
+
+
+def dn_exp2_neg(t):
+    """Test hook (wtgpu_test_hooks.h): wt/film_denoise.h's dn_exp2_neg, 2^-t for t >= 0, element by element on the host; t, result: numpy f32."""
+    import numpy as np
+    t = np.ascontiguousarray(t, dtype=np.float32)
+    out = np.zeros(t.shape, dtype=np.float32)
+    _check(load_library().wtgpu_test_dn_exp2_neg(t.ctypes.data, t.size, out.ctypes.data))
+    return out
 
 
 def load_library():
@@ -208,6 +223,9 @@ def load_library():
     lib.wtgpu_film_compare_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmCompareSpec), vp, u32, vp, vp]
     lib.wtgpu_film_polar_device.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(FilmPolarSpec), vp, vp, vp, vp]
     lib.wtgpu_film_polar_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(FilmPolarSpec), vp, u32, vp, vp, vp]
+    lib.wtgpu_film_denoise_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmDenoiseSpec), vp, vp, vp]
+    lib.wtgpu_film_denoise_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmDenoiseSpec), vp, u32, vp, vp]
+    lib.wtgpu_test_dn_exp2_neg.argtypes = [vp, u64, vp]
     lib.wtgpu_calibrate_copy.argtypes = [u64, i32]
     lib.wtgpu_get_counters.argtypes = [vp, C.POINTER(Counters)]
     lib.wtgpu_reset_counters.argtypes = [vp]
@@ -876,6 +894,50 @@ class Scene:
                                                         None if mp is None else mp.ctypes.data, None if p is None else p.ctypes.data))
             return mp, p
         return self._film_polar("film_polar_host", call, luminance, maps, analyser, c2s2, picture, picture_plane, tm, fmt, sat_gain, m is not None)
+
+    # ---- denoising a film from its two half-films (wtgpu_film_denoise_*; csrc/wt/film_denoise.h) ----
+    @staticmethod
+    def _film_denoise_spec(window, patch, k, alpha, eps):
+        return FilmDenoiseSpec(int(window), int(patch), 0, 0, float(k), float(alpha), float(eps), 0.0)
+
+    def film_denoise_device(self, films_a, spe_a, films_b, spe_b, *, window=7, patch=2, k=0.45, alpha=1.0, eps=1e-10, mask=None, residual=False, stream=None):
+        """Denoises the film that two half-films add up to, where they are (wtgpu_film_denoise_device): the dual-buffer non-local-means filter of
+        Rousselle, Knaus and Zwicker 2012.  films_a / films_b are (value, weight, light), torch f64 tensors on the scene's device, of two renders over
+        disjoint sample ranges (render_to_noise(..., halves=True)), developed with spe_a / spe_b samples per element; mask an H x W f32 tensor there
+        (pixels with mask > 0 are filtered and serve as candidates; the others come back as the merged film) or None.  window: the radius r of the
+        search window (0 .. 10: (2 r + 1)^2 candidates), patch: the radius f of the patches compared (0 .. 3), k: the filter strength, alpha: how much
+        of the noise variance is taken off a squared difference, eps: what keeps the quotient finite where there is no variance.  All planes of a pixel
+        are filtered with one set of weights, computed from Stokes component 0 of each channel of the OTHER half.  Returns {"film": torch f32
+        [H, W, channels, stokes] on the device, (fa + fb) / 2 of the two filtered halves; "residual": (fa - fb) / 2 the same way with residual=True —
+        an estimate of the error that is left — or None}.  Enqueued on `stream` (default: torch's current); nothing crosses to the host."""
+        import torch
+        dev = self._device_films("film_denoise_device", *films_a, mask)
+        self._device_films("film_denoise_device", *films_b)
+        shape = (self.height, self.width, self.spectral_channels, self.stokes)
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        res = torch.empty(shape, dtype=torch.float32, device=dev) if residual else None
+        spec = self._film_denoise_spec(window, patch, k, alpha, eps)
+        _check(load_library().wtgpu_film_denoise_device(self._h, self._stream_arg(stream, dev), *(t.data_ptr() for t in films_a), int(spe_a),
+                                                        *(t.data_ptr() for t in films_b), int(spe_b), C.byref(spec), None if mask is None else mask.data_ptr(),
+                                                        out.data_ptr(), None if res is None else res.data_ptr()))
+        return {"film": out, "residual": res}
+
+    def film_denoise_host(self, films_a, spe_a, films_b, spe_b, *, window=7, patch=2, k=0.45, alpha=1.0, eps=1e-10, mask=None, residual=False, threads=0):
+        """film_denoise_device's twin on host threads from numpy films (wtgpu_film_denoise_host; threads 0 = all cores): the same dict, "film" and
+        "residual" numpy arrays, bit for bit the device's.  No device needed.  Naive per pixel and candidate: what the device is held to, not a fast path."""
+        import numpy as np
+        sets = [self._host_films("film_denoise_host", *films)[:3] for films in (films_a, films_b)]
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+        if m is not None and m.size != self.width * self.height:
+            raise ValueError("film_denoise_host: a mask of the scene's size expected")
+        shape = (self.height, self.width, self.spectral_channels, self.stokes)
+        out = np.zeros(shape, dtype=np.float32)
+        res = np.zeros(shape, dtype=np.float32) if residual else None
+        spec = self._film_denoise_spec(window, patch, k, alpha, eps)
+        _check(load_library().wtgpu_film_denoise_host(self._h, *(t.ctypes.data for t in sets[0]), int(spe_a), *(t.ctypes.data for t in sets[1]), int(spe_b),
+                                                      C.byref(spec), None if m is None else m.ctypes.data, int(threads), out.ctypes.data,
+                                                      None if res is None else res.ctypes.data))
+        return {"film": out, "residual": res}
 
     def profile_counters(self, n=8):
         """Test hook (wtgpu_test_hooks.h): the first n WTGPU_PROFILE scratch counters, accumulated since upload."""

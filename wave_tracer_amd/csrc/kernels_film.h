@@ -1,4 +1,4 @@
-// wave_tracer_amd — what the film kernels (kernels_develop.hip, kernels_stats.hip, kernels_compare.hip, kernels_polar.hip) and their host twins share beyond the
+// wave_tracer_amd — what the film kernels (kernels_develop.hip, kernels_stats.hip, kernels_compare.hip, kernels_polar.hip, kernels_denoise.hip) and their host twins share beyond the
 // arithmetic of wt/film_stats.h: the chunk geometry of the fixed summation order on a wavefront, the reduction of the chunk sums, the grid that
 // follows the film, the choice of a kernel by (channels, luminance), and the host threads of the twins (kernels_mask.hip's too).
 //

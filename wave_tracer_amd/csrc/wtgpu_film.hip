@@ -1,10 +1,12 @@
 // wave_tracer_amd — the entry points that read films: develop, the tonemap spec / device / host calls (kernels_develop.hip), film statistics
-// (kernels_stats.hip), film comparison (kernels_compare.hip) and the polarisation view (kernels_polar.hip); what they check of a film and keep with the scene between calls.
+// (kernels_stats.hip), film comparison (kernels_compare.hip), the polarisation view (kernels_polar.hip) and the denoiser of two half-films (kernels_denoise.hip); what they check of a film
+// and keep with the scene between calls.
 #include "wtgpu_host.h"
 #include "wt/tonemap.h"
 #include "wt/film_stats.h"
 #include "wt/film_compare.h"
 #include "wt/film_polar.h"
+#include "wt/film_denoise.h"
 
 // The film a call reads, the Stokes component and the FS_* flags it asks for -> planes: the planes per call (channels, + 1 with FS_LUMINANCE).
 // `what` opens the message.
@@ -377,6 +379,70 @@ int wtgpu_film_polar_host(const wtgpu_scene* s, const double* value, const doubl
     } catch (const std::exception& e) {
         return fail(WTGPU_ERR_INVALID, e.what());
     }
+    return WTGPU_OK;
+}
+
+// ---- denoising a film from its two half-films (kernels_denoise.hip; wt/film_denoise.h) -------------------------------------------------------
+// what a spec says by itself and against the scene's film; a: what the kernels are told
+static int film_denoise_check(const wtgpu_scene* s, const wtgpu_film_denoise_spec* spec, film_denoise_args_t& a) {
+    const sensor_t& sn = s->host.sensor;
+    if (sn.channels != 1 && sn.channels != 3) return fail(WTGPU_ERR_INVALID, "film_denoise: a film of 1 or 3 channels expected");
+    if (spec->window_radius > kDnMaxWindow)
+        return fail(WTGPU_ERR_INVALID, "film_denoise: window_radius " + std::to_string(spec->window_radius) + " out of range (0 .. " + std::to_string(kDnMaxWindow) + ")");
+    if (spec->patch_radius > kDnMaxPatch)
+        return fail(WTGPU_ERR_INVALID, "film_denoise: patch_radius " + std::to_string(spec->patch_radius) + " out of range (0 .. " + std::to_string(kDnMaxPatch) + ")");
+    if (spec->flags) return fail(WTGPU_ERR_INVALID, "film_denoise: no flags are defined (0 expected)");
+    if (!std::isfinite(spec->k) || !(spec->k > 0.f)) return fail(WTGPU_ERR_INVALID, "film_denoise: a finite k > 0 expected");
+    if (!std::isfinite(spec->alpha) || spec->alpha < 0.f) return fail(WTGPU_ERR_INVALID, "film_denoise: a finite alpha >= 0 expected");
+    if (!std::isfinite(spec->eps) || !(spec->eps > 0.f)) return fail(WTGPU_ERR_INVALID, "film_denoise: a finite eps > 0 expected");
+    static_assert(kFsMaxPlanes * 3 == kDnMaxPlanes, "three channels of four Stokes components");
+    a = film_denoise_args_t{};
+    a.r = spec->window_radius, a.f = spec->patch_radius;
+    a.k2 = spec->k * spec->k;
+    a.alpha = spec->alpha, a.eps = spec->eps;
+    const uint32_t side = 2u * a.f + 1u;
+    a.inv_norm = 1.0f / (float)(sn.channels * side * side);
+    return WTGPU_OK;
+}
+
+int wtgpu_film_denoise_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                              const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec, const float* d_mask, float* d_out,
+                              float* d_residual) {
+    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    film_denoise_args_t a{};
+    if (const int rc = film_denoise_check(s, spec, a)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    const sensor_t& sn = s->host.sensor;
+    if ((uint64_t)sn.width * sn.height == 0) return fail(WTGPU_ERR_INVALID, "film_denoise: the film has no pixels");
+    device_guard_t guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // first use: the developed half-films, their variance, what one direction leaves for the other.  Nothing comes back to the host, so the call
+    // does not wait; calls on different streams would share the scratch memory and must be ordered by the caller.
+    if (!s->d_denoise)
+        if (const int rc = dmalloc(s, &s->d_denoise, film_denoise_scratch_floats(sn))) return rc;
+    // Both directions in one launch up to 4 planes, one launch each for 12, unless the knob says otherwise: film_denoise_launch has the measurement.
+    const uint32_t fused = s->knobs.film_denoise_fused == 2 ? (film_planes(sn) <= 4 ? 1u : 0u) : s->knobs.film_denoise_fused;
+    const int e = film_denoise_launch(sn, stream, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, fused, d_mask, s->d_denoise,
+                                      d_out, d_residual);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_denoise_filter: ") + hipGetErrorString((hipError_t)e));
+    return WTGPU_OK;
+}
+int wtgpu_film_denoise_host(const wtgpu_scene* s, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                            const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec, const float* mask, uint32_t n_threads,
+                            float* out, float* residual) {
+    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    film_denoise_args_t a{};
+    if (const int rc = film_denoise_check(s, spec, a)) return rc;
+    try {
+        film_denoise_host(s->host.sensor, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, mask, n_threads, out, residual);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+int wtgpu_test_dn_exp2_neg(const float* t, uint64_t n, float* out) {
+    if (!t || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    film_denoise_exp2_neg(t, n, out);
     return WTGPU_OK;
 }
 

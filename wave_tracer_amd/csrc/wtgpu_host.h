@@ -7,7 +7,7 @@
 //   wtgpu_trace_ab.hip   WTGPU_TRACE_AB replay harness, the alternative forms of the per-lane traversal
 //   wtgpu_counters.hip   wtgpu_get_counters and its profile printers, reset
 //   wtgpu_queries.hip    ray / cone / region queries, sensor masks, the test probes
-//   wtgpu_film.hip       what reads films: develop and tonemap, film statistics, film comparison
+//   wtgpu_film.hip       what reads films: develop and tonemap, film statistics, film comparison, the polarisation view, the denoiser
 //   wtgpu_control.hip    cancel / pause / resume / capture / progressive render; the RCCL film reduction
 #pragma once
 #include <hip/hip_runtime.h>
@@ -119,6 +119,7 @@ struct wtgpu_scene {
     float* h_tm_table = nullptr;
     hipEvent_t ev_tm = nullptr;
     film_scratch_t fs, fc, fp;           // wtgpu_film_stats_device, wtgpu_film_compare_device, wtgpu_film_polar_device
+    float* d_denoise = nullptr;          // wtgpu_film_denoise_device: the developed half-films, their variance and what one direction leaves for the other
     // WTGPU_TRACE_AB (diagnostic, tests/test_gpu_traversal.py): accumulated over the replayed rounds — milliseconds of k_trace_refill / k_trace_sm on the
     // same queue, words of their outputs that differ (traversal records + triangle lists + heavy-queue checksums), walks replayed
     double ab_ms[2] = {0, 0};

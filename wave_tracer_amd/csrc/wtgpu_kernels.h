@@ -14,7 +14,8 @@
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
 //   kernels_compare.hip k_film_compare / k_film_compare_finish: difference statistics of two films (not part of a render)
 //   kernels_polar.hip   k_film_polar / k_film_polar_finish: polarisation maps, Stokes sums and false-colour picture of a Stokes film (not part of a render)
-//   kernels_film.h      what the last four share on the device and in their host twins: chunk geometry, level reduction, grid, dispatch, host threads
+//   kernels_denoise.hip k_denoise_prepare / _variance / k_denoise_filter: the dual-buffer non-local-means filter of two half-films (not part of a render)
+//   kernels_film.h      what the last five share on the device and in their host twins: chunk geometry, level reduction, grid, dispatch, host threads
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -36,6 +37,7 @@ using namespace wt;
 namespace wt {
 struct tonemap_args_t;   // wt/tonemap.h (kernels_develop.hip and the entry points that launch it)
 struct film_polar_args_t;   // wt/film_polar.h (kernels_polar.hip and its entry points)
+struct film_denoise_args_t;   // wt/film_denoise.h (kernels_denoise.hip and its entry points)
 }
 
 namespace wtk {
@@ -604,6 +606,19 @@ int film_polar_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, co
                       void* d_picture);
 void film_polar_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, uint32_t flags, const film_polar_args_t& a,
                      const float* mask, uint32_t n_threads, void* out_rec, float* maps, void* picture);
+// kernels_denoise.hip: the dual-buffer non-local-means filter of two half-films (wtgpu_film_denoise_device / wtgpu_film_denoise_host; wt/film_denoise.h).
+// Two film sets as wtgpu_render fills them (they may be the same memory); a: the radii, k x k, alpha, eps and the patch norm.  d_scratch:
+// film_denoise_scratch_floats(sn) floats, none of which has to be cleared; d_out, d_residual (may be null): [height][width][planes] f32.  fused: both
+// directions in one launch of k_denoise_filter (1) or one launch each (0); WTGPU_FILM_DENOISE_FUSED, whose default chooses by the film's planes.  Three or four kernels on `stream`; the launch
+// returns a hipError_t.  film_denoise_exp2_neg: wt/film_denoise.h's dn_exp2_neg element by element, for the test of its bound.
+size_t film_denoise_scratch_floats(const sensor_t& sn);
+int film_denoise_launch(const sensor_t& sn, hipStream_t stream, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                        const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const film_denoise_args_t& a, uint32_t fused,
+                        const float* d_mask, float* d_scratch, float* d_out, float* d_residual);
+void film_denoise_host(const sensor_t& sn, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                       const double* b_weight, const double* b_light, uint64_t spe_b, const film_denoise_args_t& a, const float* mask, uint32_t n_threads,
+                       float* out, float* residual);
+void film_denoise_exp2_neg(const float* t, uint64_t n, float* out);
 
 }   // namespace wtk
 using namespace wtk;

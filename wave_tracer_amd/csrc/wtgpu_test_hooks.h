@@ -58,6 +58,8 @@ int wtgpu_test_flux_queries(wtgpu_scene* s, void* stream, const uint32_t* d_quer
  *   everything in flight. */
 int wtgpu_test_connect_class_order(uint32_t* keys, uint32_t cap, uint32_t* n_keys, uint32_t* key_dim);
 int wtgpu_test_connect_class_items(wtgpu_scene* s, uint32_t slice, uint32_t* table, uint32_t* items, uint32_t items_cap, uint32_t* n_items);
+/* out[i] = dn_exp2_neg(t[i]) of wt/film_denoise.h (2^-t for t >= 0, the film denoiser's weight function), on the host: for the test of its bound. */
+int wtgpu_test_dn_exp2_neg(const float* t, uint64_t n, float* out);
 #ifdef __cplusplus
 }
 #endif

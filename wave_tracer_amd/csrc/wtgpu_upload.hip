@@ -321,6 +321,7 @@ void release_device(wtgpu_scene* s) {
     film_scratch_free(s->fs);
     film_scratch_free(s->fc);
     film_scratch_free(s->fp);
+    s->d_denoise = nullptr;      // (freed with dev_allocs)
     s->uploaded = false;
 }
 

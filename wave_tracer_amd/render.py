@@ -78,6 +78,28 @@ def polarisation(scene, films, spe, **kw):
     return polar(*films, spe, **kw)
 
 
+def denoise(scene, films_a, films_b, spe, **kw):
+    """Denoises the film that the half-films A and B add up to (render_to_noise(..., halves=True); `spe` samples per element each): films_a / films_b
+    are (value, weight, light), torch tensors on the scene's device (Scene.film_denoise_device: everything stays there) or numpy arrays
+    (Scene.film_denoise_host).  kw: window, patch, k, alpha, eps, mask, residual (default here: True).  Returns that call's dict — "film", "residual" —
+    and "residual_rel" = ||residual|| / ||film|| over the guide planes (Stokes component 0 of each channel) of the pixels where both are finite: an
+    ESTIMATE of the relative error that is left, from the difference of the two filtered halves (None with residual=False; 0 for an all-zero film)."""
+    on_host = isinstance(films_a[0], np.ndarray)
+    out = (scene.film_denoise_host if on_host else scene.film_denoise_device)(films_a, spe, films_b, spe, **dict({"residual": True}, **kw))
+    out["residual_rel"] = None
+    if out["residual"] is not None:
+        film, res = (t[..., 0] for t in (out["film"], out["residual"]))
+        if on_host:
+            ok = np.isfinite(film).all(axis=-1) & np.isfinite(res).all(axis=-1)
+            num, den = float((res[ok].astype(np.float64) ** 2).sum()), float((film[ok].astype(np.float64) ** 2).sum())
+        else:
+            import torch
+            ok = torch.isfinite(film).all(dim=-1) & torch.isfinite(res).all(dim=-1)
+            num, den = float((res[ok].double() ** 2).sum()), float((film[ok].double() ** 2).sum())
+        out["residual_rel"] = float(np.sqrt(num / den)) if den > 0 else 0.0
+    return out
+
+
 def _render_range_hip(scene, device):
     """render_to_noise's default renderer: the HIP path into fresh films on the scene's GPU (there is no CPU fallback)."""
     import torch
@@ -93,14 +115,16 @@ def _render_range_hip(scene, device):
     return renderer
 
 
-def render_to_noise(scene, target, *, max_spp, chunk_spp=8, seed=1, device=0, mask=None, renderer=None):
+def render_to_noise(scene, target, *, max_spp, chunk_spp=8, seed=1, device=0, mask=None, renderer=None, halves=False):
     """Renders until noise_estimate says the film is good enough, or until max_spp samples per element (even: both halves keep equal counts).  Two
     film sets: pair i renders the samples [2 i c, (2 i + 1) c) into A and [(2 i + 1) c, (2 i + 2) c) into B, c = chunk_spp (the last pair is
     shortened to what max_spp leaves); the RNG counter is (pixel, sample, stream), so A + B is the film one render of the same samples gives, up
     to the order of its additions.  After every pair one noise_estimate of A against B (on the device nothing but its record is downloaded);
     the loop stops when it is <= target.  `renderer(begin, end, seed) -> (value, weight, light)` (torch tensors, or numpy arrays for a CPU
     renderer) stands in for the HIP path in tests, as shard_renderer does in render_distributed.
-    Returns ((value, weight, light) merged: A += B where the films are, samples per element, [(spp, estimate), ...] one entry per pair)."""
+    Returns ((value, weight, light) merged: A += B where the films are, samples per element, [(spp, estimate), ...] one entry per pair); with
+    halves=True a fourth element, (A, B): copies of the two half-film sets as they stood before the merge, each of samples // 2 samples per element —
+    what denoise() filters."""
     max_spp, c = int(max_spp), max(1, int(chunk_spp))
     if max_spp < 2 or max_spp % 2:
         raise ValueError(f"render_to_noise: an even max_spp >= 2 expected (two halves of equal size), got {max_spp}")
@@ -120,9 +144,10 @@ def render_to_noise(scene, target, *, max_spp, chunk_spp=8, seed=1, device=0, ma
         history.append((done, noise_estimate(scene, a, b, done // 2, mask=mask)))
         if history[-1][1] <= target:
             break
+    kept = tuple(tuple(t.copy() if isinstance(t, np.ndarray) else t.clone() for t in half) for half in (a, b)) if halves else None
     for t, u in zip(a, b):
         t += u
-    return a, done, history
+    return (a, done, history, kept) if halves else (a, done, history)
 
 
 def render(scene, spp, seed=1, device=0, sample_begin=0):
