@@ -945,6 +945,15 @@ class Scene:
         _check(load_library().wtgpu_test_profile_counters(self._h, out, n))
         return [int(v) for v in out]
 
+    def pass_c_tiers(self):
+        """Test hook: what pass C in tiers (WTGPU_PASS_C_TIERS=1; kernels_fsd.hip) counted since the counters were reset — the walks settled by
+        the prep / wide / hard kernel, the pass-C walks, the rounds that had a pass-C queue, those whose queue was no multiple of 8 / shorter
+        than 8, and the lengths of the first queues (wtgpu_kernels.h: kPassCTierSlot ...)."""
+        p = self.profile_counters(224)
+        rounds = p[164]
+        return {"prep": p[160], "wide": p[161], "hard": p[162], "walks": p[163], "rounds": rounds, "rounds_not_multiple_of_8": p[165],
+                "rounds_shorter_than_8": p[166], "queue_lengths": p[168:168 + min(rounds, 56)]}
+
     def connect_class_items(self, slice=0, max_items=1 << 22):
         """Test hook (wtgpu_test_hooks.h): what the last batch connected by k_connect_class on state slice `slice` left behind — (start of every
         class in the flattened item space, samples per class, key per class), all in the device's class order, and the samples in that order."""

@@ -255,4 +255,365 @@ WT_D void interact_c_body(const launch_args_t& a, int in) {
 __global__ void __launch_bounds__(64, WTGPU_LB_INTERACT_C) k_interact_c(launch_args_t a, int in) { interact_c_body<64>(a, in); }
 __global__ void __launch_bounds__(WTGPU_HARD_BLOCK) k_interact_c_hard(launch_args_t a, int in) { interact_c_body<WTGPU_HARD_BLOCK>(a, in); }
 
+// ---- Pass C in TIERS (WTGPU_PASS_C_TIERS=1, the default; the two kernels above are the A/B reference) -------------------------------------------
+// interact_c_body runs three parts of very different width on one wavefront per walk: the power sum (lane = triangle of the list: 10-20 lanes),
+// the tries (64 lanes, of which every try behind the first accepted one is wasted — most apertures accept within a handful) and the commit
+// (ONE lane: 57 + 86 record words, beam transform, roulette) — 13 of 64 lanes per vector instruction on the headline workload.  Here each part
+// has the lane shape that fits it:
+//   k_interact_c_prep        8 lanes per walk, 8 walks per wavefront (the shape of k_path_fsd): power sum, recp_I, tries 0 .. 7
+//   k_interact_c_wide        one wavefront per walk that prep did not settle: tries 8 .. easy_tries, 64 per step
+//   k_interact_c_hard_tries  four wavefronts per walk that outlasts easy_tries
+//   k_interact_c_commit      lane = walk (the shape of pass B): bdpt_walk_step with the outcome
+// A try's draws depend on its index only and the lowest accepted try wins in every tier, so the accepted try is the one interact_c_body finds;
+// recp_I is the same sum in the same tree (below); the commit rebuilds the same fsd_defer_t.  Per walk nothing differs, only the order of the
+// next round's queue and of the film's atomic adds.
+//
+// The power sum, bit for bit: interact_c_body holds triangle j in lane j (0 beyond the list) and reduces by xor 32, 16, 8, 4, 2, 1.  f64 addition
+// is commutative, so after the first three steps lane s < 8 holds ((v[s] + v[s+32]) + (v[s+16] + v[s+48])) + ((v[s+8] + v[s+40]) + (v[s+24] + v[s+56])).
+// Group lane s evaluates exactly those eight triangles, t_k = v[s + 8k], adds them in that order, and the group finishes with xor 4, 2, 1.
+//
+// THIN ROUNDS.  Groups pay where walks outnumber the wavefronts: a group's lane sums ceil(ntris / 8) triangles one after the other, and the tiers
+// run one after the other.  From the fourth round or so a batch's pass-C queue holds fewer walks than the grid has wavefronts x 8, the pass is
+// bound by the LATENCY of its longest walk, and one wavefront per walk is the shorter way (measured, one stream, us per round of prep + wide
+// against k_interact_c: 1365 / 3103 in round 0, 567 / 469 in round 3, 240 / 100 in rounds 9-14).  A round whose queue holds at most `thin_below`
+// walks (the host: WTGPU_PASS_C_THIN, 8, x the grid's wavefronts) therefore runs interact_c_tries_body<64, true> right here: power sum with a lane per
+// triangle, tries from 0 with 64 lanes, outcome to the commit queue — interact_c_body without its commit; the wide queue stays empty.
+template <int BLOCK, bool THIN>
+WT_D void interact_c_tries_body(const launch_args_t& a, uint32_t easy_tries);
+__global__ void __launch_bounds__(64, WTGPU_LB_INTERACT_C) k_interact_c_prep(launch_args_t a, uint32_t thin_below, uint32_t easy_tries) {
+    uint32_t* ctl = a.st.ctl;
+    const uint32_t n = ctl[CTL_INTC_COUNT];
+    const int lane = threadIdx.x & 63;
+    const uint32_t s = (uint32_t)lane & (kPrepTries - 1u), group = (uint32_t)lane / kPrepTries;
+    const fsd_pool_t pool = fsd_pool_of(a);
+    uint32_t* wide_queue = pass_c_wide_queue(a);
+    uint32_t* commit_queue = pass_c_commit_queue(a);
+    unsigned long long* prof = a.st.counters + kNumCounters;
+    unsigned long long settled = 0;
+    if (a.count_stats && blockIdx.x == 0 && threadIdx.x == 0 && n > 0) {   // the round's pass-C queue, for the tests of the tiers
+        atomicAdd(prof + kPassCWalksSlot, (unsigned long long)n);
+        const unsigned long long r = atomicAdd(prof + kPassCRoundsSlot, 1ull);
+        if (n % kPrepTries) atomicAdd(prof + kPassCRoundsSlot + 1, 1ull);
+        if (n < kPrepTries) atomicAdd(prof + kPassCRoundsSlot + 2, 1ull);
+        if (r < kPassCQueueSlots) prof[kPassCQueueSlot + r] = n;
+    }
+    if (n <= thin_below) {   // (uniform over the grid)
+        interact_c_tries_body<64, true>(a, easy_tries);
+        return;
+    }
+    for (;;) {
+        const long long pl0 = a.profile == 3 ? clock64() : 0;
+        const uint32_t base0 = wave_grab0(ctl + CTL_INTC_HEAD, 64u / kPrepTries);   // eight walks per wavefront, eight lanes each
+        if (base0 >= n) break;
+        const uint32_t item = base0 + group;
+        const bool have = item < n;
+        uint32_t w = 0, slot = 0, base = 0, max_tries = 0;
+        fsd_aperture_t ap;
+        memset(&ap, 0, sizeof(ap));
+        sampler_t ss = make_sampler(a.seed, 0, 0, 0);
+        bool marker = false;
+        double flux = 0.0;
+        if (have) {
+            w = a.st.intc_queue[item];
+            uint32_t i, stream;
+            walk_ident(a, w, i, stream);
+            const uint64_t sample_id = sample_id_of(a, i);
+            const uint32_t rng_draws = a.st.walks[(size_t)w * a.st.walk_words + WT_WALK_WORD(rng_draws)];
+            slot = WT_TRAV_U(a, w, by);   // left by pass B
+            ap = pool.hdr[slot];
+            ss = make_sampler(a.seed, sample_id, stream, 0);
+            base = fsd_tries_base(make_sampler(a.seed, sample_id, stream, rng_draws));
+            // ---- intercepted power of the whole region (same z-slab, cone and facing as the reference's list-based sum)
+            const uint32_t tr_tuid = WT_TRAV_U(a, w, tuid);
+            marker = is_region_marker(tr_tuid);
+            if (marker) {   // the region overflowed the bounded list: summed over all of it by k_flux_split / k_flux_tasks
+                flux = a.st.facc[w];
+            } else {
+                const walk_trace_in_t wk = walk_load_trace_in(a.st.walks, a.st.walk_words, w);   // (the lanes of a group read the same words)
+                const cone_t benv = wk.env;   // the beam's own envelope (not offset for tracing)
+                const float tr_dist = WT_TRAV_F(a, w, dist), tr_depth = WT_TRAV_F(a, w, region_depth);
+                const uint32_t tr_ntris = WT_TRAV_U(a, w, ntris);
+                const bool tr_front = WT_TRAV_U(a, w, front_face) != 0;
+                const range_t izr{tr_dist, tr_dist + tr_depth};
+                const vec2 axes = cone_axes(benv, tr_dist);
+                const vec2 sigma{axes.x / kBeamEnvelope, axes.y / kBeamEnvelope};
+                const frame_t bframe = cone_frame(benv);
+                const uint32_t* tl = a.st.tris + (size_t)w * kTriListWords;
+                double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0, t4 = 0.0, t5 = 0.0, t6 = 0.0, t7 = 0.0;   // t_k: triangle s + 8 k of the list
+#pragma unroll 1
+                for (uint32_t k = 0; s + kPrepTries * k < tr_ntris && k < 8u; ++k) {
+                    const double f = (double)region_triangle_flux(a.sc, bframe, benv, izr, sigma, tl[s + kPrepTries * k], tr_front);
+                    t0 = k == 0u ? f : t0;
+                    t1 = k == 1u ? f : t1;
+                    t2 = k == 2u ? f : t2;
+                    t3 = k == 3u ? f : t3;
+                    t4 = k == 4u ? f : t4;
+                    t5 = k == 5u ? f : t5;
+                    t6 = k == 6u ? f : t6;
+                    t7 = k == 7u ? f : t7;
+                }
+                flux = ((t0 + t4) + (t2 + t6)) + ((t1 + t5) + (t3 + t7));
+            }
+        }
+        // (every lane of the wavefront: the groups that hold a region marker, or no walk, add their own value to itself — and drop the result)
+        double fsum = flux;
+#pragma unroll
+        for (int off = (int)kPrepTries / 2; off > 0; off >>= 1) fsum += __shfl_xor(fsum, off, 64);
+        if (!marker) flux = fsum;
+        if (have) {
+            const float I = (float)(1.0 - flux);
+            ap.recp_I = I > 0.f ? 1.f / I : 0.f;
+            if (s == 0u) pool.hdr[slot] = ap;
+            max_tries = fsd_max_tries(ap);
+        }
+        const long long pc0 = a.profile == 3 ? clock64() : 0;
+        // ---- tries 0 .. 7, one per lane of the group; the segments come from the pool (the L1 serves the group's repeats)
+        fsd_try_t r{{0.f, 0.f}, 0.f, 0u};
+        if (have && s < max_tries) r = fsd_try(a.sc, ap, fsd_edges_ref_t{pool.edges + (size_t)ap.edge_offset, 1}, sampler_at(ss, base + s * kFsdDrawsPerTry));
+        const uint32_t am = (uint32_t)(__ballot(r.accept != 0) >> (group * kPrepTries)) & ((1u << kPrepTries) - 1u);   // the group's accepted tries
+        const bool acc = am != 0u;
+        const uint32_t t_acc = acc ? (uint32_t)__ffs((int)am) - 1u : 0u;
+        const int wl = (int)(group * kPrepTries + t_acc);   // (within the group; without an accepted try: its first lane, whose zeros nobody reads)
+        const float rx = __shfl(r.x.x, wl, 64), ry = __shfl(r.x.y, wl, 64), rf = __shfl(r.f, wl, 64);
+        // ---- accepted, or no try left (a dead aperture, max_tries = 0): the outcome for the commit; else the wide kernel goes on at try 8
+        const bool lead = have && s == 0u;
+        const bool settle = lead && (acc || max_tries <= kPrepTries);
+        if (settle) {
+            uint32_t* o = pass_c_outcome(a, w);
+            o[0] = acc ? (kOutcomeAccepted | t_acc) : 0u;
+            o[1] = __float_as_uint(rx);
+            o[2] = __float_as_uint(ry);
+            o[3] = __float_as_uint(rf);
+            ++settled;
+        }
+        wave_append(commit_queue, ctl + CTL_PCC_COUNT, settle, w);
+        wave_append(wide_queue, ctl + CTL_PCW_COUNT, lead && !settle, w);
+        if (a.profile == 3) {   // WTGPU_PROFILE=3: pass-C cost by aperture size (bin = floor(log2(segments))); a wavefront's clocks, shared out among its walks
+            const long long pt = clock64();
+            const long long ng = (long long)__popcll(__ballot(lead));
+            if (lead) {
+                const int bin = 31 - __clz((int)max(ap.n_edges, 1u));
+                atomicAdd(prof + 8 + bin, 1ull);
+                atomicAdd(prof + 24 + bin, (unsigned long long)(acc ? t_acc + 1u : min(max_tries, kPrepTries)));
+                atomicAdd(prof + 112 + bin, (unsigned long long)((pc0 - pl0) / ng));
+                atomicAdd(prof + 40 + bin, (unsigned long long)((pt - pc0) / ng));
+            }
+        }
+    }
+    if (a.count_stats) flush_counter(a, kNumCounters + kPassCTierSlot, settled);
+}
+
+// Tries only, for the walks whose first kPrepTries tries were rejected: BLOCK = 64 from try kPrepTries to easy_tries (segments staged in LDS, as in
+// interact_c_body), BLOCK = 256 from there to the end.  The aperture's header holds recp_I since k_interact_c_prep.  easy_tries (>= kPrepTries):
+// kEasyTries, or what the tests set to drive walks into every tier (WTGPU_PASS_C_EASY_TRIES) — results do not depend on it.
+// THIN (BLOCK = 64, from k_interact_c_prep): the walks of pass C's own queue — the power sum first, then the tries from 0.
+template <int BLOCK, bool THIN>
+WT_D void interact_c_tries_body(const launch_args_t& a, uint32_t easy_tries) {
+    constexpr bool HARD = BLOCK > 64;
+    static_assert(!(HARD && THIN), "thin rounds: one wavefront per walk");
+    __shared__ uint32_t s_item;
+    __shared__ uint32_t s_tmin;
+    __shared__ float s_res[3];
+    __shared__ fsd_edge_t s_seg[kStageSegs];   // the walk's aperture segments (7 KB; larger apertures are read from the pool)
+    uint32_t* ctl = a.st.ctl;
+    const uint32_t n = ctl[HARD ? CTL_INTD_COUNT : (THIN ? CTL_INTC_COUNT : CTL_PCW_COUNT)];
+    const uint32_t* queue_in = HARD ? a.st.intd_queue : (THIN ? a.st.intc_queue : pass_c_wide_queue(a));
+    uint32_t* commit_queue = pass_c_commit_queue(a);
+    unsigned long long* prof = a.st.counters + kNumCounters;
+    const int tid = threadIdx.x;
+    const fsd_pool_t pool = fsd_pool_of(a);
+    unsigned long long settled = 0, settled_early = 0;
+    for (;;) {
+        uint32_t item = 0;
+        if (HARD) {   // four wavefronts: through the shared word, between real barriers — the first one BEFORE the branch on the thread index
+            __syncthreads();   // (wtgpu_kernels.h: wave_grab0 says why; it also keeps the last iteration's readers ahead of the write)
+            if (tid == 0) s_item = atomicAdd(ctl + CTL_INTD_HEAD, 1u);
+            __syncthreads();
+            item = s_item;
+        } else
+            item = wave_grab_item(ctl + (THIN ? CTL_INTC_HEAD : CTL_PCW_HEAD));
+        if (item >= n) break;
+        const uint32_t w = queue_in[item];
+        uint32_t i, stream;
+        walk_ident(a, w, i, stream);
+        const uint64_t sample_id = sample_id_of(a, i);
+        const uint32_t rng_draws = a.st.walks[(size_t)w * a.st.walk_words + WT_WALK_WORD(rng_draws)];
+        const uint32_t slot = WT_TRAV_U(a, w, by);   // left by pass B
+        fsd_aperture_t ap = pool.hdr[slot];
+        const fsd_edges_ref_t ed = fsd_pool_edges(pool, slot);
+        const long long pc0 = a.profile == 3 ? clock64() : 0;
+        if (THIN) {
+            // ---- intercepted power of the whole region, as in interact_c_body: lane = triangle of the (complete) list, wave reduction
+            const walk_trace_in_t wk = walk_load_trace_in(a.st.walks, a.st.walk_words, w);   // uniform address: broadcast
+            const cone_t benv = wk.env;   // the beam's own envelope (not offset for tracing)
+            const float tr_dist = WT_TRAV_F(a, w, dist), tr_depth = WT_TRAV_F(a, w, region_depth);
+            const uint32_t tr_tuid = WT_TRAV_U(a, w, tuid), tr_ntris = WT_TRAV_U(a, w, ntris);
+            const bool tr_front = WT_TRAV_U(a, w, front_face) != 0;
+            const range_t izr{tr_dist, tr_dist + tr_depth};
+            const vec2 axes = cone_axes(benv, tr_dist);
+            const vec2 sigma{axes.x / kBeamEnvelope, axes.y / kBeamEnvelope};
+            double flux;
+            if (is_region_marker(tr_tuid)) {   // the region overflowed the bounded list: summed over all of it by k_flux_split / k_flux_tasks
+                flux = a.st.facc[w];
+            } else {
+                const uint32_t* tl = a.st.tris + (size_t)w * kTriListWords;
+                flux = (uint32_t)tid < tr_ntris ? (double)region_triangle_flux(a.sc, cone_frame(benv), benv, izr, sigma, tl[tid], tr_front) : 0.0;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) flux += __shfl_xor(flux, off, 64);
+            }
+            const float I = (float)(1.0 - flux);
+            ap.recp_I = I > 0.f ? 1.f / I : 0.f;
+            if (tid == 0) pool.hdr[slot] = ap;
+        }
+        const sampler_t ss = make_sampler(a.seed, sample_id, stream, 0);
+        const uint32_t base = fsd_tries_base(make_sampler(a.seed, sample_id, stream, rng_draws));
+        const uint32_t max_tries = fsd_max_tries(ap);
+        const uint32_t t_begin = HARD ? easy_tries : (THIN ? 0u : kPrepTries), t_end = HARD ? max_tries : (max_tries < easy_tries ? max_tries : easy_tries);
+        bool acc = false;
+        uint32_t t_acc = 0;
+        float rx = 0.f, ry = 0.f, rf = 0.f;
+        auto run_tries = [&](const fsd_edges_ref_t& edr) {
+            for (uint32_t t0 = t_begin; t0 < t_end && !acc; t0 += BLOCK) {
+                const uint32_t t = t0 + (uint32_t)tid;
+                fsd_try_t r{{0.f, 0.f}, 0.f, 0u};
+                if (t < t_end) r = fsd_try(a.sc, ap, edr, sampler_at(ss, base + t * kFsdDrawsPerTry));
+                if (!HARD) {
+                    const unsigned long long am = __ballot(r.accept != 0);
+                    if (am) {
+                        const int wl = __ffsll((long long)am) - 1;
+                        rx = __shfl(r.x.x, wl, 64);
+                        ry = __shfl(r.x.y, wl, 64);
+                        rf = __shfl(r.f, wl, 64);
+                        t_acc = t0 + (uint32_t)wl;
+                        acc = true;
+                    }
+                } else {   // the lowest accepted try of the block
+                    if (tid == 0) s_tmin = 0xFFFFFFFFu;
+                    __syncthreads();
+                    if (r.accept) atomicMin(&s_tmin, t);
+                    __syncthreads();
+                    const uint32_t tm = s_tmin;
+                    if (tm != 0xFFFFFFFFu) {
+                        if (t == tm) {
+                            s_res[0] = r.x.x;
+                            s_res[1] = r.x.y;
+                            s_res[2] = r.f;
+                        }
+                        __syncthreads();
+                        rx = s_res[0];
+                        ry = s_res[1];
+                        rf = s_res[2];
+                        t_acc = tm;
+                        acc = true;
+                    }
+                    __syncthreads();
+                }
+            }
+        };
+        if (t_begin >= t_end) {   // (nothing to try here: a boundary at kPrepTries)
+        } else if (ap.n_edges <= kStageSegs) {
+            __syncthreads();   // (the previous walk's tries are done with the buffer)
+            for (uint32_t k = (uint32_t)tid; k < ap.n_edges; k += BLOCK) s_seg[k] = ed.p[k];
+            __syncthreads();
+            run_tries(fsd_edges_ref_t{s_seg, 1});
+        } else
+            run_tries(ed);
+        if (a.profile == 3 && tid == 0) {   // WTGPU_PROFILE=3: the wide and hard tries by aperture size
+            const int bin = 31 - __clz((int)max(ap.n_edges, 1u));
+            atomicAdd(prof + (THIN ? 8 : 144) + bin, 1ull);
+            atomicAdd(prof + 24 + bin, (unsigned long long)(acc ? t_acc + 1u - t_begin : t_end - t_begin));
+            atomicAdd(prof + (THIN ? 40 : 128) + bin, (unsigned long long)(clock64() - pc0));
+        }
+        if (tid == 0) {
+            if (!HARD && !acc && t_end < max_tries) {   // none of the first easy_tries tries accepted: four wavefronts take over
+                a.st.intd_queue[atomicAdd(ctl + CTL_INTD_COUNT, 1u)] = w;
+            } else {
+                uint32_t* o = pass_c_outcome(a, w);
+                o[0] = acc ? (kOutcomeAccepted | t_acc) : 0u;
+                o[1] = __float_as_uint(rx);
+                o[2] = __float_as_uint(ry);
+                o[3] = __float_as_uint(rf);
+                commit_queue[atomicAdd(ctl + CTL_PCC_COUNT, 1u)] = w;
+                if (THIN && (acc ? t_acc < kPrepTries : max_tries <= kPrepTries))   // (what the groups of eight would have settled: counted as theirs)
+                    ++settled_early;
+                else
+                    ++settled;
+            }
+        }
+    }
+    if (a.count_stats && tid == 0 && settled) atomicAdd(prof + kPassCTierSlot + (HARD ? 2 : 1), settled);
+    if (THIN && a.count_stats && tid == 0 && settled_early) atomicAdd(prof + kPassCTierSlot, settled_early);
+}
+__global__ void __launch_bounds__(64, WTGPU_LB_INTERACT_C) k_interact_c_wide(launch_args_t a, uint32_t easy_tries) { interact_c_tries_body<64, false>(a, easy_tries); }
+__global__ void __launch_bounds__(WTGPU_HARD_BLOCK) k_interact_c_hard_tries(launch_args_t a, uint32_t easy_tries) { interact_c_tries_body<WTGPU_HARD_BLOCK, false>(a, easy_tries); }
+
+// The commit, lane = walk of the commit queue (the shape of pass B, interact_body<1>): the fsd_defer_t interact_c_body's lane 0 builds, from the
+// outcome record, then bdpt_walk_step with it — vertex append, beam transform, Russian roulette — and the walk goes to the next round's queue.
+// (No traversal stack: with known_no_primary set the step makes no BVH query, as in pass B.)
+__global__ void __launch_bounds__(kBlock, WTGPU_LB_INTERACT_B) k_interact_c_commit(launch_args_t a, int in) {
+    uint32_t* ctl = a.st.ctl;
+    const uint32_t n = ctl[CTL_PCC_COUNT];
+    const uint32_t* commit_queue = pass_c_commit_queue(a);
+    bdpt_counters_t ctr;
+    memset(&ctr, 0, sizeof(ctr));
+    const fsd_pool_t pool = fsd_pool_of(a);
+    for (;;) {
+        const uint32_t base0 = wave_grab(ctl + CTL_PCC_HEAD);
+        if (base0 >= n) break;
+        const uint32_t qi = base0 + (threadIdx.x & 63);
+        const bool valid = qi < n;
+        bool cont = false;
+        uint32_t w = 0;
+        const long long pm0 = a.profile == 3 ? clock64() : 0;
+        int bin = 0;
+        if (valid) {
+            w = commit_queue[qi];
+            uint32_t i, stream;
+            walk_ident(a, w, i, stream);
+            const uint64_t sample_id = sample_id_of(a, i);
+            walk_t wk;
+            soa_load(a.st.walks, a.st.walk_words, w, wk);
+            trav_result_t tr;
+            soa_load(a.st.trav, kTravWords, w, tr);
+            const uint32_t slot = __float_as_uint(tr.by);   // left by pass B
+            const fsd_aperture_t ap = pool.hdr[slot];   // (recp_I: k_interact_c_prep's)
+            const uint32_t* o = pass_c_outcome(a, w);
+            const uint32_t o0 = o[0];
+            const bool acc = (o0 & kOutcomeAccepted) != 0u;
+            const uint32_t t_acc = o0 & ~kOutcomeAccepted;
+            const float rx = __uint_as_float(o[1]), ry = __uint_as_float(o[2]), rf = __uint_as_float(o[3]);
+            const uint32_t base = fsd_tries_base(make_sampler(a.seed, sample_id, stream, wk.rng_draws));
+            const uint32_t max_tries = fsd_max_tries(ap);
+            bin = 31 - __clz((int)max(ap.n_edges, 1u));
+            fsd_defer_t defer;
+            defer.defer_sampling = defer.to_sampling_pass = 0;
+            defer.have_aperture = 1;
+            defer.split_no_primary = 0;
+            defer.known_no_primary = 1;
+            defer.no_primary = 0;
+            defer.has_gather = defer.gather_n_edges = defer.gather_edge_overflow = 0;
+            defer.gather_flux = 0.f;
+            defer.gather_edges = nullptr;
+            defer.pending = 0;
+            defer.resolved = 1;
+            defer.slot = slot;
+            defer.base = base;
+            defer.next_try = 0;
+            defer.fs = fsd_finalize(ap, acc, vec2{rx, ry}, rf);
+            defer.end_draws = fsd_draws_after(base, acc ? t_acc : max_tries - 1u);
+            const uint_list_t tris{a.st.tris + (size_t)w * kTriListWords, 1u, kMaxConeTris};
+            const vertex_store_t vs = walk_vertices(a, w);
+            cont = bdpt_walk_step<2>(a.sc, wk, tr, tris, vs, pool, a.seed, sample_id, stream, &ctr, nullptr, &defer);
+            wk.active = cont ? 1u : 0u;
+            soa_store(a.st.walks, a.st.walk_words, w, wk);
+        }
+        if (a.profile == 3) {   // (a wavefront's clocks, shared out among its walks)
+            const long long dt = clock64() - pm0, nv = (long long)__popcll(__ballot(valid));
+            if (valid) atomicAdd(a.st.counters + kNumCounters + 96 + bin, (unsigned long long)(dt / nv));
+        }
+        queue_append(a, ctl, 1 - in, cont, w);
+    }
+    if (a.count_stats) flush_counters(a.st.counters, ctr);
+}
+
 }   // namespace wtk

@@ -55,6 +55,7 @@ WT_D void trace_round_begin(uint32_t* ctl, int in, uint32_t round, uint32_t n) {
     ctl[CTL_EPOOL_COUNT] = 0;
     ctl[CTL_INTD_COUNT] = 0;
     ctl[CTL_INTD_HEAD] = 0;
+    ctl[CTL_PCW_COUNT] = ctl[CTL_PCW_HEAD] = ctl[CTL_PCC_COUNT] = ctl[CTL_PCC_HEAD] = 0;   // pass C in tiers: its wide and commit queues
 #pragma unroll
     for (uint32_t c = 0; c < kNumWalkClasses; ++c) ctl[CTL_CLS_COUNT0 + c] = ctl[CTL_CLS_HEAD0 + c] = 0;   // the class queues of this round's pass A
     // plt_path: this round's wedge pool and the queue it fills for the next round's k_path_fsd; this round's k_path_fsd / k_path_nee heads

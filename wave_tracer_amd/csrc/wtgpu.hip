@@ -202,8 +202,18 @@ struct batch_launcher_t {
             HP_LAUNCH(k_flux_split, dim3(std::max<uint32_t>(1u, gh / 4u)), dim3(64), 0, st_, a);
             HP_LAUNCH(k_flux_tasks, dim3(std::max<uint32_t>(1u, gh * grid_mul_flux)), dim3(64), 0, st_, a);
             rec(r, st_);
-            HP_LAUNCH(k_interact_c, dim3(std::max<uint32_t>(1u, gh / grid_div_c)), dim3(64), 0, st_, a, in);
-            HP_LAUNCH(k_interact_c_hard, dim3(std::max<uint32_t>(1u, gh / K.grid_div_hard)), dim3(WTGPU_HARD_BLOCK), 0, st_, a, in);
+            if (K.pass_c_tiers) {   // pass C in three lane shapes (kernels_fsd.hip): groups of eight lanes, then whole wavefronts for the tries that are left, then a lane per walk
+                const uint32_t g_prep = std::max<uint32_t>(1u, gh / grid_div_c);
+                // (a queue of at most WTGPU_PASS_C_THIN walks per wavefront of the grid: one wavefront per walk inside k_interact_c_prep, the thin rounds' shorter way)
+                const uint32_t thin_below = (uint32_t)std::min<uint64_t>((uint64_t)K.pass_c_thin * g_prep, 0xFFFFFFFFull);
+                HP_LAUNCH(k_interact_c_prep, dim3(g_prep), dim3(64), 0, st_, a, thin_below, K.pass_c_easy_tries);
+                HP_LAUNCH(k_interact_c_wide, dim3(std::max<uint32_t>(1u, gh / grid_div_c)), dim3(64), 0, st_, a, K.pass_c_easy_tries);
+                HP_LAUNCH(k_interact_c_hard_tries, dim3(std::max<uint32_t>(1u, gh / K.grid_div_hard)), dim3(WTGPU_HARD_BLOCK), 0, st_, a, K.pass_c_easy_tries);
+                HP_LAUNCH(k_interact_c_commit, dim3(std::max<uint32_t>(1u, g0 / grid_div_b)), dim3(kBlock), 0, st_, a, in);
+            } else {
+                HP_LAUNCH(k_interact_c, dim3(std::max<uint32_t>(1u, gh / grid_div_c)), dim3(64), 0, st_, a, in);
+                HP_LAUNCH(k_interact_c_hard, dim3(std::max<uint32_t>(1u, gh / K.grid_div_hard)), dim3(WTGPU_HARD_BLOCK), 0, st_, a, in);
+            }
             rec(r, st_);
         }
         r.rounds_launched = r_end;

@@ -61,6 +61,12 @@ int wtgpu_get_counters(wtgpu_scene* s, wtgpu_counters* out) {
         fprintf(stderr, "[wtgpu profile] pass C by aperture size (slice 0): bin=log2(segments) items tries/item kticks/item total-Mticks\n");
         for (int b = 0; b < 16; ++b)
             if (p[8 + b]) fprintf(stderr, "[wtgpu profile]   C %2d %8llu %10.1f %10.1f %10.1f   fetch+load %.1f commit %.1f kticks/item\n", b, p[8 + b], double(p[24 + b]) / p[8 + b], double(p[40 + b]) / p[8 + b] * 1e-3, double(p[40 + b]) * 1e-6, double(p[112 + b]) / p[8 + b] * 1e-3, double(p[96 + b]) / p[8 + b] * 1e-3);
+        if (s->knobs.pass_c_tiers) {   // the tiered form: the lines above hold prep's sum (fetch+load) and prep's tries (kticks/item), tries/item over all tiers
+            fprintf(stderr, "[wtgpu profile] pass C in tiers (slice 0): walks settled by prep %llu, wide %llu, hard %llu; wide + hard tries by aperture size: bin items kticks/item total-Mticks\n",
+                    p[kPassCTierSlot], p[kPassCTierSlot + 1], p[kPassCTierSlot + 2]);
+            for (int b = 0; b < 16; ++b)
+                if (p[144 + b]) fprintf(stderr, "[wtgpu profile]   W %2d %8llu %10.1f %10.1f\n", b, p[144 + b], double(p[128 + b]) / p[144 + b] * 1e-3, double(p[128 + b]) * 1e-6);
+        }
         fprintf(stderr, "[wtgpu profile] pass B by gathered scene edges: bin items kticks/item total-Mticks\n");
         for (int b = 0; b < 16; ++b)
             if (p[56 + b]) fprintf(stderr, "[wtgpu profile]   B %2d %8llu %10.1f %10.1f\n", b, p[56 + b], double(p[72 + b]) / p[56 + b] * 1e-3, double(p[72 + b]) * 1e-6);

@@ -5,7 +5,8 @@
 //                       _dielectric / _spm / _any: by material class), k_edges, k_interact_b (pass B), k_light_rounds (a batch's thin last rounds)
 //   kernels_trace.hip   k_trace_refill (body: kernels_trace_refill.h, which k_light_rounds runs too), the staged k_tr_axis / _cone / _policy / _tail,
 //                       k_trace_heavy (+ the per-query kernels of the traversal parity tests, the PMC calibration copy)
-//   kernels_fsd.hip     k_flux_split, k_flux_tasks, k_interact_c, k_interact_c_hard (Fraunhofer interactions: power sums, rejection sampling)
+//   kernels_fsd.hip     k_flux_split, k_flux_tasks, k_interact_c_prep, _wide, _hard_tries, _commit (Fraunhofer interactions: power sums, rejection sampling in
+//                       three lane shapes; k_interact_c, k_interact_c_hard: the one-wavefront-per-walk form, WTGPU_PASS_C_TIERS=0)
 //   kernels_path.hip    k_path_generate, _fsd, _interact, _edges, _interact_b, _nee, _flush (plt_path)
 //   kernels_connect.hip k_connect_enum, _scan, _class / _strat (+ _open), the staged _eval / _shadow / _mis, _splat / _splat_tiled
 //   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
@@ -80,6 +81,7 @@ enum : uint32_t { CTL_STRAT_HEAD_OPEN = 25, CTL_UTD_COUNT0 = 26, CTL_UTD_COUNT1 
                   CTL_TPOL_COUNT0 = 41, CTL_TPOL_COUNT1 = 42, CTL_TPOL_HEAD = 43, CTL_TCONE_COUNT0 = 44, CTL_TCONE_COUNT1 = 45, CTL_TCONE_HEAD = 46,   // the staged trace kernels' queues (trace_stage_t)
                   CTL_CLS_COUNT0 = 33, CTL_CLS_HEAD0 = 37,   // the material-sorted pass A: sizes and dequeue heads of the kNumWalkClasses class queues (k_classify / k_interact_cls)
                   CTL_LIGHT_DONE = 47, CTL_LIGHT_STOP = 48,   // k_light_rounds: whole rounds it ran, the stage the host has to continue the next one from (0: none)
+                  CTL_PCW_COUNT = 49, CTL_PCW_HEAD = 50, CTL_PCC_COUNT = 51, CTL_PCC_HEAD = 52,   // pass C in tiers: the wide queue and the commit queue (k_interact_c_prep's own queue is pass C's: CTL_INTC_*)
                   CTL_WORDS = 56 };   // (CTL_BACK*: see queue_append)   // (CTL_GATHER_*: queue of k_edges)
 constexpr uint32_t kTriListWords = 128;   // per-walk list storage: 64 triangle ids, or (after coop_gather) up to 96 edge ids
 constexpr uint32_t kGatherMarker = 0xFFFFFFFEu;   // trav.tuid of a walk whose interaction region was gathered
@@ -124,7 +126,7 @@ struct device_state_t {
     uint32_t* intb_queue = nullptr;    // walks whose interaction takes the expensive (no primary triangle) path
     uint32_t* gather_queue = nullptr;  // ... of those, the ones whose triangle list overflowed (coop_gather first)
     uint32_t* intc_queue = nullptr;    // ... and the ones that built a Fraunhofer aperture with edges (sampled in pass C)
-    uint32_t* intd_queue = nullptr;    // ... of those, the ones whose rejection sampling outlasts kEasyTries tries (k_interact_c_hard)
+    uint32_t* intd_queue = nullptr;    // ... of those, the ones whose rejection sampling outlasts kEasyTries tries (k_interact_c_hard); behind it, same allocation: pass_c_wide_queue, pass_c_commit_queue
     uint2* ftasks = nullptr;           // (walk, subtree) tasks of the intercepted-power sums of overflowed regions (k_flux_split / k_flux_tasks)
     uint32_t ftask_cap = 0;
     double* facc = nullptr;            // [2cap] their accumulators
@@ -189,7 +191,7 @@ struct trace_stage_t {
 };
 constexpr size_t kStageWords = sizeof(trace_stage_t) / 4;
 constexpr size_t kNumCounters = sizeof(bdpt_counters_t) / sizeof(unsigned long long);
-constexpr size_t kProfSlots = 128;   // WTGPU_PROFILE scratch counters behind the public ones
+constexpr size_t kProfSlots = 224;   // WTGPU_PROFILE scratch counters behind the public ones (from kPassCTierSlot on: the tier counts of pass C, kept whenever statistics are)
 constexpr size_t kDroppedSlot = kNumCounters + kProfSlots;   // ... and behind those: children a full cooperative traversal stack could not hold (wt/coop.h)
 
 
@@ -216,6 +218,23 @@ struct launch_args_t {
 WT_D uint32_t* trace_stage_words(const launch_args_t& a) { return a.st.trav + kTravWords * 2 * (size_t)a.st.cap; }   // [2 cap][kStageWords]
 WT_D uint32_t* trace_pol_queue(const launch_args_t& a) { return a.st.heavy_queue + 2 * (size_t)a.st.cap; }
 WT_D uint32_t* trace_cone_queue(const launch_args_t& a) { return a.st.heavy_queue + 4 * (size_t)a.st.cap; }
+// ---- pass C in tiers (kernels_fsd.hip: k_interact_c_prep -> k_interact_c_wide -> k_interact_c_hard_tries -> k_interact_c_commit) ----------------------
+// Two more [2 cap] queues behind the hard queue (same allocation, like the two above): the walks whose first kPrepTries tries were all rejected, and
+// the walks whose outcome is known and waits for k_interact_c_commit.
+WT_D uint32_t* pass_c_wide_queue(const launch_args_t& a) { return a.st.intd_queue + 2 * (size_t)a.st.cap; }
+WT_D uint32_t* pass_c_commit_queue(const launch_args_t& a) { return a.st.intd_queue + 4 * (size_t)a.st.cap; }
+// The OUTCOME of a walk's rejection sampling, from the kernel that found it to k_interact_c_commit: the first four words of the walk's
+// triangle-list slot (st.tris) — [0] kOutcomeAccepted | index of the accepted try (0: every try was rejected), [1] x.x, [2] x.y, [3] f of that try.
+// The slot is dead at that point: its last reader in a round is the intercepted-power sum of k_interact_c_prep (a wavefront writes a walk's
+// outcome after the group's sum has consumed every loaded triangle id); the try kernels read the aperture pool only; the commit re-enters
+// bdpt_walk_step with known_no_primary, have_aperture and resolved set, which skips the list scan, the edge gathering and the power sum — the
+// step's three readers of the list; and the next round's trace kernels rewrite the list before anything reads it again.
+constexpr uint32_t kOutcomeAccepted = 0x80000000u;   // (a try index is below kFsdMaxEdges x 1024 = 2^22)
+WT_D uint32_t* pass_c_outcome(const launch_args_t& a, uint32_t w) { return a.st.tris + (size_t)w * kTriListWords; }
+constexpr uint32_t kPrepTries = 8;   // tries of k_interact_c_prep: one per lane of a walk's group of eight
+// statistics of the tiers, behind the WTGPU_PROFILE slots proper (index into st.counters + kNumCounters): walks settled by the prep / wide / hard
+// kernel, pass-C walks, rounds with a pass-C queue / whose queue is no multiple of kPrepTries / is shorter, the lengths of the first such queues
+constexpr size_t kPassCTierSlot = 160, kPassCWalksSlot = 163, kPassCRoundsSlot = 164, kPassCQueueSlot = 168, kPassCQueueSlots = kProfSlots - kPassCQueueSlot;
 // (block size as a constant: blockDim would pull 256 bytes of hidden kernel arguments into the kernel-argument segment)
 WT_D void lds_stack(stack_entry_t* lds, stack_entry_t* spill, stack_ref_t& s, uint32_t block = kBlock) {
     s = make_stack_ref(lds + threadIdx.x, block, kLdsStack + kSpillStack, kLdsStack, spill);
@@ -394,6 +413,7 @@ WT_D void ctl_reset_batch(uint32_t* ctl) {
     ctl[CTL_INTB_COUNT] = ctl[CTL_INTB_HEAD] = ctl[CTL_GATHER_COUNT] = ctl[CTL_GATHER_HEAD] = ctl[CTL_INTC_COUNT] = ctl[CTL_INTC_HEAD] = 0;
     ctl[CTL_FTASK_COUNT] = ctl[CTL_FTASK_HEAD] = ctl[CTL_FSPLIT_HEAD] = ctl[CTL_EPOOL_COUNT] = ctl[CTL_FSD_ECOUNTER] = 0;
     ctl[CTL_INTD_COUNT] = ctl[CTL_INTD_HEAD] = 0;
+    ctl[CTL_PCW_COUNT] = ctl[CTL_PCW_HEAD] = ctl[CTL_PCC_COUNT] = ctl[CTL_PCC_HEAD] = 0;
 }
 // pass A of a round begins (one lane of the grid): the trace queues are ready for the NEXT round's k_trace
 WT_D void interact_round_begin(uint32_t* ctl) {
@@ -529,6 +549,10 @@ __global__ void k_flux_split(launch_args_t a);
 __global__ void k_flux_tasks(launch_args_t a);
 __global__ void k_interact_c(launch_args_t a, int in);
 __global__ void k_interact_c_hard(launch_args_t a, int in);
+__global__ void k_interact_c_prep(launch_args_t a, uint32_t thin_below, uint32_t easy_tries);
+__global__ void k_interact_c_wide(launch_args_t a, uint32_t easy_tries);
+__global__ void k_interact_c_hard_tries(launch_args_t a, uint32_t easy_tries);
+__global__ void k_interact_c_commit(launch_args_t a, int in);
 __global__ void k_path_generate(launch_args_t a);
 __global__ void k_path_fsd(launch_args_t a, const path_state_t* __restrict__ ps, uint32_t round);
 __global__ void k_path_edges(launch_args_t a, const path_state_t* __restrict__ ps);

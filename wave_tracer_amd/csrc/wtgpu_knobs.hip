@@ -59,6 +59,9 @@ const knob_t kKnobs[] = {
     {"WTGPU_COOP_IO", K(coop_io), KNOB_U32, 0, 0, kU32, "1: pass A with wave-cooperative record transfers (k_interact_coop)"},
     {"WTGPU_STAGED_CONNECT", K(staged_connect), KNOB_U32, 0, 0, kU32, "connections: 0 k_connect_strat (one kernel per strategy item); 1 k_connect_eval -> k_connect_shadow -> k_connect_mis, in chunks"},
     {"WTGPU_CONNECT_CLASS", K(connect_class), KNOB_U32, 1, 0, kU32, "connections (the one-kernel form): 0 k_connect_strat (an item is one strategy of a sample); 1 k_connect_class (an item is a sample, bucketed by the lengths of its subpaths, all of its strategies in a row; DESIGN.md §4)"},
+    {"WTGPU_PASS_C_TIERS", K(pass_c_tiers), KNOB_U32, 1, 0, 1, "pass C: 1 in three lane shapes (k_interact_c_prep: 8 lanes per walk, power sum and tries 0-7; k_interact_c_wide / _hard_tries: tries only; k_interact_c_commit: lane = walk); 0 k_interact_c / k_interact_c_hard, one wavefront per walk (A/B; the results do not depend on it; DESIGN.md §4)"},
+    {"WTGPU_PASS_C_EASY_TRIES", K(pass_c_easy_tries), KNOB_U32, 512, 8, kU32, "pass C in tiers: the try from which four wavefronts take a walk over (kernels_fsd.hip: kEasyTries); the tests move it to drive walks into every tier, the results do not depend on it"},
+    {"WTGPU_PASS_C_THIN", K(pass_c_thin), KNOB_U32, 8, 0, kU32, "pass C in tiers: a round whose queue holds at most this many walks per wavefront of k_interact_c_prep's grid takes one wavefront per walk there (the thin rounds are bound by their longest walk, not by lanes); 0: groups of eight always (the tests); the results do not depend on it"},
     {"WTGPU_TILED_SPLAT", K(tiled_splat), KNOB_U32, 1, 0, kU32, "0: the plain per-sample splat kernel"},
     {"WTGPU_TRACE_STAGED", K(trace_staged), KNOB_U32, 1, 0, kU32, "1: the traversal in stages (k_tr_axis / k_tr_cone / k_tr_policy / k_tr_tail) ..."},
     {"WTGPU_TRACE_STAGES", K(trace_stages), KNOB_U32, 3, 1, 16, "... with this many cone stages before the tail ..."},

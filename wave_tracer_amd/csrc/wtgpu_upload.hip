@@ -185,7 +185,7 @@ static int alloc_slice(wtgpu_scene* s, uint32_t k, uint64_t batch_cap, unsigned 
     if ((rc = dmalloc(s, &st.intb_queue, W2))) return rc;
     if ((rc = dmalloc(s, &st.gather_queue, W2))) return rc;
     if ((rc = dmalloc(s, &st.intc_queue, W2))) return rc;
-    if ((rc = dmalloc(s, &st.intd_queue, W2))) return rc;
+    if ((rc = dmalloc(s, &st.intd_queue, (path_mode ? 1 : 3) * W2))) return rc;   // (+ pass C's wide and commit queues: pass_c_wide_queue / pass_c_commit_queue)
     st.ftask_cap = path_mode ? 1u : (1u << 22);
     if ((rc = dmalloc(s, &st.ftasks, (size_t)st.ftask_cap))) return rc;
     if ((rc = dmalloc(s, &st.facc, path_mode ? 1 : W2))) return rc;
