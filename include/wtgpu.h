@@ -215,6 +215,42 @@ int wtgpu_sensor_mask(wtgpu_scene* scene, void* stream, const uint8_t* shape_fla
  * reference's own CPU job, bit for bit what wtgpu_sensor_mask computes.  No device needed. */
 int wtgpu_sensor_mask_host(const wtgpu_scene* scene, const uint8_t* shape_flags, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out);
 
+/* First-hit maps of a perspective sensor ("AOVs", "G-buffer"): what every pixel's primary rays see first — how far, where, which way it faces,
+ * where on its texture, which shape and triangle.  Noise-free guides for a feature-aware filter and, for a radio scene, the building under a pixel.
+ *   rays     samples >= 1: exactly the rays of wtgpu_sensor_mask for the same `samples` and `seed` — sample s of pixel p draws from the stream
+ *            (seed, p * samples + s) through the sensor's own pixel sampling (perspective.hpp:229-262, k = 0), range [0, inf).  samples == 0: one
+ *            ray per pixel through the pixel's centre, the same statement with the offset (0, 0); no draw, `seed` is not used.  At most 4096.
+ *   sample   of a ray that hits: dist (ads_t::intersect), wp = origin + direction x dist, and the surface record the integrators shade with
+ *            (intersection_surface_t, src/interaction/intersection.cpp:33-72) at that triangle, barycentric point and wp — the shading frame
+ *            includes the `normalmap` wrapper (bsdf/normalmap.hpp:48-62).
+ *   maps     [height][width][K] f32, K = the floats of the bits of `maps`, in bit order:
+ *              1  COVERAGE        1  float(n_hit) / float(samples) (samples == 0 counts as 1), n_hit = the rays of the pixel that hit
+ *              2  DEPTH           1  dist
+ *              4  POSITION        3  wp
+ *              8  NORMAL_GEO      3  the geometric normal as the triangle has it, NOT flipped towards the camera
+ *             16  NORMAL_SHADING  3  the shading normal
+ *             32  UV              2  the texture coordinates ((0, 0) on a mesh without them)
+ *             64  FACING          1  1 if the ray meets the triangle's front (dot(n, direction) <= 0), else 0
+ *            Every map but COVERAGE is the MEAN over the hitting samples: an f32 sum in sample order s = 0, 1, ..., first term first, divided
+ *            once by float(n_hit).  Mean normals are not renormalised: a length below 1 marks a pixel that sees an edge.  A pixel that no
+ *            sample hits holds 0 in every float map.
+ *   ids      [height][width][Ki] u32, of the first sample in order that hits: 1 SHAPE, the shape's index (the order of wtgpu_scene_shape_id);
+ *            2 TRIANGLE, the triangle's index within its shape.  0xFFFFFFFF for a pixel without a hit.
+ * Errors (WTGPU_ERR_INVALID with a message): a sensor that is not perspective (a virtual-plane sensor has no primary ray in this sense), unknown
+ * map or id bits, samples > 4096, a requested group whose pointer is NULL, nothing requested.  A group that is not requested may be NULL. */
+typedef struct wtgpu_first_hit_spec {
+    uint32_t samples;
+    uint32_t maps /* 1 COVERAGE, 2 DEPTH, 4 POSITION, 8 NORMAL_GEO, 16 NORMAL_SHADING, 32 UV, 64 FACING */, ids /* 1 SHAPE, 2 TRIANGLE */, pad;
+    uint64_t seed;
+} wtgpu_first_hit_spec;
+/* On the device, into the caller's DEVICE buffers, asynchronously on `stream`: one kernel — one lane per sample up to 64 samples, one lane per
+ * pixel beyond and for the centre ray (WTGPU_FIRST_HIT_PER_SAMPLE=0: always); the result does not depend on the form.  Needs an uploaded scene
+ * (WTGPU_ERR_INVALID otherwise); counts nothing and touches neither films nor counters. */
+int wtgpu_first_hit(wtgpu_scene* scene, void* stream, const wtgpu_first_hit_spec* spec, float* d_maps, uint32_t* d_ids);
+/* The same on `n_threads` host threads (0: all cores) from the host description, into HOST memory: bit for bit what wtgpu_first_hit computes, and
+ * the result does not depend on n_threads.  No device needed. */
+int wtgpu_first_hit_host(const wtgpu_scene* scene, const wtgpu_first_hit_spec* spec, uint32_t n_threads, float* maps, uint32_t* ids);
+
 /* Profiling aid: `repeats` launches of a streaming copy of n_dwords 32-bit words (one dword per lane, coalesced: the access width
  * of the SoA path state) with a known byte count, used to calibrate rocprofv3's FETCH_SIZE / WRITE_SIZE (tools/profile_round.sh). */
 int wtgpu_calibrate_copy(uint64_t n_dwords, int repeats);

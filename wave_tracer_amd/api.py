@@ -37,6 +37,10 @@ class SensorMaskSpec(C.Structure):   # wtgpu_sensor_mask_spec
                 ("n_shapes", C.c_uint32)]
 
 
+class FirstHitSpec(C.Structure):     # wtgpu_first_hit_spec
+    _fields_ = [("samples", C.c_uint32), ("maps", C.c_uint32), ("ids", C.c_uint32), ("pad", C.c_uint32), ("seed", C.c_uint64)]
+
+
 class TonemapSpec(C.Structure):      # wtgpu_tonemap_spec
     _fields_ = [("present", C.c_int32), ("op", C.c_int32), ("mode", C.c_int32), ("gamma", C.c_float), ("db_min", C.c_float), ("db_max", C.c_float),
                 ("colourmap", C.c_char_p), ("function", C.c_char_p)]
@@ -88,6 +92,10 @@ class FilmDenoiseSpec(C.Structure):  # wtgpu_film_denoise_spec
                 ("eps", C.c_float), ("pad2", C.c_float)]
 
 
+# bit i of wtgpu_first_hit_spec.maps / .ids, the floats (words) of each and their order in memory
+FIRST_HIT_MAPS = [("coverage", 1), ("depth", 1), ("position", 3), ("normal_geo", 3), ("normal_shading", 3), ("uv", 2), ("facing", 1)]
+FIRST_HIT_IDS = [("shape", 1), ("triangle", 1)]
+FIRST_HIT_MAX_SAMPLES = 4096
 FILM_POLAR_MAPS = ["dolp", "dop", "docp", "aolp", "chi", "analyser"]      # bit i of wtgpu_film_polar_spec.maps, and the order of the maps in memory
 FILM_STATS_SCALES = ["linear", "dB"]
 FILM_STATS_ABS, FILM_STATS_LUMINANCE = 1, 2
@@ -123,6 +131,7 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_scene_stats_json", "wtgpu_calibrate_copy", "wtgpu_render_async", "wtgpu_join", "wtgpu_query_regions", "wtgpu_render_progressive",
            "wtgpu_cancel", "wtgpu_pause", "wtgpu_resume", "wtgpu_capture_intermediate", "wtgpu_comm_unique_id", "wtgpu_comm_create", "wtgpu_film_reduce", "wtgpu_comm_destroy", "wtgpu_scene_create_from_xml",
            "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host",
+           "wtgpu_first_hit", "wtgpu_first_hit_host",
            "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host",
            "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host",
            "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host",
@@ -212,6 +221,8 @@ def load_library():
     lib.wtgpu_scene_sensor_mask_spec.argtypes = [vp, C.POINTER(SensorMaskSpec)]
     lib.wtgpu_sensor_mask.argtypes = [vp, vp, vp, u32, u64, vp]
     lib.wtgpu_sensor_mask_host.argtypes = [vp, vp, u32, u64, u32, vp]
+    lib.wtgpu_first_hit.argtypes = [vp, vp, C.POINTER(FirstHitSpec), vp, vp]
+    lib.wtgpu_first_hit_host.argtypes = [vp, C.POINTER(FirstHitSpec), u32, vp, vp]
     lib.wtgpu_scene_tonemap_spec.argtypes = [vp, C.POINTER(TonemapSpec)]
     lib.wtgpu_develop_device.argtypes = [vp, vp, vp, vp, vp, u64, vp]
     lib.wtgpu_tonemap_device.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(Tonemap), u32, vp, u32, vp]
@@ -597,6 +608,62 @@ class Scene:
         out = np.zeros((self.height, self.width), np.float32)
         _check(load_library().wtgpu_sensor_mask_host(self._h, None if flags is None else flags.ctypes.data, n, int(seed), int(threads), out.ctypes.data))
         return out
+
+    @staticmethod
+    def _first_hit_args(samples, seed, maps, ids):
+        """-> (wtgpu_first_hit_spec, [(name, offset, n)] of the maps, K, the same of the ids, Ki); names in any order, memory in bit order."""
+        def group(names, table, what):
+            names = [names] if isinstance(names, str) else list(names)
+            known = [n for n, _ in table]
+            for n in names:
+                if n not in known:
+                    raise ValueError(f"first_hit: unknown {what} {n!r} (one of {known})")
+            bits, layout, off = 0, [], 0
+            for i, (n, k) in enumerate(table):
+                if n in names:
+                    bits |= 1 << i
+                    layout.append((n, off, k))
+                    off += k
+            return bits, layout, off
+        mbits, mlay, K = group(maps, FIRST_HIT_MAPS, "map")
+        ibits, ilay, Ki = group(ids, FIRST_HIT_IDS, "id")
+        return FirstHitSpec(int(samples), mbits, ibits, 0, int(seed)), mlay, K, ilay, Ki
+
+    @staticmethod
+    def _first_hit_views(out, mlay, ilay, m, i):
+        for n, off, k in mlay:
+            out[n] = m[..., off] if k == 1 else m[..., off:off + k]
+        for n, off, k in ilay:
+            out[n] = i[..., off]
+        return out
+
+    def first_hit(self, samples=0, seed=1, maps=("coverage", "depth", "position", "normal_geo", "normal_shading", "uv", "facing"), ids=("shape", "triangle"),
+                  stream=None):
+        """First-hit maps of the perspective sensor on the scene's device (wtgpu_first_hit): {name: torch tensor [H, W] or [H, W, n]}, f32 maps
+        (coverage, depth, position 3, normal_geo 3, normal_shading 3, uv 2, facing) and int32 ids holding the u32 bits (shape: the index
+        shape_ids is listed by; triangle: within the shape; -1 = 0xFFFFFFFF without a hit) — views of one allocation per group.  samples 0:
+        the ray through every pixel's centre; n >= 1: the n rays of sensor_mask(samples=n, seed), the maps their means over the rays that hit,
+        the ids the first hitting ray's.  Enqueued on `stream` (default: torch's current)."""
+        import torch
+        if self.device is None:
+            raise WtgpuError("first_hit: upload(device) first")
+        dev = torch.device("cuda", self.device)
+        spec, mlay, K, ilay, Ki = self._first_hit_args(samples, seed, maps, ids)
+        m = torch.empty((self.height, self.width, K), dtype=torch.float32, device=dev) if K else None
+        i = torch.empty((self.height, self.width, Ki), dtype=torch.int32, device=dev) if Ki else None
+        _check(load_library().wtgpu_first_hit(self._h, self._stream_arg(stream, dev), C.byref(spec), m.data_ptr() if K else None,
+                                              i.data_ptr() if Ki else None))
+        return self._first_hit_views({}, mlay, ilay, m, i)
+
+    def first_hit_host(self, samples=0, seed=1, maps=("coverage", "depth", "position", "normal_geo", "normal_shading", "uv", "facing"),
+                       ids=("shape", "triangle"), threads=0):
+        """The same maps on host threads (wtgpu_first_hit_host; threads 0 = all cores), as numpy (ids: uint32): bit for bit the device's."""
+        import numpy as np
+        spec, mlay, K, ilay, Ki = self._first_hit_args(samples, seed, maps, ids)
+        m = np.zeros((self.height, self.width, K), np.float32) if K else None
+        i = np.zeros((self.height, self.width, Ki), np.uint32) if Ki else None
+        _check(load_library().wtgpu_first_hit_host(self._h, C.byref(spec), int(threads), m.ctypes.data if K else None, i.ctypes.data if Ki else None))
+        return self._first_hit_views({}, mlay, ilay, m, i)
 
     @property
     def tonemap_spec(self):

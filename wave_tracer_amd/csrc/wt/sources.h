@@ -459,12 +459,15 @@ WT_HD sensor_sample_t sensor_sample(const scene_t& sc, uint32_t px, uint32_t py,
 // The mean ray of perspective_t::sample at k = 0 (perspective.hpp:229-262), which is what mask_t::create_mask traces (src/sensor/mask.cpp:49-50):
 // the ray part of the perspective branch of sensor_sample above, with the same draws in the same order and no beam (k = 0 has no sourcing
 // geometry).  A perspective beam's envelope starts at the sensor's position along `dir` (sg_envelope of a source without a surface).
-WT_HD void persp_sample_mean_ray(const sensor_t& s, uint32_t px, uint32_t py, sampler_t& sampler, vec3& ro, vec3& rd) {
+// persp_mean_ray: that ray for a given offset from the pixel's centre, in pixels ((0, 0): the ray through the centre, wt/first_hit.h).
+WT_HD void persp_mean_ray(const sensor_t& s, uint32_t px, uint32_t py, vec2 pixel_offset, vec3& ro, vec3& rd) {
     const vec3 centre = persp_point_on_sensor(s, vec2{float(px) + .5f, float(py) + .5f});
-    const vec2 pixel_offset = sampler_r2(sampler) - vec2{.5f, .5f};
     const vec3 dir_local = normalize(centre + pixel_offset.x * s.ddir_dx + pixel_offset.y * s.ddir_dy);
     ro = s.position;
     rd = to_world(s.frame, dir_local);
+}
+WT_HD void persp_sample_mean_ray(const sensor_t& s, uint32_t px, uint32_t py, sampler_t& sampler, vec3& ro, vec3& rd) {
+    persp_mean_ray(s, px, py, sampler_r2(sampler) - vec2{.5f, .5f}, ro, rd);
 }
 // sensor_t::sample_direct
 WT_HD sensor_direct_sample_t sensor_sample_direct(const scene_t& sc, vec3 wp, float k, sampler_t& sampler) {

@@ -11,6 +11,7 @@
 //   kernels_connect.hip k_connect_enum, _scan, _class / _strat (+ _open), the staged _eval / _shadow / _mis, _splat / _splat_tiled
 //   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
 //   kernels_mask.hip    k_sensor_mask_wave / k_sensor_mask_lane: by-geometry sensor masks (not part of a render)
+//   kernels_firsthit.hip k_first_hit / k_first_hit_wave: first-hit maps of a perspective sensor — depth, position, normals, uv, ids (not part of a render)
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
 //   kernels_compare.hip k_film_compare / k_film_compare_finish: difference statistics of two films (not part of a render)
@@ -589,6 +590,13 @@ int test_flux_queries(const scene_t& sc, hipStream_t stream, const uint32_t* d_q
 // the mask's regex.  The launch returns a hipError_t.
 int sensor_mask_launch(const scene_t& sc, hipStream_t stream, const uint8_t* d_shape_matches, uint32_t samples, uint64_t seed, float* d_out);
 void sensor_mask_host(const scene_t& sc, const uint8_t* shape_matches, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out);
+// kernels_firsthit.hip: first-hit maps of a perspective sensor (wtgpu_first_hit / wtgpu_first_hit_host; wt/first_hit.h).  maps / ids: the bits of
+// wtgpu_first_hit_spec; d_maps: [height][width][fh_map_floats(maps)] f32, d_ids: [height][width][fh_id_words(ids)] u32, each may be null when no
+// bit of its group is set.  samples 0: the ray through the pixel's centre.  per_sample: the measured alternative (WTGPU_FIRST_HIT_PER_SAMPLE).  The launch
+// returns a hipError_t.
+int first_hit_launch(const scene_t& sc, hipStream_t stream, uint32_t samples, uint64_t seed, uint32_t maps, uint32_t ids, uint32_t per_sample, float* d_maps,
+                     uint32_t* d_ids);
+void first_hit_host(const scene_t& sc, uint32_t samples, uint64_t seed, uint32_t maps, uint32_t ids, uint32_t n_threads, float* out_maps, uint32_t* out_ids);
 // kernels_develop.hip: film development and tonemapping (wtgpu_develop_device / wtgpu_tonemap_device / wtgpu_tonemap_host).  Films as wtgpu_render
 // fills them; `t.table` is a DEVICE pointer for the launch and a host pointer for the host twin; s: the Stokes component; d_mask: null, or one
 // f32 per pixel that becomes the fourth component.  per_pixel / lds_table: the measured alternatives (WTGPU_DEVELOP_PER_PIXEL, WTGPU_TONEMAP_LDS_TABLE).

@@ -1,6 +1,7 @@
 // wave_tracer_amd — entry points that are neither a render nor read a film (wtgpu_film.hip): ray / cone / region queries, by-geometry sensor
-// masks, the probes of the kernel tests (wtgpu_test_hooks.h), the PMC calibration copy.
+// masks, first-hit maps, the probes of the kernel tests (wtgpu_test_hooks.h), the PMC calibration copy.
 #include "wtgpu_host.h"
+#include "wt/first_hit.h"
 #include "wt/flux_probe.h"
 #include "wt/sources_probe.h"
 
@@ -97,6 +98,39 @@ int wtgpu_sensor_mask_host(const wtgpu_scene* s, const uint8_t* shape_flags, uin
     if (const int rc = mask_flags_for(s, shape_flags, samples, &flags)) return rc;
     try {
         sensor_mask_host(s->host, flags, samples, seed, n_threads, out);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+
+// ---- first-hit maps (wt/first_hit.h, kernels_firsthit.hip) ---------------------------------------------------------------------------------
+// the checks both forms share
+static int first_hit_check(const wtgpu_scene* s, const wtgpu_first_hit_spec* spec, const float* maps, const uint32_t* ids) {
+    if (!s || !spec) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (s->host.sensor.type != SENSOR_PERSPECTIVE)
+        return fail(WTGPU_ERR_INVALID, "first-hit maps need a perspective sensor (a virtual-plane sensor has no primary ray through a pixel)");
+    if (spec->maps & ~(uint32_t)FH_ALL_MAPS) return fail(WTGPU_ERR_INVALID, "first-hit maps: unknown map bits (1 COVERAGE .. 64 FACING)");
+    if (spec->ids & ~(uint32_t)FH_ALL_IDS) return fail(WTGPU_ERR_INVALID, "first-hit maps: unknown id bits (1 SHAPE, 2 TRIANGLE)");
+    if (spec->samples > kFhMaxSamples) return fail(WTGPU_ERR_INVALID, "first-hit maps: 0 .. 4096 samples per pixel expected");
+    if (!spec->maps && !spec->ids) return fail(WTGPU_ERR_INVALID, "first-hit maps: nothing requested (no map and no id bit)");
+    if (spec->maps && !maps) return fail(WTGPU_ERR_INVALID, "first-hit maps: maps requested, but the maps pointer is NULL");
+    if (spec->ids && !ids) return fail(WTGPU_ERR_INVALID, "first-hit maps: ids requested, but the ids pointer is NULL");
+    return WTGPU_OK;
+}
+int wtgpu_first_hit(wtgpu_scene* s, void* stream, const wtgpu_first_hit_spec* spec, float* d_maps, uint32_t* d_ids) {
+    if (const int rc = first_hit_check(s, spec, d_maps, d_ids)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    device_guard_t guard(s->device);
+    const int e = first_hit_launch(s->dev, static_cast<hipStream_t>(stream), spec->samples, spec->seed, spec->maps, spec->ids,
+                                   s->knobs.first_hit_per_sample, d_maps, d_ids);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_first_hit: ") + hipGetErrorString((hipError_t)e));
+    return WTGPU_OK;
+}
+int wtgpu_first_hit_host(const wtgpu_scene* s, const wtgpu_first_hit_spec* spec, uint32_t n_threads, float* maps, uint32_t* ids) {
+    if (const int rc = first_hit_check(s, spec, maps, ids)) return rc;
+    try {
+        first_hit_host(s->host, spec->samples, spec->seed, spec->maps, spec->ids, n_threads, maps, ids);
     } catch (const std::exception& e) {
         return fail(WTGPU_ERR_INVALID, e.what());
     }

@@ -37,6 +37,11 @@ def tonemap_db(x, db_min, db_max):
     return np.where(x == 0, 0.0, out)
 
 
+def normals_to_rgb(n):
+    """The usual picture of a normal map (Scene.first_hit's normal_geo / normal_shading, [..., 3]): n * 0.5 + 0.5, clamped to [0, 1]."""
+    return np.clip(np.asarray(n, dtype=np.float32) * np.float32(.5) + np.float32(.5), 0.0, 1.0)
+
+
 def colourmap(v, name="turbo"):
     """Maps v in [0,1] to RGB.  'grey' or 'turbo' (polynomial approximation of Google's Turbo map)."""
     v = np.clip(np.asarray(v, dtype=np.float64), 0.0, 1.0)

@@ -177,6 +177,21 @@ def sensor_mask(scene, samples=None, seed=1, shapes=None, device=0):
     return mask.cpu().numpy()
 
 
+def first_hit(scene, samples=0, seed=1, maps=("coverage", "depth", "position", "normal_geo", "normal_shading", "uv", "facing"), ids=("shape", "triangle"),
+              device=0):
+    """The scene's first-hit maps (Scene.first_hit: depth, position, normals, uv, facing, shape and triangle ids per pixel) computed on one
+    GPU, as {name: numpy array} (ids: uint32, 0xFFFFFFFF without a hit).  Uploads the scene like render()."""
+    import numpy as np
+    import torch
+    if scene.device is None:
+        scene.upload(device)
+    dev = torch.device("cuda", scene.device)
+    with torch.cuda.device(dev):
+        out = scene.first_hit(samples, seed, maps, ids)
+        torch.cuda.synchronize(dev)
+    return {k: v.cpu().numpy().view(np.uint32) if v.dtype == torch.int32 else v.cpu().numpy() for k, v in out.items()}
+
+
 def shard_samples(spp, rank, world):
     """Sample-index sharding: rank r renders [r*spp/world, (r+1)*spp/world)."""
     b = (spp * rank) // world
