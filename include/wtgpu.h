@@ -472,6 +472,35 @@ int wtgpu_film_denoise_host(const wtgpu_scene* scene, const double* a_value, con
                             const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec,
                             const float* mask, uint32_t n_threads, float* out, float* residual);
 
+/* The same filter steered by noise-free feature planes (Rousselle, Manzi and Zwicker 2013: min(w_colour, w_feature), here with one exponential) —
+ * what wtgpu_first_hit produces: normals, depth, coverage, shape ids.  Colour-only weights cannot keep what is weaker than the noise; a guide can.
+ *   guide      d_guide[height][width][n_guides] f32, 0 <= n_guides <= 8, with scale[g] finite and >= 0 per plane.
+ *   distance   F(p, q) = sum over g of ((g_g(p) - g_g(q))^2 x scale[g]), sequentially from +0 in plane order; pointwise, no patch.
+ *   weight     with D the colour distance above: w = weight(F) where F is a NaN (0), else weight(F > D ? F : D).  A NaN D still gives 0.
+ *   non-finite a non-finite guide value at p or q gives weight 0: such a pixel is nobody's candidate, has no positive sum itself and passes through.
+ *   ids        with flag 1 (SAME_ID) a candidate must also have d_ids[q] == d_ids[p] ([height][width] u32): a candidate condition like the mask.
+ * Everything else — variance, patch distance, orders, pass-through, one set of weights for all planes and both directions — is the unguided call's.
+ * All scales 0 with finite guides, or one id everywhere, give the unguided result bit for bit; a guide that separates regions by F >= 126 / log2 e
+ * equals SAME_ID with the region index.  f32 + - x and comparisons only: device and host agree bit for bit.
+ * Errors (WTGPU_ERR_INVALID with a message): n_guides > 8, unknown flag bits, a scale that is not finite or negative, a guide / id pointer missing
+ * where it is needed or given where it is not used (d_guide NULL iff n_guides == 0, d_ids NULL iff not SAME_ID), neither guides nor SAME_ID (that
+ * is the unguided call), and everything the unguided call refuses, with its messages (spec->flags stays 0). */
+typedef struct wtgpu_film_denoise_guides {
+    uint32_t n_guides /* 0 .. 8 */, flags /* 1 SAME_ID */;
+    float scale[8];
+} wtgpu_film_denoise_guides;
+/* On the device, asynchronous on `stream`; d_guide, d_ids DEVICE.  Needs an uploaded scene; uses the unguided call's scratch memory and no more;
+ * touches neither films nor counters. */
+int wtgpu_film_denoise_guided_device(wtgpu_scene* scene, void* stream, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                                     const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec,
+                                     const wtgpu_film_denoise_guides* guides, const float* d_guide, const uint32_t* d_ids, const float* d_mask, float* d_out,
+                                     float* d_residual);
+/* The same from HOST memory on `n_threads` host threads (0: all cores): the reference the device is held to, bit for bit. */
+int wtgpu_film_denoise_guided_host(const wtgpu_scene* scene, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                                   const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec,
+                                   const wtgpu_film_denoise_guides* guides, const float* guide, const uint32_t* ids, const float* mask, uint32_t n_threads,
+                                   float* out, float* residual);
+
 void wtgpu_scene_destroy(wtgpu_scene* scene);
 const char* wtgpu_last_error(void);
 const char* wtgpu_scene_stats_json(const wtgpu_scene* scene);

@@ -1,4 +1,4 @@
-"""What the five film benchmarks (bench_develop.py, bench_film_stats.py, bench_film_compare.py, bench_film_polar.py, bench_film_denoise.py) share: the two full-size films, the timing of
+"""What the film benchmarks (bench_develop.py, bench_film_stats.py, bench_film_compare.py, bench_film_polar.py, bench_film_denoise.py, bench_film_denoise_guided.py) share: the two full-size films, the timing of
 a call between device events, the alternation of the paths, the seeded log-uniform films and the one JSON line at the end."""
 import json
 import os

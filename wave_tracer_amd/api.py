@@ -92,6 +92,12 @@ class FilmDenoiseSpec(C.Structure):  # wtgpu_film_denoise_spec
                 ("eps", C.c_float), ("pad2", C.c_float)]
 
 
+class FilmDenoiseGuides(C.Structure):  # wtgpu_film_denoise_guides
+    _fields_ = [("n_guides", C.c_uint32), ("flags", C.c_uint32), ("scale", C.c_float * 8)]
+
+
+FILM_DENOISE_SAME_ID = 1
+FILM_DENOISE_MAX_GUIDES = 8
 # bit i of wtgpu_first_hit_spec.maps / .ids, the floats (words) of each and their order in memory
 FIRST_HIT_MAPS = [("coverage", 1), ("depth", 1), ("position", 3), ("normal_geo", 3), ("normal_shading", 3), ("uv", 2), ("facing", 1)]
 FIRST_HIT_IDS = [("shape", 1), ("triangle", 1)]
@@ -135,7 +141,8 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host",
            "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host",
            "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host",
-           "wtgpu_film_denoise_device", "wtgpu_film_denoise_host"]
+           "wtgpu_film_denoise_device", "wtgpu_film_denoise_host",
+           "wtgpu_film_denoise_guided_device", "wtgpu_film_denoise_guided_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
 CAPTURE_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_void_p)
 
@@ -236,6 +243,8 @@ def load_library():
     lib.wtgpu_film_polar_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(FilmPolarSpec), vp, u32, vp, vp, vp]
     lib.wtgpu_film_denoise_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmDenoiseSpec), vp, vp, vp]
     lib.wtgpu_film_denoise_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmDenoiseSpec), vp, u32, vp, vp]
+    lib.wtgpu_film_denoise_guided_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmDenoiseSpec), C.POINTER(FilmDenoiseGuides), vp, vp, vp, vp, vp]
+    lib.wtgpu_film_denoise_guided_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmDenoiseSpec), C.POINTER(FilmDenoiseGuides), vp, vp, vp, u32, vp, vp]
     lib.wtgpu_test_dn_exp2_neg.argtypes = [vp, u64, vp]
     lib.wtgpu_calibrate_copy.argtypes = [u64, i32]
     lib.wtgpu_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -967,7 +976,49 @@ class Scene:
     def _film_denoise_spec(window, patch, k, alpha, eps):
         return FilmDenoiseSpec(int(window), int(patch), 0, 0, float(k), float(alpha), float(eps), 0.0)
 
-    def film_denoise_device(self, films_a, spe_a, films_b, spe_b, *, window=7, patch=2, k=0.45, alpha=1.0, eps=1e-10, mask=None, residual=False, stream=None):
+    def _film_denoise_guides(self, what, guide, guide_scale, ids, device):
+        """guide / guide_scale / ids of film_denoise_device (device: the torch device) or film_denoise_host (None) -> (wtgpu_film_denoise_guides, the
+        guide [H, W, G] f32 or None, the ids [H, W] holding u32 bits or None), contiguous and of the scene's size, or a refusal.  What only the entry
+        point can judge — the scales' values, the count against 8 — goes there."""
+        import numpy as np
+        n = self.width * self.height
+        if guide is None and guide_scale is not None:
+            raise ValueError(f"{what}: guide_scale without a guide")
+        G, g, i = 0, None, None
+        if guide is not None:
+            if device is None:
+                g = np.ascontiguousarray(guide, dtype=np.float32)
+                ok = g.ndim in (2, 3)
+            else:
+                import torch
+                ok = isinstance(guide, torch.Tensor) and guide.is_cuda and guide.device == device and guide.dtype == torch.float32 and guide.dim() in (2, 3)
+                g = guide.contiguous() if ok else None
+            if not ok or tuple(g.shape[:2]) != (self.height, self.width):
+                raise ValueError(f"{what}: guide: [H, W] or [H, W, G] f32 of the scene's size expected" + ("" if device is None else f", a tensor on {device}"))
+            G = 1 if len(g.shape) == 2 else int(g.shape[2])
+        if ids is not None:
+            if device is None:
+                i = np.ascontiguousarray(ids)
+                ok = i.dtype in (np.dtype(np.int32), np.dtype(np.uint32)) and i.size == n
+            else:
+                import torch
+                ok = isinstance(ids, torch.Tensor) and ids.is_cuda and ids.device == device and ids.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) \
+                    and ids.numel() == n
+                i = ids.contiguous() if ok else None
+            if not ok:
+                raise ValueError(f"{what}: ids: [H, W] int32 or uint32 of the scene's size expected" + ("" if device is None else f", a tensor on {device}"))
+        scales = np.zeros(0, np.float32) if guide is None else np.ones(G, np.float32) if guide_scale is None else np.atleast_1d(np.asarray(guide_scale, dtype=np.float32))
+        if guide is not None and scales.size == 1 and G > 1:
+            scales = np.repeat(scales, G)
+        if scales.ndim != 1 or scales.size != G:
+            raise ValueError(f"{what}: guide_scale: a scalar or {G} values expected, got {scales.size}")
+        spec = FilmDenoiseGuides(G, FILM_DENOISE_SAME_ID if i is not None else 0)
+        for j, s in enumerate(scales[:FILM_DENOISE_MAX_GUIDES]):
+            spec.scale[j] = float(s)
+        return spec, g, i
+
+    def film_denoise_device(self, films_a, spe_a, films_b, spe_b, *, window=7, patch=2, k=0.45, alpha=1.0, eps=1e-10, mask=None, residual=False, stream=None,
+                            guide=None, guide_scale=None, ids=None):
         """Denoises the film that two half-films add up to, where they are (wtgpu_film_denoise_device): the dual-buffer non-local-means filter of
         Rousselle, Knaus and Zwicker 2012.  films_a / films_b are (value, weight, light), torch f64 tensors on the scene's device, of two renders over
         disjoint sample ranges (render_to_noise(..., halves=True)), developed with spe_a / spe_b samples per element; mask an H x W f32 tensor there
@@ -976,7 +1027,11 @@ class Scene:
         of the noise variance is taken off a squared difference, eps: what keeps the quotient finite where there is no variance.  All planes of a pixel
         are filtered with one set of weights, computed from Stokes component 0 of each channel of the OTHER half.  Returns {"film": torch f32
         [H, W, channels, stokes] on the device, (fa + fb) / 2 of the two filtered halves; "residual": (fa - fb) / 2 the same way with residual=True —
-        an estimate of the error that is left — or None}.  Enqueued on `stream` (default: torch's current); nothing crosses to the host."""
+        an estimate of the error that is left — or None}.  Enqueued on `stream` (default: torch's current); nothing crosses to the host.
+        Guided (wtgpu_film_denoise_guided_device; with guide, guide_scale and ids all None the call is exactly the unguided one): guide a torch f32
+        tensor [H, W] or [H, W, G] there, G <= 8 noise-free feature planes (render.first_hit_guides builds one from Scene.first_hit); guide_scale a
+        scalar or G values >= 0 (default 1): the squared difference of plane g counts scale[g] times; a candidate's weight comes from the LARGER of
+        the colour distance and the feature distance.  ids: an int32 / uint32 tensor [H, W]; only pixels with the pixel's own id are candidates."""
         import torch
         dev = self._device_films("film_denoise_device", *films_a, mask)
         self._device_films("film_denoise_device", *films_b)
@@ -984,14 +1039,23 @@ class Scene:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
         res = torch.empty(shape, dtype=torch.float32, device=dev) if residual else None
         spec = self._film_denoise_spec(window, patch, k, alpha, eps)
+        if guide is not None or guide_scale is not None or ids is not None:
+            gspec, g, i = self._film_denoise_guides("film_denoise_device", guide, guide_scale, ids, dev)
+            _check(load_library().wtgpu_film_denoise_guided_device(self._h, self._stream_arg(stream, dev), *(t.data_ptr() for t in films_a), int(spe_a),
+                                                                   *(t.data_ptr() for t in films_b), int(spe_b), C.byref(spec), C.byref(gspec),
+                                                                   None if g is None else g.data_ptr(), None if i is None else i.data_ptr(),
+                                                                   None if mask is None else mask.data_ptr(), out.data_ptr(), None if res is None else res.data_ptr()))
+            return {"film": out, "residual": res}
         _check(load_library().wtgpu_film_denoise_device(self._h, self._stream_arg(stream, dev), *(t.data_ptr() for t in films_a), int(spe_a),
                                                         *(t.data_ptr() for t in films_b), int(spe_b), C.byref(spec), None if mask is None else mask.data_ptr(),
                                                         out.data_ptr(), None if res is None else res.data_ptr()))
         return {"film": out, "residual": res}
 
-    def film_denoise_host(self, films_a, spe_a, films_b, spe_b, *, window=7, patch=2, k=0.45, alpha=1.0, eps=1e-10, mask=None, residual=False, threads=0):
+    def film_denoise_host(self, films_a, spe_a, films_b, spe_b, *, window=7, patch=2, k=0.45, alpha=1.0, eps=1e-10, mask=None, residual=False, threads=0,
+                          guide=None, guide_scale=None, ids=None):
         """film_denoise_device's twin on host threads from numpy films (wtgpu_film_denoise_host; threads 0 = all cores): the same dict, "film" and
-        "residual" numpy arrays, bit for bit the device's.  No device needed.  Naive per pixel and candidate: what the device is held to, not a fast path."""
+        "residual" numpy arrays, bit for bit the device's.  No device needed.  Naive per pixel and candidate: what the device is held to, not a fast path.
+        guide, guide_scale, ids: as film_denoise_device's, numpy arrays (wtgpu_film_denoise_guided_host)."""
         import numpy as np
         sets = [self._host_films("film_denoise_host", *films)[:3] for films in (films_a, films_b)]
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
@@ -1001,6 +1065,13 @@ class Scene:
         out = np.zeros(shape, dtype=np.float32)
         res = np.zeros(shape, dtype=np.float32) if residual else None
         spec = self._film_denoise_spec(window, patch, k, alpha, eps)
+        if guide is not None or guide_scale is not None or ids is not None:
+            gspec, g, i = self._film_denoise_guides("film_denoise_host", guide, guide_scale, ids, None)
+            _check(load_library().wtgpu_film_denoise_guided_host(self._h, *(t.ctypes.data for t in sets[0]), int(spe_a), *(t.ctypes.data for t in sets[1]), int(spe_b),
+                                                                 C.byref(spec), C.byref(gspec), None if g is None else g.ctypes.data,
+                                                                 None if i is None else i.ctypes.data, None if m is None else m.ctypes.data, int(threads),
+                                                                 out.ctypes.data, None if res is None else res.ctypes.data))
+            return {"film": out, "residual": res}
         _check(load_library().wtgpu_film_denoise_host(self._h, *(t.ctypes.data for t in sets[0]), int(spe_a), *(t.ctypes.data for t in sets[1]), int(spe_b),
                                                       C.byref(spec), None if m is None else m.ctypes.data, int(threads), out.ctypes.data,
                                                       None if res is None else res.ctypes.data))

@@ -84,11 +84,27 @@ __global__ void __launch_bounds__(kFilmBlock) k_denoise_variance(const float* __
 // offset's S_d is written after the barrier behind h, its h after the barrier behind its S_d.
 // kMode 0: both directions in one launch, the first direction's result in registers.  1 / 2: the first / the second direction alone; the first
 // leaves fa and whether it had a sum in `fa_buf` / `fa_ok`, where the second finds them (the measured alternative: film_denoise_launch).
-template <uint32_t C, uint32_t ST, int kMode>
+// kGuided (wtgpu_film_denoise_guided_device; wt/film_denoise.h, "Guides"): the last argument carries the guide buffer, the id plane and the scales, G a
+// run-time value.  The id plane of the candidate square goes into LDS behind the candidate bytes (SAME_ID: a candidate condition, tested before the
+// patch sum is read); every lane holds g(p) in registers and takes g(q) either from global memory, where it also reads x(q) (staged = 0), or from
+// the G planes of the candidate square in LDS, plane-major (staged = 1: dn_guided_staged decides, by WTGPU_FILM_DENOISE_GUIDE_LDS and by what
+// fits into 64 KB).  F and the id test come before the weight; x(q) is read only where w > 0.  The unguided instantiations take an empty struct
+// there and contain none of this.
+struct dn_guide_args_t {
+    const float* g;          // [H][W][G], null with G = 0
+    const uint32_t* ids;     // [H][W], null without SAME_ID
+    uint32_t staged;
+    film_denoise_guides_t gd;
+};
+struct dn_no_guides_t {};
+template <bool kGuided>
+using dn_guide_arg = std::conditional_t<kGuided, dn_guide_args_t, dn_no_guides_t>;
+
+template <uint32_t C, uint32_t ST, int kMode, bool kGuided>
 __global__ void __launch_bounds__(kFilmBlock) k_denoise_filter(const float* __restrict__ xa, const float* __restrict__ xb, const float* __restrict__ var,
                                                                const unsigned char* __restrict__ valid, const float* __restrict__ mask, film_denoise_args_t a,
                                                                uint32_t W, uint32_t H, float* fa_buf, unsigned char* fa_ok, float* __restrict__ out,
-                                                               float* __restrict__ residual) {
+                                                               float* __restrict__ residual, dn_guide_arg<kGuided> ga) {
     constexpr uint32_t P = C * ST, T = kDnTile;
     extern __shared__ __attribute__((aligned(16))) float dn_lds[];   // dn_filter_lds_bytes: sized by the call's radii, not by the largest
     const int r = (int)a.r, f = (int)a.f, R = r + f;
@@ -98,6 +114,16 @@ __global__ void __launch_bounds__(kFilmBlock) k_denoise_filter(const float* __re
     float* const s_s = s_y + C * SS;            // [T2 x T2]
     float* const s_h = s_s + T2 * T2;           // [T2 x T]
     unsigned char* const s_ok = reinterpret_cast<unsigned char*>(s_h + T2 * T);   // [SO x SO]
+    const uint32_t SO2 = SO * SO;
+    uint32_t G = 0;
+    bool same_id = false, staged = false;
+    uint32_t* s_id = nullptr;                   // [SO x SO] with SAME_ID
+    float* s_g = nullptr;                       // [G][SO x SO] where the guides are staged
+    if constexpr (kGuided) {
+        G = ga.gd.n, same_id = (ga.gd.flags & kDnSameId) != 0, staged = ga.staged != 0;
+        s_id = reinterpret_cast<uint32_t*>(s_ok + (SO2 + 3u) / 4u * 4u);
+        s_g = reinterpret_cast<float*>(s_id + (same_id ? SO2 : 0u));
+    }
     const int x0 = (int)(blockIdx.x * T), y0 = (int)(blockIdx.y * T);
     const uint32_t tid = threadIdx.x, tx = tid & (T - 1u), ty = tid / T;
     const uint32_t px = (uint32_t)x0 + tx, py = (uint32_t)y0 + ty;
@@ -112,11 +138,24 @@ __global__ void __launch_bounds__(kFilmBlock) k_denoise_filter(const float* __re
     for (uint32_t idx = tid; idx < SO * SO; idx += kFilmBlock) {
         const int qx = x0 - r + (int)(idx % SO), qy = y0 - r + (int)(idx / SO);
         bool ok = qx >= 0 && qy >= 0 && (uint32_t)qx < W && (uint32_t)qy < H;
+        uint64_t g = 0;
         if (ok) {
-            const uint64_t g = (uint64_t)qy * W + (uint32_t)qx;
+            g = (uint64_t)qy * W + (uint32_t)qx;
             ok = valid[g] != 0 && (!mask || mask[g] > 0.f);
         }
         s_ok[idx] = ok ? 1 : 0;
+        if constexpr (kGuided) {   // (what is no candidate is never looked up)
+            if (same_id) s_id[idx] = ok ? ga.ids[g] : 0u;
+            if (staged)
+                for (uint32_t k = 0; k < G; ++k) s_g[k * SO2 + idx] = ok ? ga.g[g * G + k] : 0.f;
+        }
+    }
+    float gp[kDnMaxGuides];
+    uint32_t idp = 0;
+    if constexpr (kGuided) {
+#pragma unroll
+        for (uint32_t k = 0; k < kDnMaxGuides; ++k) gp[k] = inside && k < G ? ga.g[p * G + k] : 0.f;
+        if (same_id && inside) idp = ga.ids[p];
     }
     // the (at most two) region pixels u and row sums this thread computes per offset: where u is in the halo, where the row sum starts in the region
     const uint32_t n_region = T2 * T2, n_rows = T2 * T;
@@ -178,13 +217,34 @@ __global__ void __launch_bounds__(kFilmBlock) k_denoise_filter(const float* __re
                     }
                 }
                 __syncthreads();
-                if (active && s_ok[(uint32_t)((int)cand0 + dy * (int)SO + dx)] != 0) {
+                const uint32_t cq = (uint32_t)((int)cand0 + dy * (int)SO + dx);
+                bool cand = active && s_ok[cq] != 0;
+                if constexpr (kGuided) {
+                    if (cand && same_id) cand = s_id[cq] == idp;
+                }
+                if (cand) {
+                    const uint64_t q = (uint64_t)((int64_t)p + (int64_t)dy * (int64_t)W + dx);
                     float D = s_h[ty * T + tx];
                     for (uint32_t j = 1; j <= n2f; ++j) D += s_h[(ty + j) * T + tx];
-                    const float w = dn_weight(D * a.inv_norm);
+                    float Dc = D * a.inv_norm;
+                    if constexpr (kGuided) {
+                        float F = 0.f;
+                        if (staged) {
+#pragma unroll
+                            for (uint32_t k = 0; k < kDnMaxGuides; ++k)
+                                if (k < G) F += dn_feature_term(gp[k], s_g[k * SO2 + cq], ga.gd.scale[k]);
+                        } else {
+                            const float* __restrict__ gq = ga.g + q * G;
+#pragma unroll
+                            for (uint32_t k = 0; k < kDnMaxGuides; ++k)
+                                if (k < G) F += dn_feature_term(gp[k], gq[k], ga.gd.scale[k]);
+                        }
+                        Dc = dn_guided(Dc, F);
+                    }
+                    const float w = dn_weight(Dc);
                     if (w > 0.f) {
                         sw += w;
-                        const float* __restrict__ xq = x + (uint64_t)((int64_t)p + (int64_t)dy * (int64_t)W + dx) * P;
+                        const float* __restrict__ xq = x + q * P;
 #pragma unroll
                         for (uint32_t i = 0; i < P; ++i) acc[i] += w * (xq[i] - xp[i]);
                     }
@@ -223,34 +283,45 @@ __global__ void __launch_bounds__(kFilmBlock) k_denoise_filter(const float* __re
 }
 
 // the filter's LDS for a call's radii: v and y of the halo, S_d, its row sums, the candidate bytes (rounded up to whole floats)
-static size_t dn_filter_lds_bytes(uint32_t C, uint32_t r, uint32_t f) {
+// guided: + a word per candidate for the ids (SAME_ID) and, where the guides are staged, n_staged planes of the candidate square
+static size_t dn_filter_lds_bytes(uint32_t C, uint32_t r, uint32_t f, bool ids = false, uint32_t n_staged = 0) {
     const size_t S = kDnTile + 2 * (r + f), T2 = kDnTile + 2 * f, SO = kDnTile + 2 * r;
-    return (2 * C * S * S + T2 * T2 + T2 * kDnTile + (SO * SO + 3) / 4) * sizeof(float);
+    return (2 * C * S * S + T2 * T2 + T2 * kDnTile + (SO * SO + 3) / 4 + (ids ? SO * SO : 0) + n_staged * SO * SO) * sizeof(float);
 }
-static_assert((2 * 3 * kDnMaxHalo * kDnMaxHalo + kDnMaxRegion * kDnMaxRegion + kDnMaxRegion * kDnTile + (kDnMaxCand * kDnMaxCand + 3) / 4) * sizeof(float) <= 65536,
-              "the largest halo fits the 64 KB a launch may ask for without an attribute");
+constexpr size_t kDnMaxLds = 65536;   // what a launch may ask for without an attribute
+static_assert((2 * 3 * kDnMaxHalo * kDnMaxHalo + kDnMaxRegion * kDnMaxRegion + kDnMaxRegion * kDnTile + (kDnMaxCand * kDnMaxCand + 3) / 4 + kDnMaxCand * kDnMaxCand) *
+                      sizeof(float) <= kDnMaxLds,
+              "the largest halo and its id plane fit the 64 KB a launch may ask for without an attribute");
+// The guides go into LDS where the knob asks for it and they fit beside the rest; from global memory otherwise.  Which form: on the MI355X
+// (tools/bench_film_denoise_guided.py, profiles/film_denoise_guided_bench.json: window 7, patch 2, five planes and ids; median of 15 calls each,
+// alternated, beside the unguided call at 5.02 / 7.40 ms in the same run) from global memory 7.69 ms on the cornell film (P = 3) and 10.77 ms on the
+// polarimetric room film (P = 12), staged 8.54 and 10.71 ms: 18 KB more LDS leave three blocks per CU where the id plane alone leaves four, and
+// the loads it saves were served by the caches.  The knob's default is therefore 0.
+static bool dn_guided_staged(uint32_t C, const film_denoise_args_t& a, const film_denoise_guides_t& gd, uint32_t knob) {
+    return knob != 0 && gd.n > 0 && dn_filter_lds_bytes(C, a.r, a.f, (gd.flags & kDnSameId) != 0, gd.n) <= kDnMaxLds;
+}
 
-template <uint32_t C, uint32_t ST>
+template <uint32_t C, uint32_t ST, bool kGuided>
 static void denoise_launch_cs(hipStream_t stream, const double* a_value, const double* a_weight, const double* a_light, double sl_a, const double* b_value,
                               const double* b_weight, const double* b_light, double sl_b, const film_denoise_args_t& a, bool fused, const float* d_mask, uint32_t W,
                               uint32_t H, float* xa, float* xb, float* fa, float* e, float* v, unsigned char* valid, unsigned char* fa_ok, float* d_out,
-                              float* d_residual) {
+                              float* d_residual, const dn_guide_arg<kGuided>& ga, size_t lds) {
     const uint64_t npix = (uint64_t)W * H;
-    const size_t lds = dn_filter_lds_bytes(C, a.r, a.f);
     const dim3 pixels((uint32_t)((npix + kFilmBlock - 1) / kFilmBlock)), tiles((W + kDnTile - 1) / kDnTile, (H + kDnTile - 1) / kDnTile), block(kFilmBlock);
     hipLaunchKernelGGL((k_denoise_prepare<C, ST>), pixels, block, 0, stream, a_value, a_weight, a_light, sl_a, b_value, b_weight, b_light, sl_b, npix, xa, xb, e, valid);
     hipLaunchKernelGGL((k_denoise_variance<C>), pixels, block, 0, stream, e, W, H, v);
     if (fused) {
-        hipLaunchKernelGGL((k_denoise_filter<C, ST, 0>), tiles, block, lds, stream, xa, xb, v, valid, d_mask, a, W, H, fa, fa_ok, d_out, d_residual);
+        hipLaunchKernelGGL((k_denoise_filter<C, ST, 0, kGuided>), tiles, block, lds, stream, xa, xb, v, valid, d_mask, a, W, H, fa, fa_ok, d_out, d_residual, ga);
     } else {
-        hipLaunchKernelGGL((k_denoise_filter<C, ST, 1>), tiles, block, lds, stream, xa, xb, v, valid, d_mask, a, W, H, fa, fa_ok, d_out, d_residual);
-        hipLaunchKernelGGL((k_denoise_filter<C, ST, 2>), tiles, block, lds, stream, xa, xb, v, valid, d_mask, a, W, H, fa, fa_ok, d_out, d_residual);
+        hipLaunchKernelGGL((k_denoise_filter<C, ST, 1, kGuided>), tiles, block, lds, stream, xa, xb, v, valid, d_mask, a, W, H, fa, fa_ok, d_out, d_residual, ga);
+        hipLaunchKernelGGL((k_denoise_filter<C, ST, 2, kGuided>), tiles, block, lds, stream, xa, xb, v, valid, d_mask, a, W, H, fa, fa_ok, d_out, d_residual, ga);
     }
 }
 
-int film_denoise_launch(const sensor_t& sn, hipStream_t stream, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
-                        const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const film_denoise_args_t& a, uint32_t fused,
-                        const float* d_mask, float* d_scratch, float* d_out, float* d_residual) {
+template <bool kGuided>
+static int denoise_launch(const sensor_t& sn, hipStream_t stream, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                          const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const film_denoise_args_t& a, uint32_t fused,
+                          const float* d_mask, float* d_scratch, float* d_out, float* d_residual, const dn_guide_arg<kGuided>& ga, bool ids, uint32_t n_staged) {
     const uint32_t W = sn.width, H = sn.height, stokes = film_stokes(sn);
     if ((uint64_t)W * H == 0 || (stokes != 1 && stokes != 4) || a.r > kDnMaxWindow || a.f > kDnMaxPatch) return (int)hipErrorInvalidValue;
     // Which form: on the MI355X (tools/bench_film_denoise.py, profiles/film_denoise_bench.json: window 7, patch 2; median of 15 calls each, alternated,
@@ -264,22 +335,44 @@ int film_denoise_launch(const sensor_t& sn, hipStream_t stream, const double* a_
     const double sl_a = develop_scale(spe_a), sl_b = develop_scale(spe_b);
     if (!film_dispatch(sn.channels, false, [&](auto c, auto) {
             constexpr uint32_t C = decltype(c)::value;
+            const size_t lds = dn_filter_lds_bytes(C, a.r, a.f, ids, n_staged);
             if (stokes == 1)
-                denoise_launch_cs<C, 1>(stream, a_value, a_weight, a_light, sl_a, b_value, b_weight, b_light, sl_b, a, fused != 0, d_mask, W, H, s + l.xa, s + l.xb, s + l.fa,
-                                        s + l.e, s + l.v, valid, fa_ok, d_out, d_residual);
+                denoise_launch_cs<C, 1, kGuided>(stream, a_value, a_weight, a_light, sl_a, b_value, b_weight, b_light, sl_b, a, fused != 0, d_mask, W, H, s + l.xa, s + l.xb,
+                                                 s + l.fa, s + l.e, s + l.v, valid, fa_ok, d_out, d_residual, ga, lds);
             else
-                denoise_launch_cs<C, 4>(stream, a_value, a_weight, a_light, sl_a, b_value, b_weight, b_light, sl_b, a, fused != 0, d_mask, W, H, s + l.xa, s + l.xb, s + l.fa,
-                                        s + l.e, s + l.v, valid, fa_ok, d_out, d_residual);
+                denoise_launch_cs<C, 4, kGuided>(stream, a_value, a_weight, a_light, sl_a, b_value, b_weight, b_light, sl_b, a, fused != 0, d_mask, W, H, s + l.xa, s + l.xb,
+                                                 s + l.fa, s + l.e, s + l.v, valid, fa_ok, d_out, d_residual, ga, lds);
         }))
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
+int film_denoise_launch(const sensor_t& sn, hipStream_t stream, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                        const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const film_denoise_args_t& a, uint32_t fused,
+                        const float* d_mask, float* d_scratch, float* d_out, float* d_residual) {
+    return denoise_launch<false>(sn, stream, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, fused, d_mask, d_scratch, d_out, d_residual,
+                                 dn_no_guides_t{}, false, 0);
+}
+
+// The guided call: the same three or four kernels, the filter in its guided instantiation.  guide_lds: WTGPU_FILM_DENOISE_GUIDE_LDS.
+int film_denoise_guided_launch(const sensor_t& sn, hipStream_t stream, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                               const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const film_denoise_args_t& a, uint32_t fused,
+                               const film_denoise_guides_t& gd, uint32_t guide_lds, const float* d_guide, const uint32_t* d_ids, const float* d_mask,
+                               float* d_scratch, float* d_out, float* d_residual) {
+    if (gd.n > kDnMaxGuides || (gd.n > 0) != (d_guide != nullptr) || ((gd.flags & kDnSameId) != 0) != (d_ids != nullptr)) return (int)hipErrorInvalidValue;
+    const bool ids = (gd.flags & kDnSameId) != 0, staged = dn_guided_staged(sn.channels, a, gd, guide_lds);
+    const dn_guide_args_t ga{d_guide, d_ids, staged ? 1u : 0u, gd};
+    return denoise_launch<true>(sn, stream, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, fused, d_mask, d_scratch, d_out, d_residual, ga,
+                                ids, staged ? gd.n : 0u);
+}
+
 // ---- the host twin: the same wt/film_denoise.h functions on host threads, naive per pixel and candidate in the header's orders; every pixel is
-// one thread's, so the result does not depend on the number of threads --------------------------------------------------------------------------
+// one thread's, so the result does not depend on the number of threads.  gd (may be null: the unguided call), guide, ids: wt/film_denoise.h's guides ----
 void film_denoise_host(const sensor_t& sn, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
                        const double* b_weight, const double* b_light, uint64_t spe_b, const film_denoise_args_t& a, const float* mask, uint32_t n_threads,
-                       float* out, float* residual) {
+                       float* out, float* residual, const film_denoise_guides_t* gd, const float* guide, const uint32_t* ids) {
+    const uint32_t G = gd ? gd->n : 0u;
+    const bool same_id = gd && (gd->flags & kDnSameId) != 0;
     const uint32_t W = sn.width, H = sn.height, C = sn.channels, ST = film_stokes(sn), P = C * ST;
     const uint64_t npix = (uint64_t)W * H;
     const double sl_a = develop_scale(spe_a), sl_b = develop_scale(spe_b);
@@ -326,7 +419,7 @@ void film_denoise_host(const sensor_t& sn, const double* a_value, const double* 
                             const int qx = (int)px + dx, qy = py + dy;
                             if (qx < 0 || qy < 0 || (uint32_t)qx >= W || (uint32_t)qy >= H) continue;
                             const uint64_t q = (uint64_t)qy * W + (uint32_t)qx;
-                            if (!ok[q]) continue;
+                            if (!ok[q] || (same_id && ids[q] != ids[p])) continue;
                             float D = 0.f;
                             for (int j = -f; j <= f; ++j) {
                                 float h = 0.f;
@@ -338,7 +431,13 @@ void film_denoise_host(const sensor_t& sn, const double* a_value, const double* 
                                 }
                                 D = j == -f ? h : D + h;
                             }
-                            const float w = dn_weight(D * a.inv_norm);
+                            float Dc = D * a.inv_norm;
+                            if (gd) {
+                                float F = 0.f;
+                                for (uint32_t g = 0; g < G; ++g) F += dn_feature_term(guide[p * G + g], guide[q * G + g], gd->scale[g]);
+                                Dc = dn_guided(Dc, F);
+                            }
+                            const float w = dn_weight(Dc);
                             if (w > 0.f) {
                                 sw += w;
                                 for (uint32_t i = 0; i < P; ++i) acc[i] += w * (x[q * P + i] - x[p * P + i]);

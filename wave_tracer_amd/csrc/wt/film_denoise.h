@@ -32,6 +32,14 @@
 // not finite) gives out_i = (a_i + b_i) x 0.5f and residual_i = (a_i - b_i) x 0.5f.
 // Outputs.  out_i = (fa_i + fb_i) x 0.5f, residual_i = (fa_i - fb_i) x 0.5f, [height][width][P] f32; a NaN is stored as THE quiet NaN 0x7fc00000.
 // A constant film is a fixed point and r = 0 returns (a + b) x 0.5f, both bit for bit.
+// Guides (wtgpu_film_denoise_guided_*; Rousselle, Manzi and Zwicker 2013's min(w_colour, w_feature) with ONE exponential).  A guide buffer
+// g[H][W][G] f32, 0 <= G <= 8, with a scale s_g >= 0 per plane, and optionally an id plane id[H][W] u32.  Feature distance, pointwise (no patch):
+//   F(p, q) = sum over g of ((g_g(p) - g_g(q))^2 x s_g), sequentially from +0 in plane order (dn_feature).
+// With Dc = D(p, q) x inv_norm: dn_guided(Dc, F) is F where F is a NaN, else F > Dc ? F : Dc, and w = dn_weight(dn_guided(Dc, F)); a NaN Dc
+// still gives 0.  A non-finite guide value at p or q makes F infinite or a NaN (inf x 0 is a NaN), so the weight is 0: a pixel whose own guide
+// is not finite has sw = 0 and passes through by the rule above, and is nobody's candidate.  With the flag SAME_ID a candidate must also
+// have id(q) == id(p): a candidate condition like `valid` and the mask (the pixel itself always qualifies).  F = +0 everywhere (all scales 0,
+// finite guides; or G = 0) changes no weight: 0 > Dc only where Dc < 0, where both weights are 1.
 #pragma once
 #include "core.h"
 #include "tonemap.h"
@@ -84,6 +92,22 @@ WT_HD float dn_weight(float D) {
     if (!(D == D)) return 0.f;
     if (D <= 0.f) return 1.f;
     return dn_exp2_neg(D * kDnLog2e);
+}
+
+// the guides of a call: G planes with their scales, and whether a candidate must carry the pixel's id
+constexpr uint32_t kDnMaxGuides = 8, kDnSameId = 1;
+struct film_denoise_guides_t {
+    uint32_t n, flags;
+    float scale[kDnMaxGuides];
+};
+// one plane's term of F, and what F does to the colour distance (the head of the file)
+WT_HD float dn_feature_term(float gp, float gq, float s) {
+    const float d = gp - gq;
+    return (d * d) * s;
+}
+WT_HD float dn_guided(float Dc, float F) {
+    if (!(F == F)) return F;
+    return F > Dc ? F : Dc;
 }
 
 WT_HD float dn_e(float a, float b) {

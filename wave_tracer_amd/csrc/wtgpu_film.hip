@@ -440,6 +440,67 @@ int wtgpu_film_denoise_host(const wtgpu_scene* s, const double* a_value, const d
     }
     return WTGPU_OK;
 }
+// what the guides say by themselves and against the pointers that come with them; gd: what the kernels and the host twin are told
+static int film_denoise_guides_check(const wtgpu_film_denoise_guides* guides, const void* guide, const void* ids, film_denoise_guides_t& gd) {
+    static_assert(sizeof(wtgpu_film_denoise_guides) == sizeof(film_denoise_guides_t) && kDnMaxGuides == 8, "the public struct is the header's");
+    if (guides->n_guides > kDnMaxGuides)
+        return fail(WTGPU_ERR_INVALID, "film_denoise_guided: n_guides " + std::to_string(guides->n_guides) + " out of range (0 .. " + std::to_string(kDnMaxGuides) + ")");
+    if (guides->flags & ~kDnSameId) return fail(WTGPU_ERR_INVALID, "film_denoise_guided: unknown flag bits (1 SAME_ID is the only one)");
+    const bool same_id = (guides->flags & kDnSameId) != 0;
+    if (guides->n_guides == 0 && !same_id)
+        return fail(WTGPU_ERR_INVALID, "film_denoise_guided: neither guides nor SAME_ID: this is the unguided call (wtgpu_film_denoise_device / _host)");
+    for (uint32_t g = 0; g < guides->n_guides; ++g)
+        if (!std::isfinite(guides->scale[g]) || guides->scale[g] < 0.f)
+            return fail(WTGPU_ERR_INVALID, "film_denoise_guided: scale " + std::to_string(g) + ": a finite value >= 0 expected");
+    if (guides->n_guides > 0 && !guide) return fail(WTGPU_ERR_INVALID, "film_denoise_guided: n_guides > 0 without a guide buffer");
+    if (guides->n_guides == 0 && guide) return fail(WTGPU_ERR_INVALID, "film_denoise_guided: a guide buffer with n_guides = 0");
+    if (same_id && !ids) return fail(WTGPU_ERR_INVALID, "film_denoise_guided: SAME_ID without an id plane");
+    if (!same_id && ids) return fail(WTGPU_ERR_INVALID, "film_denoise_guided: an id plane without SAME_ID");
+    gd = film_denoise_guides_t{};
+    gd.n = guides->n_guides, gd.flags = guides->flags;
+    for (uint32_t g = 0; g < gd.n; ++g) gd.scale[g] = guides->scale[g];
+    return WTGPU_OK;
+}
+
+int wtgpu_film_denoise_guided_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                                     const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec,
+                                     const wtgpu_film_denoise_guides* guides, const float* d_guide, const uint32_t* d_ids, const float* d_mask, float* d_out,
+                                     float* d_residual) {
+    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !guides || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    film_denoise_args_t a{};
+    if (const int rc = film_denoise_check(s, spec, a)) return rc;
+    film_denoise_guides_t gd{};
+    if (const int rc = film_denoise_guides_check(guides, d_guide, d_ids, gd)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    const sensor_t& sn = s->host.sensor;
+    if ((uint64_t)sn.width * sn.height == 0) return fail(WTGPU_ERR_INVALID, "film_denoise: the film has no pixels");
+    device_guard_t guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // the unguided call's scratch memory and no more: the guides are read where the caller has them
+    if (!s->d_denoise)
+        if (const int rc = dmalloc(s, &s->d_denoise, film_denoise_scratch_floats(sn))) return rc;
+    const uint32_t fused = s->knobs.film_denoise_fused == 2 ? (film_planes(sn) <= 4 ? 1u : 0u) : s->knobs.film_denoise_fused;
+    const int e = film_denoise_guided_launch(sn, stream, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, fused, gd, s->knobs.film_denoise_guide_lds,
+                                             d_guide, d_ids, d_mask, s->d_denoise, d_out, d_residual);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_denoise_filter (guided): ") + hipGetErrorString((hipError_t)e));
+    return WTGPU_OK;
+}
+int wtgpu_film_denoise_guided_host(const wtgpu_scene* s, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                                   const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec,
+                                   const wtgpu_film_denoise_guides* guides, const float* guide, const uint32_t* ids, const float* mask, uint32_t n_threads, float* out,
+                                   float* residual) {
+    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !guides || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    film_denoise_args_t a{};
+    if (const int rc = film_denoise_check(s, spec, a)) return rc;
+    film_denoise_guides_t gd{};
+    if (const int rc = film_denoise_guides_check(guides, guide, ids, gd)) return rc;
+    try {
+        film_denoise_host(s->host.sensor, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, mask, n_threads, out, residual, &gd, guide, ids);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
 int wtgpu_test_dn_exp2_neg(const float* t, uint64_t n, float* out) {
     if (!t || !out) return fail(WTGPU_ERR_INVALID, "null argument");
     film_denoise_exp2_neg(t, n, out);

@@ -40,6 +40,7 @@ namespace wt {
 struct tonemap_args_t;   // wt/tonemap.h (kernels_develop.hip and the entry points that launch it)
 struct film_polar_args_t;   // wt/film_polar.h (kernels_polar.hip and its entry points)
 struct film_denoise_args_t;   // wt/film_denoise.h (kernels_denoise.hip and its entry points)
+struct film_denoise_guides_t;
 }
 
 namespace wtk {
@@ -649,7 +650,14 @@ int film_denoise_launch(const sensor_t& sn, hipStream_t stream, const double* a_
                         const float* d_mask, float* d_scratch, float* d_out, float* d_residual);
 void film_denoise_host(const sensor_t& sn, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
                        const double* b_weight, const double* b_light, uint64_t spe_b, const film_denoise_args_t& a, const float* mask, uint32_t n_threads,
-                       float* out, float* residual);
+                       float* out, float* residual, const film_denoise_guides_t* gd = nullptr, const float* guide = nullptr, const uint32_t* ids = nullptr);
+// The guided filter (wtgpu_film_denoise_guided_*; wt/film_denoise.h "Guides"): gd the plane count, flags and scales; d_guide [height][width][gd.n] f32
+// (null iff gd.n == 0), d_ids [height][width] u32 (null iff not SAME_ID); guide_lds: WTGPU_FILM_DENOISE_GUIDE_LDS (1: the candidate square's guide planes
+// in LDS where they fit into 64 KB beside the rest, else and with 0 from global memory).  The host twin takes the same three through its last arguments.
+int film_denoise_guided_launch(const sensor_t& sn, hipStream_t stream, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
+                               const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const film_denoise_args_t& a, uint32_t fused,
+                               const film_denoise_guides_t& gd, uint32_t guide_lds, const float* d_guide, const uint32_t* d_ids, const float* d_mask,
+                               float* d_scratch, float* d_out, float* d_residual);
 void film_denoise_exp2_neg(const float* t, uint64_t n, float* out);
 
 }   // namespace wtk

@@ -78,13 +78,47 @@ def polarisation(scene, films, spe, **kw):
     return polar(*films, spe, **kw)
 
 
-def denoise(scene, films_a, films_b, spe, **kw):
+FIRST_HIT_GUIDE_KF = 0.6        # Rousselle, Manzi and Zwicker 2013's k_f; first_hit_guides' default scale is 1 / k_f^2 for every plane.  UNTUNED.
+
+
+def first_hit_guides(scene, samples=0, seed=1, scales=None, same_shape=True, host=False):
+    """The guides of a feature-guided denoise() from the scene's first-hit maps (Scene.first_hit on the scene's device; host=True: Scene.first_hit_host,
+    numpy, no device needed): (guide, scales, ids) with guide [H, W, 5] f32 — the shading normal (3), the natural logarithm of the depth where the
+    pixel is covered and 0 elsewhere (1), the coverage (1) —, scales the five plane scales and ids the shape map ([H, W]; None with
+    same_shape=False).  Default scales: 1 / k_f^2 = 2.78 with k_f = 0.6 for every plane, the value Rousselle 2013 use on unit-range features; the
+    log depth is not of unit range, and NOBODY HAS TUNED these numbers.  A sensor that is not perspective is refused by first_hit itself: pass
+    guides of your own to denoise() for a virtual-plane sensor."""
+    maps, ids = ("coverage", "depth", "normal_shading"), (("shape",) if same_shape else ())
+    if scales is None:
+        scales = [1.0 / FIRST_HIT_GUIDE_KF ** 2] * 5
+    scales = [float(s) for s in np.broadcast_to(np.asarray(scales, dtype=np.float64), (5,))]
+    if host:
+        fh = scene.first_hit_host(samples, seed, maps, ids)
+        cov = fh["coverage"] > 0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            logd = np.where(cov, np.log(np.where(cov, fh["depth"], np.float32(1))), np.float32(0)).astype(np.float32)
+        guide = np.concatenate([fh["normal_shading"], logd[..., None], fh["coverage"][..., None]], axis=-1).astype(np.float32)
+        return np.ascontiguousarray(guide), scales, (np.ascontiguousarray(fh["shape"]) if same_shape else None)
+    import torch
+    fh = scene.first_hit(samples, seed, maps, ids)
+    cov = fh["coverage"] > 0
+    logd = torch.where(cov, torch.log(torch.where(cov, fh["depth"], torch.ones_like(fh["depth"]))), torch.zeros_like(fh["depth"]))
+    guide = torch.cat([fh["normal_shading"], logd[..., None], fh["coverage"][..., None]], dim=-1).contiguous()
+    return guide, scales, (fh["shape"].contiguous() if same_shape else None)
+
+
+def denoise(scene, films_a, films_b, spe, guides=None, **kw):
     """Denoises the film that the half-films A and B add up to (render_to_noise(..., halves=True); `spe` samples per element each): films_a / films_b
     are (value, weight, light), torch tensors on the scene's device (Scene.film_denoise_device: everything stays there) or numpy arrays
     (Scene.film_denoise_host).  kw: window, patch, k, alpha, eps, mask, residual (default here: True).  Returns that call's dict — "film", "residual" —
     and "residual_rel" = ||residual|| / ||film|| over the guide planes (Stokes component 0 of each channel) of the pixels where both are finite: an
-    ESTIMATE of the relative error that is left, from the difference of the two filtered halves (None with residual=False; 0 for an all-zero film)."""
+    ESTIMATE of the relative error that is left, from the difference of the two filtered halves (None with residual=False; 0 for an all-zero film).
+    guides: None (the colour-only filter, as before), a (guide, scales, ids) triple as first_hit_guides returns it — arrays where the films are; ids or
+    guide may be None — or True: first_hit_guides(scene) with its untuned defaults, on the host for numpy films."""
     on_host = isinstance(films_a[0], np.ndarray)
+    if guides is not None and guides is not False:
+        guide, scales, ids = first_hit_guides(scene, host=on_host) if guides is True else guides
+        kw = dict(kw, guide=guide, guide_scale=None if guide is None else scales, ids=ids)
     out = (scene.film_denoise_host if on_host else scene.film_denoise_device)(films_a, spe, films_b, spe, **dict({"residual": True}, **kw))
     out["residual_rel"] = None
     if out["residual"] is not None:
