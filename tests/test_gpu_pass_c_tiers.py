@@ -189,6 +189,54 @@ def test_films_differ_by_summation_order_only(built, case, film):
         _check(f"{case}_{film}", f"boundary {b}", _rel_l1(a, b0), _rel_l1(b2, b0), FLOOR[film])
 
 
+_PARENT = os.path.join(ROOT, "tests", "golden", "pass_c_counters_parent.json")
+_ORDER_FREE_TIERS = ("walks", "prep", "rounds", "rounds_not_multiple_of_8", "rounds_shorter_than_8")   # (neither the boundary nor the streams' order move these)
+
+
+def _tiers_pinned(t, every_tier):
+    """The tier counts that a rerun must reproduce: `every_tier` adds wide / hard, which hold at the fixture's boundary (512) only; the queue
+    lengths sorted, and only while every round's length was kept (beyond 56 rounds the streams' order decides which ones are)."""
+    out = {k: int(t[k]) for k in _ORDER_FREE_TIERS + (("wide", "hard") if every_tier else ())}
+    if t["rounds"] <= 56:
+        out["queue_lengths"] = sorted(int(v) for v in t["queue_lengths"])
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(CASES))
+def test_counters_equal_those_of_the_parent_commit(built, case):
+    """Both forms share their device functions (pass_c_tries, pass_c_commit_walk, ...), so their agreement no longer says that either is right:
+    tests/golden/pass_c_counters_parent.json holds, per case, counters() of the old form and pass_c_tiers() at boundary 512 as the kernels of
+    commit 366ab4f (before the pieces were shared) gave them on the MI355X, seed 31; PASS_C_PARENT_RECORD=<file> writes such a table.  Every run
+    of the module — old form twice, boundaries 8 / 64 / 512, thin rounds — gives those integers."""
+    r = _case(case)
+    out = os.environ.get("PASS_C_PARENT_RECORD")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        try:
+            with open(out) as f:
+                rec = json.load(f)
+        except (OSError, ValueError):
+            rec = {}
+        rec[case] = {"counters": {k: int(v) for k, v in r["old"]["counters"].items()},
+                     "tiers": {k: [int(x) for x in v] if k == "queue_lengths" else int(v) for k, v in r[512]["tiers"].items()}}
+        with open(out, "w") as f:
+            json.dump(rec, f, indent=1, sort_keys=True)
+        parent = rec[case]
+    else:
+        with open(_PARENT) as f:
+            parent = json.load(f)[case]
+    assert parent["tiers"]["walks"] > 0, (case, parent)
+    for run in ("old", "old2") + BOUNDARIES + ("thin",):
+        new = r[run]["counters"]
+        assert set(new) == set(parent["counters"]), (case, run, sorted(new), sorted(parent["counters"]))
+        for k, v in parent["counters"].items():
+            assert isinstance(new[k], int) and new[k] == v, (case, run, k, v, new[k])
+    for run in BOUNDARIES + ("thin",):
+        every_tier = run in (512, "thin")
+        assert _tiers_pinned(r[run]["tiers"], every_tier) == _tiers_pinned(parent["tiers"], every_tier), (case, run, r[run]["tiers"], parent["tiers"])
+
+
 def _butterfly(v, offsets):
     """`flux += __shfl_xor(flux, off)` over the last axis, for every offset in turn: every lane adds its partner's value to its own."""
     lanes = np.arange(v.shape[-1])
@@ -199,7 +247,7 @@ def _butterfly(v, offsets):
 
 @pytest.mark.parametrize("n", [1, 7, 8, 9, 33, 64])
 def test_flux_tree_of_the_groups_equals_the_wave_butterfly(n):
-    """CPU, numpy f64: lane j of 64 holds triangle j (zero beyond the list) and the wavefront reduces by xor 32 .. 1 (interact_c_body); group lane
+    """CPU, numpy f64: lane j of 64 holds triangle j (zero beyond the list) and the wavefront reduces by xor 32 .. 1 (pass_c_region_power_wave); group lane
     s of 8 holds t_k = triangle s + 8 k, adds ((t0 + t4) + (t2 + t6)) + ((t1 + t5) + (t3 + t7)) and the group reduces by xor 4, 2, 1
     (k_interact_c_prep).  The same tree: equal bit for bit, in every lane."""
     rng = np.random.default_rng(1000 + n)

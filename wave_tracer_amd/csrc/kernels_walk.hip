@@ -48,18 +48,10 @@ WT_D void interact_body(const launch_args_t& a, int in, int first_round) {
         const uint32_t qi = base + (threadIdx.x & 63);
         bool cont = false;
         uint32_t w = 0;
-        fsd_defer_t defer;
-        defer.pending = defer.resolved = 0;
-        defer.slot = defer.base = defer.next_try = defer.end_draws = 0;
+        fsd_defer_t defer = fsd_defer_none();
         defer.defer_sampling = PASS_B ? 1u : 0u;
-        defer.to_sampling_pass = 0;
-        defer.have_aperture = 0;
         defer.split_no_primary = PASS_B ? 0u : 1u;
         defer.known_no_primary = PASS_B ? 1u : 0u;
-        defer.no_primary = 0;
-        defer.has_gather = defer.gather_n_edges = defer.gather_edge_overflow = 0;
-        defer.gather_flux = 0.f;
-        defer.gather_edges = nullptr;
         bool need_gather = false;
         const bool valid = qi < n;
         if (valid) w = PASS_B ? a.st.intb_queue[qi] : queue_walk(a, ctl, in, qi, first_round);

@@ -614,6 +614,35 @@ struct fsd_defer_t {
     long long marks[8];
 #endif
 };
+// Nothing asked of the step and nothing handed to it (`fs` is written by whoever resolves the loop): what every kernel starts its record from.
+WT_HD fsd_defer_t fsd_defer_none() {
+    fsd_defer_t d;
+    d.pending = d.resolved = 0;
+    d.slot = d.base = d.next_try = d.end_draws = 0;
+    d.defer_sampling = d.to_sampling_pass = d.have_aperture = 0;
+    d.split_no_primary = d.known_no_primary = d.no_primary = 0;
+    d.has_gather = d.gather_n_edges = d.gather_edge_overflow = 0;
+    d.gather_flux = 0.f;
+    d.gather_edges = nullptr;
+    return d;
+}
+// What a rejection loop that ran outside the step found: the lowest accepted try, its point and scattering function — or no accepted try.
+struct fsd_outcome_t {
+    uint32_t acc, t_acc;
+    vec2 x;
+    float f;
+};
+// The record of a walk whose loop over aperture `ap` (pool slot `slot`, tries keyed from draw `base`) ended with `o`: no primary triangle, the
+// aperture exists, the sample is final.  Without an accepted try the walk's stream moves past the last try (max_tries = 0 wraps to `base`).
+WT_HD fsd_defer_t fsd_defer_resolved(const fsd_aperture_t& ap, uint32_t slot, uint32_t base, uint32_t max_tries, const fsd_outcome_t& o) {
+    fsd_defer_t d = fsd_defer_none();
+    d.known_no_primary = d.have_aperture = d.resolved = 1;
+    d.slot = slot;
+    d.base = base;
+    d.fs = fsd_finalize(ap, o.acc != 0u, o.x, o.f);
+    d.end_draws = fsd_draws_after(base, o.acc ? o.t_acc : max_tries - 1u);
+    return d;
+}
 
 #if defined(WTGPU_STEP_PROF) && defined(__HIP_DEVICE_COMPILE__)
 #define WT_STEP_MARK(i) \

@@ -59,13 +59,15 @@ int wtgpu_get_counters(wtgpu_scene* s, wtgpu_counters* out) {
         unsigned long long p[kProfSlots];
         HIP_CHECK(hipMemcpy(p, s->slices[0].counters + kNumCounters, sizeof(p), hipMemcpyDeviceToHost));
         fprintf(stderr, "[wtgpu profile] pass C by aperture size (slice 0): bin=log2(segments) items tries/item kticks/item total-Mticks\n");
-        for (int b = 0; b < 16; ++b)
-            if (p[8 + b]) fprintf(stderr, "[wtgpu profile]   C %2d %8llu %10.1f %10.1f %10.1f   fetch+load %.1f commit %.1f kticks/item\n", b, p[8 + b], double(p[24 + b]) / p[8 + b], double(p[40 + b]) / p[8 + b] * 1e-3, double(p[40 + b]) * 1e-6, double(p[112 + b]) / p[8 + b] * 1e-3, double(p[96 + b]) / p[8 + b] * 1e-3);
+        for (int b = 0; b < 16; ++b) {
+            const unsigned long long n = p[kPassCProfWalks + b];
+            if (n) fprintf(stderr, "[wtgpu profile]   C %2d %8llu %10.1f %10.1f %10.1f   fetch+load %.1f commit %.1f kticks/item\n", b, n, double(p[kPassCProfTries + b]) / n, double(p[kPassCProfTicks + b]) / n * 1e-3, double(p[kPassCProfTicks + b]) * 1e-6, double(p[kPassCProfLoadTicks + b]) / n * 1e-3, double(p[kPassCProfCommitTicks + b]) / n * 1e-3);
+        }
         if (s->knobs.pass_c_tiers) {   // the tiered form: the lines above hold prep's sum (fetch+load) and prep's tries (kticks/item), tries/item over all tiers
             fprintf(stderr, "[wtgpu profile] pass C in tiers (slice 0): walks settled by prep %llu, wide %llu, hard %llu; wide + hard tries by aperture size: bin items kticks/item total-Mticks\n",
                     p[kPassCTierSlot], p[kPassCTierSlot + 1], p[kPassCTierSlot + 2]);
             for (int b = 0; b < 16; ++b)
-                if (p[144 + b]) fprintf(stderr, "[wtgpu profile]   W %2d %8llu %10.1f %10.1f\n", b, p[144 + b], double(p[128 + b]) / p[144 + b] * 1e-3, double(p[128 + b]) * 1e-6);
+                if (p[kPassCProfWideWalks + b]) fprintf(stderr, "[wtgpu profile]   W %2d %8llu %10.1f %10.1f\n", b, p[kPassCProfWideWalks + b], double(p[kPassCProfWideTicks + b]) / p[kPassCProfWideWalks + b] * 1e-3, double(p[kPassCProfWideTicks + b]) * 1e-6);
         }
         fprintf(stderr, "[wtgpu profile] pass B by gathered scene edges: bin items kticks/item total-Mticks\n");
         for (int b = 0; b < 16; ++b)

@@ -233,7 +233,24 @@ WT_D uint32_t* pass_c_commit_queue(const launch_args_t& a) { return a.st.intd_qu
 // step's three readers of the list; and the next round's trace kernels rewrite the list before anything reads it again.
 constexpr uint32_t kOutcomeAccepted = 0x80000000u;   // (a try index is below kFsdMaxEdges x 1024 = 2^22)
 WT_D uint32_t* pass_c_outcome(const launch_args_t& a, uint32_t w) { return a.st.tris + (size_t)w * kTriListWords; }
+WT_D void pass_c_store_outcome(const launch_args_t& a, uint32_t w, const fsd_outcome_t& r) {
+    uint32_t* o = pass_c_outcome(a, w);
+    o[0] = r.acc ? (kOutcomeAccepted | r.t_acc) : 0u;
+    o[1] = __float_as_uint(r.x.x);
+    o[2] = __float_as_uint(r.x.y);
+    o[3] = __float_as_uint(r.f);
+}
+WT_D fsd_outcome_t pass_c_load_outcome(const launch_args_t& a, uint32_t w) {
+    const uint32_t* o = pass_c_outcome(a, w);
+    const uint32_t o0 = o[0];
+    return fsd_outcome_t{(o0 & kOutcomeAccepted) != 0u ? 1u : 0u, o0 & ~kOutcomeAccepted, vec2{__uint_as_float(o[1]), __uint_as_float(o[2])}, __uint_as_float(o[3])};
+}
 constexpr uint32_t kPrepTries = 8;   // tries of k_interact_c_prep: one per lane of a walk's group of eight
+// WTGPU_PROFILE=3, pass C by aperture size (index into st.counters + kNumCounters, + bin = floor(log2(segments)) < 16): walks, tries, clock ticks of
+// power sum + tries, of the commit and of fetch + load; the wide and hard tries of the tiers: ticks and walks
+constexpr size_t kPassCProfWalks = 8, kPassCProfTries = 24, kPassCProfTicks = 40, kPassCProfCommitTicks = 96, kPassCProfLoadTicks = 112, kPassCProfWideTicks = 128,
+                 kPassCProfWideWalks = 144;
+WT_D int pass_c_prof_bin(uint32_t n_edges) { return 31 - __clz((int)max(n_edges, 1u)); }
 // statistics of the tiers, behind the WTGPU_PROFILE slots proper (index into st.counters + kNumCounters): walks settled by the prep / wide / hard
 // kernel, pass-C walks, rounds with a pass-C queue / whose queue is no multiple of kPrepTries / is shorter, the lengths of the first such queues
 constexpr size_t kPassCTierSlot = 160, kPassCWalksSlot = 163, kPassCRoundsSlot = 164, kPassCQueueSlot = 168, kPassCQueueSlots = kProfSlots - kPassCQueueSlot;
