@@ -168,6 +168,38 @@ def test_a_tie_for_the_maximum_goes_to_the_lowest_pixel(scenes):
     assert sc.film_compare_host(a, 0, b, 0, mask=m)["argmax"][0] == 555
 
 
+EARLY, LATE = 3 * 256 + 17, 256 * 256 + 100      # at LEVELS: a pixel of chunk 3, and one of the last of the 257 chunks
+
+
+def late_tie_films(early):
+    """RGB films at LEVELS whose largest |d| = 2 of plane c is at pixel LATE + c and, with `early`, with the other sign at EARLY + c as well;
+    every 97th pixel differs by 0.25, so that every chunk has a candidate of its own.  On the device the 257 chunks are those of 260 wavefronts,
+    more records than the finish kernel's block has threads: the late pixel's is merged in its loop's second round (tests/test_gpu_film_compare.py)."""
+    w, h = LEVELS
+    a = (np.ones((h, w, 3)), np.ones((h, w)), np.zeros((h, w, 3)))
+    b = tuple(t.copy() for t in a)
+    v = b[0].reshape(h * w, 3)
+    v[::97] = 1.25
+    assert LATE // 256 == 256 and LATE + 2 < h * w and all(p % 97 for p in range(EARLY, EARLY + 3)) and all(p % 97 for p in range(LATE, LATE + 3))
+    for c in range(3):
+        v[LATE + c, c] = 3.0
+        if early:
+            v[EARLY + c, c] = -1.0
+    return a, b
+
+
+def test_a_late_maximum_and_a_tie_across_the_wavefronts_records(built, tmp_path):
+    """The maximum in the last chunk and its equal in chunk 3: argmax is the smaller pixel; without the early one, the late pixel."""
+    w, h = LEVELS
+    sc = stats_scene(tmp_path, 3, w, h)
+    for early in (True, False):
+        a, b = late_tie_films(early)
+        want = restate_compare(elements(3, 1, a, SPE_A, 0, False, False), elements(3, 1, b, SPE_A, 0, False, False), None, 1e-4)
+        assert want["argmax"] == [(EARLY if early else LATE) + c for c in range(3)] and want["max_abs"] == [2.0] * 3      # the restatement alone
+        for threads in (1, 5):
+            check_against_restatement(sc.film_compare_host(a, SPE_A, b, SPE_A, threads=threads), want, ("late tie", early, threads))
+
+
 def test_nothing_included(scenes):
     sc = scenes[3]
     mask = np.zeros((H, W), F32)

@@ -281,6 +281,37 @@ def test_host_twin_equals_the_restatement_over_two_levels(built, tmp_path):
     note_measured(f"films/{w}x{h}/P12", _one_film(stats_scene(tmp_path, 12, w, h), 12, w, h, 312, "two levels"))
 
 
+EARLY, LATE = 3 * 256 + 17, 256 * 256 + 100      # at LEVELS: a pixel of chunk 3, and one of the last of the 257 chunks
+
+
+def late_tie_films(early):
+    """Polarimetric RGB films at LEVELS whose largest degree of polarisation, 0.75, of channel c is at pixel LATE + c (1, 0, .75, 0) and, with
+    `early`, at EARLY + c as well, from other numbers (2, 0, 0, 1.5); dop is 0.25 elsewhere and 0.5 at every 97th pixel, so that every chunk has a
+    candidate of its own.  On the device the 257 chunks are those of 260 wavefronts, more records than the finish kernel's block has threads: the
+    late pixel's is merged in its loop's second round (tests/test_gpu_film_polar.py)."""
+    w, h = LEVELS
+    value = np.tile(np.array([1.0, 0.25, 0.0, 0.0]), (h * w, 3)).reshape(h * w, 3, 4)
+    value[::97, :, 1] = 0.5
+    assert LATE // 256 == 256 and LATE + 2 < h * w and all(p % 97 for p in range(EARLY, EARLY + 3)) and all(p % 97 for p in range(LATE, LATE + 3))
+    for c in range(3):
+        value[LATE + c, c] = (1.0, 0.0, 0.75, 0.0)
+        if early:
+            value[EARLY + c, c] = (2.0, 0.0, 0.0, 1.5)
+    return value.reshape(h, w, 12), np.ones((h, w)), np.zeros((h, w, 12))
+
+
+def test_a_late_maximum_and_a_tie_across_the_wavefronts_records(built, tmp_path):
+    """The maximum in the last chunk and its equal in chunk 3: argmax is the smaller pixel; without the early one, the late pixel."""
+    w, h = LEVELS
+    sc = stats_scene(tmp_path, 12, w, h)
+    for early in (True, False):
+        films = late_tie_films(early)
+        want = restate_polar(stokes_of(films, 3), False, None, 1.0, 0.0)
+        assert want["argmax"] == [(EARLY if early else LATE) + c for c in range(3)] and want["max_dop"] == [0.75] * 3      # the restatement alone
+        for threads in (1, 5):
+            check_against_restatement(sc.film_polar_host(*films, SPE, threads=threads), want, ("late tie", early, threads), None)
+
+
 def sweep_films(height, width):
     """An RGB polarimetric film of directions: (Q, U, V) = m (cos b cos a, cos b sin a, sin b), I = 2 m, with a over (-pi, pi], b over [-pi/2, pi/2] and
     m log-uniform from 1e-30 to 1e30 — 3 x pixels directions; the first pixels hold the borders of pol_atan2's reductions exactly."""

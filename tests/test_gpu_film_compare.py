@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_film_compare import FIELDS, NO_PIXEL, SPE_A, SPE_B, films_of, pairs
+from test_film_compare import EARLY, FIELDS, LATE, NO_PIXEL, SPE_A, SPE_B, films_of, late_tie_films, pairs
 from test_film_stats import F32, LEVELS, PLANES, checker, device_scenes, option_cases, same_bits, stats_scene
 from test_film_stats import to_device as _to_device
 
@@ -62,8 +62,18 @@ def test_device_equals_host_twin_on_many_chunks(scenes, P):
 
 @pytest.mark.parametrize("P", [3, 12])
 def test_device_equals_host_twin_over_two_levels(scenes, P):
-    """257 x 256: k_film_compare_finish goes round its loop twice, the second time over what the first wrote."""
+    """257 x 256: k_film_finish goes round its loop twice, the second time over what the first wrote."""
     _many_chunks(scenes, LEVELS, P)
+
+
+def test_a_late_maximum_and_a_tie_across_the_wavefronts_records(scenes):
+    """257 x 256: 257 chunks on 65 blocks, 260 wavefront records — k_film_finish's 256 threads go round the records twice.  The maximum is in the
+    last chunk (record 256, the second round) with its equal in chunk 3 (record 3): argmax is the smaller pixel; without the early one, the late."""
+    sc = scenes[LEVELS + (3,)]
+    for early in (True, False):
+        fa, fb = late_tie_films(early)
+        got = _same(sc, fa, _to_device(sc, fa), SPE_A, fb, _to_device(sc, fb), SPE_A, None, None, ("late tie", early))
+        assert got["argmax"].tolist() == [(EARLY if early else LATE) + c for c in range(3)] and got["max_abs"].tolist() == [2.0] * 3
 
 
 def _many_chunks(scenes, size, P):

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_film_polar import DERIVED, FIELDS, MAPS, NO_PIXEL, PICTURE_TMS, POLAR, SPE, THETA, polar_films
+from test_film_polar import DERIVED, EARLY, FIELDS, LATE, MAPS, NO_PIXEL, PICTURE_TMS, POLAR, SPE, THETA, late_tie_films, polar_films
 from test_film_stats import F32, LEVELS, checker, same_bits, stats_scene
 from test_film_stats import to_device as _to_device
 
@@ -81,8 +81,18 @@ def test_device_equals_host_twin_on_many_chunks(scenes, P):
 
 
 def test_device_equals_host_twin_over_two_levels(scenes):
-    """257 x 256: k_film_polar_finish goes round its loop twice, the second time over what the first wrote."""
+    """257 x 256: k_film_finish goes round its loop twice, the second time over what the first wrote."""
     _one_film(scenes, LEVELS, 12, 312)
+
+
+def test_a_late_maximum_and_a_tie_across_the_wavefronts_records(scenes):
+    """257 x 256: 257 chunks on 65 blocks, 260 wavefront records — k_film_finish's 256 threads go round the records twice.  The maximum is in the
+    last chunk (record 256, the second round) with its equal in chunk 3 (record 3): argmax is the smaller pixel; without the early one, the late."""
+    sc = scenes[LEVELS + (12,)]
+    for early in (True, False):
+        films = late_tie_films(early)
+        got = _same(sc, films, _to_device(sc, films), None, None, ("late tie", early))
+        assert got["argmax"].tolist() == [(EARLY if early else LATE) + c for c in range(3)] and got["max_dop"].tolist() == [0.75] * 3
 
 
 def test_the_measured_alternative_computes_the_same(built, tmp_path, monkeypatch):

@@ -71,7 +71,7 @@ def bench_film(label, reps):
            "rel_l2": [float(x) for x in n["rel_l2"]], "n_differ": [int(x) for x in n["n_differ"]]}
     out.update(alternate({"parent": strip(parent), "new": strip(new)}, reps))
     out["new_back_to_back"] = alternate({"new": strip(new)}, reps)["new"]     # the new path alone, the GPU kept busy
-    # one call = k_film_compare + k_film_compare_finish + the copy of the records, between two device events
+    # one call = k_film_compare + k_film_finish + the copy of the records, between two device events
     lum = planes == 3
     passes = alternate({"records": lambda: {"ms": event_ms(lambda: sc.film_compare_device(a, spe, b, spe))[0]},
                          "records_luminance": lambda: {"ms": event_ms(lambda: sc.film_compare_device(a, spe, b, spe, luminance=lum))[0]},

@@ -96,7 +96,7 @@ def bench_film(reps):
            "mean_dop": [float(x) for x in n["mean_dop"]], "n_over": [int(x) for x in n["n_over"]]}
     out.update(alternate({"parent": strip(parent), "new": strip(new)}, reps))
     out["new_back_to_back"] = alternate({"new": strip(new)}, reps)["new"]     # the new path alone, the GPU kept busy
-    # one call = k_film_polar + k_film_polar_finish + the copy of the records, between two device events; k_develop beside it
+    # one call = k_film_polar + k_film_finish + the copy of the records, between two device events; k_develop beside it
     lum = planes == 3
     polar = lambda **kw: (lambda: {"ms": event_ms(lambda: sc.film_polar_device(*films, spe, **kw))[0]})
     passes = alternate({"records": polar(), "records_luminance": polar(luminance=lum), "records_and_two_maps": polar(maps=("dop", "aolp")),

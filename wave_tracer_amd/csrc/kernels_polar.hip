@@ -2,40 +2,14 @@
 // a user of a polarimetric film had to download twelve planes of three f64 accumulators for.  k_film_polar reads the films once, develops in
 // registers (the developed values never reach memory), and gives per plane — each channel, and the luminance's Stokes vector where asked for —
 // the chunk sums of the six Stokes sums in the fixed order of wt/film_stats.h, one record per wavefront with its counts and its largest degree
-// of polarisation, the maps asked for and the false-colour picture of one plane; k_film_polar_finish reduces the chunk sums level after level
-// and merges the wavefronts' records.  No atomics: every field is the same whatever the schedule.  The arithmetic is
+// of polarisation, the maps asked for and the false-colour picture of one plane; kernels_film.h's k_film_finish reduces the chunk sums level
+// after level and merges the wavefronts' records.  No atomics: every field is the same whatever the schedule.  The arithmetic is
 // wt/film_polar.h's, shared with the host twin at the end of the file, and calls no libm function: every count, the maximum and its pixel, the
 // six sums and the maps — the two angles among them — are the same on both sides, bit for bit.  No render kernel is compiled here.
-#include <cstring>
-#include <mutex>
-
 #include "kernels_film.h"
 #include "wt/film_polar.h"
 
 namespace wtk {
-
-// A lane's u32 counts cannot overflow: it meets four pixels per chunk and a wavefront takes at most kFilmMaxChunksPerWave chunks, so a
-// wavefront's counts stay below 64 x 4 x 2^20 = 2^28.
-constexpr uint32_t kPolarBlocksPerCU = 8;
-
-// what a wavefront leaves behind for one plane
-struct fp_wave_rec_t {
-    double max_dop;
-    unsigned long long pixel;
-    uint32_t n, nonfinite, dark, over;
-};
-static_assert(sizeof(fp_wave_rec_t) == 32, "fp_wave_rec_t");
-
-// the largest degree of polarisation of a wavefront's lanes, by the distances of kernels_film.h's reductions
-WT_D fc_best_t fp_wave_best(fc_best_t m) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const double v = __shfl_down(m.v, d, 64);
-        const unsigned long long p = __shfl_down(m.pixel, d, 64);
-        fc_best_merge(m, v, p);
-    }
-    return m;
-}
 
 // a pixel's maps of one plane, the chosen ones in the order of their bits; 0 for a pixel the mask excludes
 WT_HD void fp_store_maps(float* maps, uint64_t pixel, uint32_t plane, uint32_t planes, const film_polar_args_t& a, const fp_plane_t& r, bool included) {
@@ -59,7 +33,7 @@ WT_HD void fp_store_maps(float* maps, uint64_t pixel, uint32_t plane, uint32_t p
 template <uint32_t C, bool kLum, bool kStaged>
 __global__ void __launch_bounds__(kFilmBlock) k_film_polar(const double* __restrict__ value, const double* __restrict__ weight, const double* __restrict__ light, double sl,
                                                            film_polar_args_t a, const float* __restrict__ mask, uint64_t npix, double* __restrict__ sums,
-                                                           uint64_t sums_stride, fp_wave_rec_t* __restrict__ wrec, float* __restrict__ maps, void* __restrict__ picture) {
+                                                           uint64_t sums_stride, film_wave_rec_t* __restrict__ wrec, float* __restrict__ maps, void* __restrict__ picture) {
     constexpr uint32_t NP = C + (kLum ? 1u : 0u), P = C * 4u;
     __shared__ __attribute__((aligned(16))) float lds_x[kStaged ? kFilmWaves * kFsChunk * P : 4];
     float* const xs = lds_x + (kStaged ? (threadIdx.x >> 6) * kFsChunk * P : 0u);   // the wavefront's own part
@@ -120,72 +94,15 @@ __global__ void __launch_bounds__(kFilmBlock) k_film_polar(const double* __restr
                 }
             }
 #pragma unroll
-            for (uint32_t k = 0; k < kFpSums; ++k) {
-                const double v = chunk_sum(t[k][0], t[k][1], t[k][2], t[k][3]);
-                if (lane == 0) sums[(c * kFpSums + k) * sums_stride + chunk] = v;
-            }
+            for (uint32_t k = 0; k < kFpSums; ++k) film_store_chunk_sum(sums + (c * kFpSums + k) * sums_stride + chunk, t[k]);
         }
         if (kStaged) {   // the next chunk's elements go where this one's were read
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
     }
-    // every wavefront of the grid leaves its records, also one that met no chunk: the finish kernel reads them all
-    const unsigned long long n_all = wave_sum_u64(n_included);
-#pragma unroll
-    for (uint32_t c = 0; c < NP; ++c) {
-        const fc_best_t m = fp_wave_best(best[c]);
-        const unsigned long long nf = wave_sum_u64(n_nonfinite[c]), dk = wave_sum_u64(n_dark[c]), ov = wave_sum_u64(n_over[c]);
-        if (lane == 0) wrec[c * n_waves + wave] = fp_wave_rec_t{m.v, m.pixel, (uint32_t)n_all, (uint32_t)nf, (uint32_t)dk, (uint32_t)ov};
-    }
+    film_store_wave_recs(wrec, n_waves, wave, n_included, n_nonfinite, n_dark, n_over, best);
 }
-
-// ---- k_film_polar_finish: kFpSums + 1 blocks per plane -------------------------------------------------------------------------------------------
-// Block (c, k < kFpSums) reduces the chunk sums of sum k of plane c (film_reduce_levels).  Block (c, kFpSums) merges the wavefronts' records of
-// plane c: integer counts, and a maximum whose order is total.  Every field of the record is written, so nobody has to clear it.
-__global__ void __launch_bounds__(kFilmBlock) k_film_polar_finish(film_polar_rec_t* __restrict__ rec, double* sums, uint64_t sums_stride, uint64_t n_chunks,
-                                                                  const fp_wave_rec_t* __restrict__ wrec, uint64_t n_waves) {
-    const uint32_t lane = threadIdx.x & 63u, c = blockIdx.x / (kFpSums + 1u), k = blockIdx.x % (kFpSums + 1u);
-    if (k < kFpSums) {
-        const double sum = film_reduce_levels(sums + (c * kFpSums + k) * sums_stride, n_chunks);
-        if (threadIdx.x == 0) rec[c].sum[k] = sum;
-        return;
-    }
-    __shared__ double s_best_v[kFilmWaves];
-    __shared__ unsigned long long s_best_pixel[kFilmWaves];
-    __shared__ unsigned long long s_count[kFilmWaves][4];
-    fc_best_t m;
-    unsigned long long cnt[4] = {0ull, 0ull, 0ull, 0ull};
-    for (uint64_t w = threadIdx.x; w < n_waves; w += kFilmBlock) {
-        const fp_wave_rec_t r = wrec[c * n_waves + w];
-        fc_best_merge(m, r.max_dop, r.pixel);
-        cnt[0] += r.n, cnt[1] += r.nonfinite, cnt[2] += r.dark, cnt[3] += r.over;
-    }
-    m = fp_wave_best(m);
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) cnt[i] = wave_sum_u64(cnt[i]);
-    if (lane == 0) {
-        s_best_v[threadIdx.x >> 6] = m.v;
-        s_best_pixel[threadIdx.x >> 6] = m.pixel;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) s_count[threadIdx.x >> 6][i] = cnt[i];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (uint32_t w = 1; w < kFilmWaves; ++w) {
-            fc_best_merge(m, s_best_v[w], s_best_pixel[w]);
-            for (uint32_t i = 0; i < 4; ++i) cnt[i] += s_count[w][i];
-        }
-        film_polar_rec_t& r = rec[c];
-        r.n = cnt[0], r.n_nonfinite = cnt[1], r.n_dark = cnt[2], r.n_over = cnt[3];
-        r.max_dop = m.v;
-        r.argmax = m.pixel;
-    }
-}
-
-// kPolarBlocksPerCU blocks per CU at most (1920 x 1088: 8160 chunks on 2040 blocks, one per wavefront)
-static uint32_t film_polar_blocks(uint64_t npix, uint32_t n_cus) { return film_grid_blocks(npix, n_cus, kPolarBlocksPerCU); }
-size_t film_polar_wave_bytes(uint64_t npix, uint32_t n_cus) { return (size_t)kFsMaxPlanes * film_polar_blocks(npix, n_cus) * kFilmWaves * sizeof(fp_wave_rec_t); }
 
 int film_polar_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
                       uint32_t flags, const film_polar_args_t& a, uint32_t staged, const float* d_mask, void* d_rec, double* d_sums, void* d_wave, float* d_maps,
@@ -194,11 +111,9 @@ int film_polar_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, co
     if (npix == 0 || film_stokes(sn) != 4) return (int)hipErrorInvalidValue;
     const double sl = develop_scale(spe);
     const bool lum = (flags & FP_LUMINANCE) != 0;
-    const uint64_t n_chunks = fs_chunks(npix), stride = fs_scratch_len(npix);
-    const uint32_t blocks = film_polar_blocks(npix, n_cus);
-    const uint64_t n_waves = (uint64_t)blocks * kFilmWaves;
-    film_polar_rec_t* rec = static_cast<film_polar_rec_t*>(d_rec);
-    fp_wave_rec_t* wrec = static_cast<fp_wave_rec_t*>(d_wave);
+    const uint64_t stride = fs_scratch_len(npix);
+    const uint32_t blocks = film_rec_blocks(npix, n_cus);
+    film_wave_rec_t* wrec = static_cast<film_wave_rec_t*>(d_wave);
     // The staged form unless the knob says otherwise.  On the MI355X (tools/bench_film_polar.py, profiles/film_polar_bench.json: the polarimetric room
     // film, 1920 x 1088, P = 12, 418 MB read; median of 15 calls each, alternated, between device events, the finish kernel and the copy of the
     // records included): records alone 0.220 ms staged against 0.279 ms with every lane loading its own pixels (0.207 against 0.286 in an earlier
@@ -213,68 +128,36 @@ int film_polar_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, co
         }))
         return (int)hipErrorInvalidValue;
     if (const hipError_t e = hipGetLastError()) return (int)e;
-    hipLaunchKernelGGL(k_film_polar_finish, dim3((sn.channels + (lum ? 1u : 0u)) * (kFpSums + 1u)), dim3(kFilmBlock), 0, stream, rec, d_sums, stride, n_chunks, wrec, n_waves);
-    return (int)hipGetLastError();
+    return film_finish_launch<kFpSums>(stream, sn.channels + (lum ? 1u : 0u), d_rec, d_sums, npix, d_wave, blocks);
 }
 
-// ---- the host twin: the same wt/film_polar.h functions on host threads, one task per chunk; the counts are integers, a chunk's sums are one
-// thread's and the maximum's order is total, so the result does not depend on the number of threads --------------------------------------------
+// ---- the host twin: the same wt/film_polar.h functions per pixel in kernels_film.h's film_records_host -------------------------------------------
 void film_polar_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, uint32_t flags, const film_polar_args_t& a,
                      const float* mask, uint32_t n_threads, void* out_rec, float* maps, void* picture) {
     const uint32_t C = sn.channels, P = C * 4u, NP = C + ((flags & FP_LUMINANCE) ? 1u : 0u);
-    const uint64_t npix = (uint64_t)sn.width * sn.height, n_chunks = fs_chunks(npix), stride = fs_scratch_len(npix);
+    const uint64_t npix = (uint64_t)sn.width * sn.height;
     const double sl = develop_scale(spe);
-    film_polar_rec_t* rec = static_cast<film_polar_rec_t*>(out_rec);
-    std::memset(rec, 0, NP * sizeof(film_polar_rec_t));
-    std::vector<double> sums((size_t)NP * kFpSums * std::max<uint64_t>(stride, 1), 0.0);
-    std::vector<fc_best_t> best(NP);
-    std::mutex merge;
-    on_threads(n_chunks, n_threads, [&](auto claim) {
-        std::vector<film_polar_rec_t> my(NP, film_polar_rec_t{});
-        std::vector<fc_best_t> my_best(NP);
-        std::vector<double> t((size_t)kFsMaxPlanes * kFpSums * kFsChunk);
-        for (uint64_t chunk = claim(); chunk < n_chunks; chunk = claim()) {
-            for (uint32_t i = 0; i < kFsChunk; ++i) {
-                const uint64_t p = chunk * kFsChunk + i;
-                const bool included = p < npix && (!mask || mask[p] > 0.f);
-                float x[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                if (p < npix)
-                    for (uint32_t k = 0; k < P; ++k) x[k] = develop_plane(value[p * P + k], weight[p], light[p * P + k], sl);
-                for (uint32_t c = 0; c < NP; ++c) {
-                    double S[4];
-                    fp_stokes(x, c, C, S);
-                    const fp_plane_t r = fp_plane(S[0], S[1], S[2], S[3], included, a.c2, a.s2);
-                    for (uint32_t k = 0; k < kFpSums; ++k) t[((size_t)c * kFpSums + k) * kFsChunk + i] = r.add[k];
-                    if (p < npix) {
-                        if (maps) fp_store_maps(maps, p, c, NP, a, r, included);
-                        if (picture && c == a.picture_plane) {
-                            float rgb[3];
-                            fp_colour(a, (float)S[0], r, rgb);
-                            tm_store(picture, p, a.format, mask ? 4u : 3u, rgb, mask ? mask[p] : 0.f);
-                        }
-                    }
-                    if (!included) continue;
-                    ++my[c].n;
-                    my[c].n_nonfinite += r.nonfinite, my[c].n_dark += r.dark, my[c].n_over += r.over;
-                    fp_best_take(my_best[c], r, p);
-                }
-            }
-            for (uint32_t c = 0; c < NP; ++c)
-                for (uint32_t k = 0; k < kFpSums; ++k) sums[((size_t)c * kFpSums + k) * stride + chunk] = fs_chunk_sum(&t[((size_t)c * kFpSums + k) * kFsChunk]);
-        }
-        std::lock_guard<std::mutex> lock(merge);
+    film_records_host<kFpSums>(npix, NP, mask, n_threads, static_cast<film_polar_rec_t*>(out_rec), [&](uint64_t p, bool included, film_element_t<kFpSums>* e) {
+        float x[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (p < npix)
+            for (uint32_t k = 0; k < P; ++k) x[k] = develop_plane(value[p * P + k], weight[p], light[p * P + k], sl);
         for (uint32_t c = 0; c < NP; ++c) {
-            film_polar_rec_t& r = rec[c];
-            r.n += my[c].n, r.n_nonfinite += my[c].n_nonfinite, r.n_dark += my[c].n_dark, r.n_over += my[c].n_over;
-            fc_best_merge(best[c], my_best[c].v, my_best[c].pixel);
+            double S[4];
+            fp_stokes(x, c, C, S);
+            const fp_plane_t r = fp_plane(S[0], S[1], S[2], S[3], included, a.c2, a.s2);
+            e[c].count[0] = r.nonfinite, e[c].count[1] = r.dark, e[c].count[2] = r.over;
+            e[c].best = fc_best_t{};
+            fp_best_take(e[c].best, r, p);
+            for (uint32_t k = 0; k < kFpSums; ++k) e[c].add[k] = r.add[k];
+            if (p >= npix) continue;
+            if (maps) fp_store_maps(maps, p, c, NP, a, r, included);
+            if (picture && c == a.picture_plane) {
+                float rgb[3];
+                fp_colour(a, (float)S[0], r, rgb);
+                tm_store(picture, p, a.format, mask ? 4u : 3u, rgb, mask ? mask[p] : 0.f);
+            }
         }
     });
-    // the levels above the chunks (k_film_polar_finish)
-    for (uint32_t c = 0; c < NP; ++c) {
-        for (uint32_t k = 0; k < kFpSums; ++k) rec[c].sum[k] = fs_reduce_levels(sums.data() + ((size_t)c * kFpSums + k) * stride, n_chunks);
-        rec[c].max_dop = best[c].v;
-        rec[c].argmax = best[c].pixel;
-    }
 }
 
 }   // namespace wtk

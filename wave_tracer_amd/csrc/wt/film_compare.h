@@ -27,12 +27,16 @@ namespace wt {
 enum film_compare_sum_e : uint32_t { FC_SUM_ABS = 0, FC_SUM_SQ = 1, FC_SUM_A_SQ = 2, FC_SUM_B_SQ = 3, FC_SUM_REL = 4, kFcSums = 5 };
 constexpr unsigned long long kFcNoPixel = ~0ull;   // argmax where nothing differs
 
-// wtgpu_film_compare as the kernels fill it
-struct film_compare_rec_t {
-    unsigned long long n, n_nonfinite, n_nonfinite_mismatch, n_differ, argmax;
-    double max_abs;
-    double sum[kFcSums];
+// The record of a "sums + counts + best" pass over a film as the kernels and the host twins fill it (kernels_film.h): n members, three counts
+// of classes, the largest value met and the pixel that has it, K sums.  wtgpu_film_compare (count: n_nonfinite, n_nonfinite_mismatch, n_differ;
+// best: max_abs) and, with K = kFpSums, wtgpu_film_polar (n_nonfinite, n_dark, n_over; max_dop) are this: wtgpu_film.hip asserts the layout.
+template <uint32_t K>
+struct film_best_rec_t {
+    unsigned long long n, count[3], argmax;
+    double best;
+    double sum[K];
 };
+using film_compare_rec_t = film_best_rec_t<kFcSums>;
 static_assert(sizeof(film_compare_rec_t) == 88, "wtgpu_film_compare");
 
 WT_HD bool fc_finite(float x) {

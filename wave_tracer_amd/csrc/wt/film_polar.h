@@ -36,12 +36,8 @@ enum film_polar_flag_e : uint32_t { FP_LUMINANCE = FS_LUMINANCE };
 enum film_polar_map_e : uint32_t { FP_DOLP = 0, FP_DOP = 1, FP_DOCP = 2, FP_AOLP = 3, FP_CHI = 4, FP_ANALYSER = 5, kFpMaps = 6 };
 enum film_polar_sum_e : uint32_t { FP_SUM_I = 0, FP_SUM_Q = 1, FP_SUM_U = 2, FP_SUM_V = 3, FP_SUM_LIN = 4, FP_SUM_POL = 5, kFpSums = 6 };
 
-// wtgpu_film_polar as the kernels fill it
-struct film_polar_rec_t {
-    unsigned long long n, n_nonfinite, n_dark, n_over, argmax;
-    double max_dop;
-    double sum[kFpSums];
-};
+// wtgpu_film_polar as the kernels fill it (wt/film_compare.h: count is n_nonfinite, n_dark, n_over; best is max_dop)
+using film_polar_rec_t = film_best_rec_t<kFpSums>;
 static_assert(sizeof(film_polar_rec_t) == 96, "wtgpu_film_polar");
 
 // what a kernel is told (by value)

@@ -1,6 +1,8 @@
 // wave_tracer_amd — the entry points that read films: develop, the tonemap spec / device / host calls (kernels_develop.hip), film statistics
 // (kernels_stats.hip), film comparison (kernels_compare.hip), the polarisation view (kernels_polar.hip) and the denoiser of two half-films (kernels_denoise.hip); what they check of a film
 // and keep with the scene between calls.
+#include <cstddef>
+
 #include "wtgpu_host.h"
 #include "wt/tonemap.h"
 #include "wt/film_stats.h"
@@ -36,6 +38,44 @@ static int film_scratch_alloc(wtgpu_scene* s, film_scratch_t& f, size_t d_bytes,
 void film_scratch_free(film_scratch_t& f) {   // (the device's parts are freed with dev_allocs)
     if (f.h_block) (void)hipHostFree(f.h_block);
     f = film_scratch_t{};
+}
+
+// What the device entry of a film pass does after its own spec checks: the two refusals all of them share, then body(stream, npix) with the
+// scene's device current.  `what` opens the message.
+template <class F>
+static int film_on_device(wtgpu_scene* s, void* stream_, const char* what, F&& body) {
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    const uint64_t npix = (uint64_t)s->host.sensor.width * s->host.sensor.height;
+    if (npix == 0) return fail(WTGPU_ERR_INVALID, std::string(what) + ": the film has no pixels");
+    device_guard_t guard(s->device);
+    return body(static_cast<hipStream_t>(stream_), npix);
+}
+// The records at the head of a feature's block — rec_bytes of them, and whatever else the first block_bytes hold — come back through the pinned
+// copy.  The call waits for its own result, so the block is free again when it returns.
+static int film_records_back(film_scratch_t& f, hipStream_t stream, void* out, size_t rec_bytes, size_t block_bytes = 0) {
+    HIP_CHECK(hipMemcpyAsync(f.h_block, f.d_block, std::max(rec_bytes, block_bytes), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    std::memcpy(out, f.h_block, rec_bytes);
+    return WTGPU_OK;
+}
+// The scratch of a records pass of K sums (compare, polar), allocated at first use: the records with the wavefronts' records behind them, the
+// pinned copy of the former, the chunk sums (all levels, kFsMaxPlanes planes of K sums).
+template <uint32_t K>
+constexpr size_t kFilmRecBytes = kFsMaxPlanes * sizeof(film_best_rec_t<K>);
+template <uint32_t K>
+static int film_rec_scratch(wtgpu_scene* s, film_scratch_t& f, uint64_t npix) {
+    static_assert(kFilmRecBytes<K> % 32 == 0, "the wavefronts' records (32 bytes each) follow the records in one block");
+    return film_scratch_alloc(s, f, kFilmRecBytes<K> + film_rec_wave_bytes(npix, s->n_cus), kFilmRecBytes<K>, (size_t)kFsMaxPlanes * K * fs_scratch_len(npix));
+}
+// a host twin's call: what it throws (an allocation) is the call's error
+template <class F>
+static int film_on_host(F&& twin) {
+    try {
+        twin();
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
 }
 
 extern "C" {
@@ -86,6 +126,16 @@ static bool same_name(const std::string& a, const char* b) {
         if (std::tolower((unsigned char)a[i]) != b[i]) return false;
     return true;
 }
+// What an operator's choice and numbers say by themselves (the tonemap calls' and the polarisation picture's).  `what` opens the messages about
+// the choice, `loader` those worded as the reference's operator loader words them.
+static int tonemap_op_check(int32_t op, int32_t mode, float gamma, float db_min, float db_max, const std::string& what, const std::string& loader) {
+    if (op == TM_FUNCTION) return fail(WTGPU_ERR_INVALID, what + "the 'function' operator is not supported (the expression is read from the scene file, not evaluated)");
+    if (op < TM_LINEAR || op > TM_FUNCTION) return fail(WTGPU_ERR_INVALID, what + "operator 0 (linear), 1 (gamma), 2 (sRGB) or 3 (dB) expected");
+    if (mode < TM_SELECT || mode > TM_COLOURMAP) return fail(WTGPU_ERR_INVALID, what + "mode 0 (select), 1 (normal) or 2 (colourmap) expected");
+    if (op == TM_GAMMA && !(gamma > 0.f)) return fail(WTGPU_ERR_INVALID, loader + "'gamma' must be positive");
+    if (op == TM_DB && !(db_max - db_min > 0.f)) return fail(WTGPU_ERR_INVALID, loader + "expected valid 'db' range to be provided");
+    return WTGPU_OK;
+}
 // The operator a tonemap call uses after the checks both forms share: `tm` (NULL: the scene's own spec, whose map must be one the library can
 // tabulate), the Stokes component, the format.  args.table points at the caller's table or into `own` (host memory), or is null when the mode
 // sends nothing through a map.
@@ -98,11 +148,7 @@ static int tonemap_args_for(const wtgpu_scene* s, const wtgpu_tonemap* tm, uint3
     (void)wtgpu_scene_tonemap_spec(s, &spec);
     const int32_t op = tm ? tm->op : spec.op, mode = tm ? tm->mode : spec.mode;
     const float gamma = tm ? tm->gamma : spec.gamma, db_min = tm ? tm->db_min : spec.db_min, db_max = tm ? tm->db_max : spec.db_max;
-    if (op == TM_FUNCTION) return fail(WTGPU_ERR_INVALID, "tonemap: the 'function' operator is not supported (the expression is read from the scene file, not evaluated)");
-    if (op < TM_LINEAR || op > TM_FUNCTION) return fail(WTGPU_ERR_INVALID, "tonemap: operator 0 (linear), 1 (gamma), 2 (sRGB) or 3 (dB) expected");
-    if (mode < TM_SELECT || mode > TM_COLOURMAP) return fail(WTGPU_ERR_INVALID, "tonemap: mode 0 (select), 1 (normal) or 2 (colourmap) expected");
-    if (op == TM_GAMMA && !(gamma > 0.f)) return fail(WTGPU_ERR_INVALID, "(tonemap operator loader) 'gamma' must be positive");
-    if (op == TM_DB && !(db_max - db_min > 0.f)) return fail(WTGPU_ERR_INVALID, "(tonemap operator loader) expected valid 'db' range to be provided");
+    if (const int rc = tonemap_op_check(op, mode, gamma, db_min, db_max, "tonemap: ", "(tonemap operator loader) ")) return rc;
     args.op = op;
     args.mode = mode;
     args.inv_gamma = 1.f / gamma;
@@ -170,12 +216,7 @@ int wtgpu_tonemap_host(const wtgpu_scene* s, const double* value, const double* 
     tonemap_args_t args{};
     std::vector<float> own;
     if (const int rc = tonemap_args_for(s, tm, stokes_component, format, args, own)) return rc;
-    try {
-        develop_tonemap_host(s->host.sensor, value, weight, light, spe, args, stokes_component, mask, format, n_threads, out);
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
+    return film_on_host([&] { develop_tonemap_host(s->host.sensor, value, weight, light, spe, args, stokes_component, mask, format, n_threads, out); });
 }
 
 // ---- film statistics (kernels_stats.hip; wt/film_stats.h) -----------------------------------------------------------------------------------
@@ -212,29 +253,22 @@ int wtgpu_film_stats_device(wtgpu_scene* s, void* stream_, const double* d_value
     float edges[kFsMaxBins + 1];
     if (const int rc = film_stats_edges_for(spec, edges)) return rc;
     if (const int rc = film_planes_for(s, "film_stats", spec->stokes_component, spec->flags, planes)) return rc;
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    const sensor_t& sn = s->host.sensor;
-    const uint64_t npix = (uint64_t)sn.width * sn.height;
-    if (npix == 0) return fail(WTGPU_ERR_INVALID, "film_stats: the film has no pixels");
-    device_guard_t guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // first use: the block, its pinned copy, the chunk sums of this scene's film (all levels, kFsMaxPlanes planes)
-    film_scratch_t& f = s->fs;
-    if (const int rc = film_scratch_alloc(s, f, kFsBlockBytes, kFsBlockBytes, (size_t)kFsMaxPlanes * fs_scratch_len(npix))) return rc;
-    // The call waits for its own result below, so the block is free again when it returns.
-    const size_t result_bytes = kFsRecBytes + (size_t)planes * spec->bins * sizeof(uint64_t), edge_bytes = (spec->bins + 1) * sizeof(float);
-    std::memcpy(f.h_block + kFsEdgeOffset, edges, edge_bytes);
-    HIP_CHECK(hipMemcpyAsync(f.d_block + kFsEdgeOffset, f.h_block + kFsEdgeOffset, edge_bytes, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemsetAsync(f.d_block, 0, result_bytes, stream));
-    const int e = film_stats_launch(sn, stream, s->n_cus, d_value, d_weight, d_light, spe, spec->stokes_component, spec->flags, d_mask,
-                                    reinterpret_cast<const float*>(f.d_block + kFsEdgeOffset), spec->bins, f.d_block, reinterpret_cast<unsigned long long*>(f.d_block + kFsRecBytes),
-                                    f.d_sums);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_stats: ") + hipGetErrorString((hipError_t)e));
-    HIP_CHECK(hipMemcpyAsync(f.h_block, f.d_block, result_bytes, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    std::memcpy(out, f.h_block, planes * sizeof(wtgpu_film_stats));
-    if (spec->bins) std::memcpy(hist, f.h_block + kFsRecBytes, (size_t)planes * spec->bins * sizeof(uint64_t));
-    return WTGPU_OK;
+    return film_on_device(s, stream_, "film_stats", [&](hipStream_t stream, uint64_t npix) -> int {
+        // first use: the block, its pinned copy, the chunk sums of this scene's film (all levels, kFsMaxPlanes planes)
+        film_scratch_t& f = s->fs;
+        if (const int rc = film_scratch_alloc(s, f, kFsBlockBytes, kFsBlockBytes, (size_t)kFsMaxPlanes * fs_scratch_len(npix))) return rc;
+        const size_t hist_bytes = (size_t)planes * spec->bins * sizeof(uint64_t), edge_bytes = (spec->bins + 1) * sizeof(float);
+        std::memcpy(f.h_block + kFsEdgeOffset, edges, edge_bytes);
+        HIP_CHECK(hipMemcpyAsync(f.d_block + kFsEdgeOffset, f.h_block + kFsEdgeOffset, edge_bytes, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemsetAsync(f.d_block, 0, kFsRecBytes + hist_bytes, stream));
+        const int e = film_stats_launch(s->host.sensor, stream, s->n_cus, d_value, d_weight, d_light, spe, spec->stokes_component, spec->flags, d_mask,
+                                        reinterpret_cast<const float*>(f.d_block + kFsEdgeOffset), spec->bins, f.d_block,
+                                        reinterpret_cast<unsigned long long*>(f.d_block + kFsRecBytes), f.d_sums);
+        if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_stats: ") + hipGetErrorString((hipError_t)e));
+        if (const int rc = film_records_back(f, stream, out, planes * sizeof(wtgpu_film_stats), kFsRecBytes + hist_bytes)) return rc;
+        if (spec->bins) std::memcpy(hist, f.h_block + kFsRecBytes, hist_bytes);
+        return WTGPU_OK;
+    });
 }
 int wtgpu_film_stats_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_film_stats_spec* spec,
                           const float* mask, uint32_t n_threads, wtgpu_film_stats* out, uint64_t* hist) {
@@ -243,25 +277,27 @@ int wtgpu_film_stats_host(const wtgpu_scene* s, const double* value, const doubl
     float edges[kFsMaxBins + 1];
     if (const int rc = film_stats_edges_for(spec, edges)) return rc;
     if (const int rc = film_planes_for(s, "film_stats", spec->stokes_component, spec->flags, planes)) return rc;
-    try {
+    return film_on_host([&] {
         film_stats_host(s->host.sensor, value, weight, light, spe, spec->stokes_component, spec->flags, mask, edges, spec->bins, n_threads, out,
                         reinterpret_cast<unsigned long long*>(hist));
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
+    });
 }
 
 // ---- film comparison (kernels_compare.hip; wt/film_compare.h) -------------------------------------------------------------------------------
-static_assert(sizeof(wtgpu_film_compare) == sizeof(film_compare_rec_t), "the kernels' record is wtgpu_film_compare");
+// wtgpu_film_compare and wtgpu_film_polar are film_best_rec_t (wt/film_compare.h): n, three counts, argmax, the maximum, the sums
+#define FILM_BEST_REC_IS(T, K, first_count, best_, first_sum)                                                                                                    \
+    static_assert(sizeof(T) == sizeof(film_best_rec_t<K>) && offsetof(T, n) == offsetof(film_best_rec_t<K>, n) &&                                               \
+                      offsetof(T, first_count) == offsetof(film_best_rec_t<K>, count) && offsetof(T, argmax) == offsetof(film_best_rec_t<K>, argmax) &&         \
+                      offsetof(T, best_) == offsetof(film_best_rec_t<K>, best) && offsetof(T, first_sum) == offsetof(film_best_rec_t<K>, sum),                  \
+                  "the kernels' record is " #T)
+FILM_BEST_REC_IS(wtgpu_film_compare, kFcSums, n_nonfinite, max_abs, sum_abs);
+FILM_BEST_REC_IS(wtgpu_film_polar, kFpSums, n_nonfinite, max_dop, sum_i);
 // what a spec says by itself and against the scene's film; planes: records per call
 static int film_compare_check(const wtgpu_scene* s, const wtgpu_film_compare_spec* spec, uint32_t& planes) {
     if (spec->flags & ~(FS_ABS | FS_LUMINANCE)) return fail(WTGPU_ERR_INVALID, "film_compare: flags 1 (ABS) and 2 (LUMINANCE) expected");
     if (!std::isfinite(spec->eps) || !(spec->eps > 0.0)) return fail(WTGPU_ERR_INVALID, "film_compare: a finite eps > 0 expected");
     return film_planes_for(s, "film_compare", spec->stokes_component, spec->flags, planes);
 }
-constexpr size_t kFcRecBytes = kFsMaxPlanes * sizeof(film_compare_rec_t);
-static_assert(kFcRecBytes % 32 == 0, "the wavefronts' records (32 bytes each) follow the records in one block");
 
 int wtgpu_film_compare_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
                               const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec, const float* d_mask,
@@ -269,25 +305,14 @@ int wtgpu_film_compare_device(wtgpu_scene* s, void* stream_, const double* a_val
     if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
     uint32_t planes = 0;
     if (const int rc = film_compare_check(s, spec, planes)) return rc;
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    const sensor_t& sn = s->host.sensor;
-    const uint64_t npix = (uint64_t)sn.width * sn.height;
-    if (npix == 0) return fail(WTGPU_ERR_INVALID, "film_compare: the film has no pixels");
-    device_guard_t guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // first use: the records with the wavefronts' records behind them, the pinned copy of the former, the chunk sums (all levels, kFsMaxPlanes
-    // planes of kFcSums sums)
-    film_scratch_t& f = s->fc;
-    if (const int rc = film_scratch_alloc(s, f, kFcRecBytes + film_compare_wave_bytes(npix, s->n_cus), kFcRecBytes, (size_t)kFsMaxPlanes * kFcSums * fs_scratch_len(npix)))
-        return rc;
-    // The call waits for its own result below, so the block is free again when it returns.
-    const int e = film_compare_launch(sn, stream, s->n_cus, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec->stokes_component, spec->flags, spec->eps,
-                                      d_mask, f.d_block, f.d_sums, f.d_block + kFcRecBytes, d_diff);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_compare: ") + hipGetErrorString((hipError_t)e));
-    HIP_CHECK(hipMemcpyAsync(f.h_block, f.d_block, planes * sizeof(film_compare_rec_t), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    std::memcpy(out, f.h_block, planes * sizeof(wtgpu_film_compare));
-    return WTGPU_OK;
+    return film_on_device(s, stream_, "film_compare", [&](hipStream_t stream, uint64_t npix) -> int {
+        film_scratch_t& f = s->fc;
+        if (const int rc = film_rec_scratch<kFcSums>(s, f, npix)) return rc;
+        const int e = film_compare_launch(s->host.sensor, stream, s->n_cus, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec->stokes_component,
+                                          spec->flags, spec->eps, d_mask, f.d_block, f.d_sums, f.d_block + kFilmRecBytes<kFcSums>, d_diff);
+        if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_compare: ") + hipGetErrorString((hipError_t)e));
+        return film_records_back(f, stream, out, planes * sizeof(wtgpu_film_compare));
+    });
 }
 int wtgpu_film_compare_host(const wtgpu_scene* s, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
                             const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec, const float* mask, uint32_t n_threads,
@@ -295,17 +320,13 @@ int wtgpu_film_compare_host(const wtgpu_scene* s, const double* a_value, const d
     if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
     uint32_t planes = 0;
     if (const int rc = film_compare_check(s, spec, planes)) return rc;
-    try {
+    return film_on_host([&] {
         film_compare_host(s->host.sensor, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec->stokes_component, spec->flags, spec->eps, mask, n_threads,
                           out, diff);
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
+    });
 }
 
 // ---- the polarisation view of a Stokes film (kernels_polar.hip; wt/film_polar.h) ------------------------------------------------------------
-static_assert(sizeof(wtgpu_film_polar) == sizeof(film_polar_rec_t), "the kernels' record is wtgpu_film_polar");
 // what a spec says by itself and against the scene's film; planes: records per call; a: what the kernels are told
 static int film_polar_check(const wtgpu_scene* s, const wtgpu_film_polar_spec* spec, uint32_t& planes, film_polar_args_t& a) {
     const sensor_t& sn = s->host.sensor;
@@ -321,10 +342,7 @@ static int film_polar_check(const wtgpu_scene* s, const wtgpu_film_polar_spec* s
         return fail(WTGPU_ERR_INVALID, "film_polar: picture_plane " + std::to_string(spec->picture_plane) + " out of range (the call has " + std::to_string(planes) + ")");
     if (spec->format > TM_U16) return fail(WTGPU_ERR_INVALID, "film_polar: format 0 (f32), 1 (u8) or 2 (u16) expected");
     const wtgpu_tonemap& tm = spec->tonemap;
-    if (tm.op == TM_FUNCTION) return fail(WTGPU_ERR_INVALID, "film_polar: the 'function' operator is not supported (the expression is read from the scene file, not evaluated)");
-    if (tm.op < TM_LINEAR || tm.op > TM_FUNCTION) return fail(WTGPU_ERR_INVALID, "film_polar: operator 0 (linear), 1 (gamma), 2 (sRGB) or 3 (dB) expected");
-    if (tm.op == TM_GAMMA && !(tm.gamma > 0.f)) return fail(WTGPU_ERR_INVALID, "film_polar: 'gamma' must be positive");
-    if (tm.op == TM_DB && !(tm.db_max - tm.db_min > 0.f)) return fail(WTGPU_ERR_INVALID, "film_polar: expected valid 'db' range to be provided");
+    if (const int rc = tonemap_op_check(tm.op, TM_NORMAL, tm.gamma, tm.db_min, tm.db_max, "film_polar: ", "film_polar: ")) return rc;   // (the picture has no mode)
     a = film_polar_args_t{};
     a.c2 = spec->c2, a.s2 = spec->s2;
     a.maps = spec->maps;
@@ -338,8 +356,6 @@ static int film_polar_check(const wtgpu_scene* s, const wtgpu_film_polar_spec* s
     a.tm.db_len = tm.db_max - tm.db_min;
     return WTGPU_OK;
 }
-constexpr size_t kFpRecBytes = kFsMaxPlanes * sizeof(film_polar_rec_t);
-static_assert(kFpRecBytes % 32 == 0, "the wavefronts' records (32 bytes each) follow the records in one block");
 
 int wtgpu_film_polar_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
                             const wtgpu_film_polar_spec* spec, const float* d_mask, wtgpu_film_polar* out, float* d_maps, void* d_picture) {
@@ -348,24 +364,14 @@ int wtgpu_film_polar_device(wtgpu_scene* s, void* stream_, const double* d_value
     film_polar_args_t a{};
     if (const int rc = film_polar_check(s, spec, planes, a)) return rc;
     if (d_maps && a.n_maps == 0) return fail(WTGPU_ERR_INVALID, "film_polar: d_maps without a map bit");
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    const sensor_t& sn = s->host.sensor;
-    const uint64_t npix = (uint64_t)sn.width * sn.height;
-    if (npix == 0) return fail(WTGPU_ERR_INVALID, "film_polar: the film has no pixels");
-    device_guard_t guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // first use: the records with the wavefronts' records behind them, the pinned copy of the former, the chunk sums (all levels, kFsMaxPlanes
-    // planes of kFpSums sums)
-    film_scratch_t& f = s->fp;
-    if (const int rc = film_scratch_alloc(s, f, kFpRecBytes + film_polar_wave_bytes(npix, s->n_cus), kFpRecBytes, (size_t)kFsMaxPlanes * kFpSums * fs_scratch_len(npix)))
-        return rc;
-    // The call waits for its own result below, so the block is free again when it returns.
-    const int e = film_polar_launch(sn, stream, s->n_cus, d_value, d_weight, d_light, spe, spec->flags, a, s->knobs.film_polar_staged, d_mask, f.d_block, f.d_sums, f.d_block + kFpRecBytes, d_maps, d_picture);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_polar: ") + hipGetErrorString((hipError_t)e));
-    HIP_CHECK(hipMemcpyAsync(f.h_block, f.d_block, planes * sizeof(film_polar_rec_t), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    std::memcpy(out, f.h_block, planes * sizeof(wtgpu_film_polar));
-    return WTGPU_OK;
+    return film_on_device(s, stream_, "film_polar", [&](hipStream_t stream, uint64_t npix) -> int {
+        film_scratch_t& f = s->fp;
+        if (const int rc = film_rec_scratch<kFpSums>(s, f, npix)) return rc;
+        const int e = film_polar_launch(s->host.sensor, stream, s->n_cus, d_value, d_weight, d_light, spe, spec->flags, a, s->knobs.film_polar_staged, d_mask, f.d_block,
+                                        f.d_sums, f.d_block + kFilmRecBytes<kFpSums>, d_maps, d_picture);
+        if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_polar: ") + hipGetErrorString((hipError_t)e));
+        return film_records_back(f, stream, out, planes * sizeof(wtgpu_film_polar));
+    });
 }
 int wtgpu_film_polar_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_film_polar_spec* spec,
                           const float* mask, uint32_t n_threads, wtgpu_film_polar* out, float* maps, void* picture) {
@@ -374,12 +380,7 @@ int wtgpu_film_polar_host(const wtgpu_scene* s, const double* value, const doubl
     film_polar_args_t a{};
     if (const int rc = film_polar_check(s, spec, planes, a)) return rc;
     if (maps && a.n_maps == 0) return fail(WTGPU_ERR_INVALID, "film_polar: maps without a map bit");
-    try {
-        film_polar_host(s->host.sensor, value, weight, light, spe, spec->flags, a, mask, n_threads, out, maps, picture);
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
+    return film_on_host([&] { film_polar_host(s->host.sensor, value, weight, light, spe, spec->flags, a, mask, n_threads, out, maps, picture); });
 }
 
 // ---- denoising a film from its two half-films (kernels_denoise.hip; wt/film_denoise.h) -------------------------------------------------------
@@ -405,41 +406,6 @@ static int film_denoise_check(const wtgpu_scene* s, const wtgpu_film_denoise_spe
     return WTGPU_OK;
 }
 
-int wtgpu_film_denoise_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
-                              const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec, const float* d_mask, float* d_out,
-                              float* d_residual) {
-    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
-    film_denoise_args_t a{};
-    if (const int rc = film_denoise_check(s, spec, a)) return rc;
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    const sensor_t& sn = s->host.sensor;
-    if ((uint64_t)sn.width * sn.height == 0) return fail(WTGPU_ERR_INVALID, "film_denoise: the film has no pixels");
-    device_guard_t guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // first use: the developed half-films, their variance, what one direction leaves for the other.  Nothing comes back to the host, so the call
-    // does not wait; calls on different streams would share the scratch memory and must be ordered by the caller.
-    if (!s->d_denoise)
-        if (const int rc = dmalloc(s, &s->d_denoise, film_denoise_scratch_floats(sn))) return rc;
-    // Both directions in one launch up to 4 planes, one launch each for 12, unless the knob says otherwise: film_denoise_launch has the measurement.
-    const uint32_t fused = s->knobs.film_denoise_fused == 2 ? (film_planes(sn) <= 4 ? 1u : 0u) : s->knobs.film_denoise_fused;
-    const int e = film_denoise_launch(sn, stream, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, fused, d_mask, s->d_denoise,
-                                      d_out, d_residual);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_denoise_filter: ") + hipGetErrorString((hipError_t)e));
-    return WTGPU_OK;
-}
-int wtgpu_film_denoise_host(const wtgpu_scene* s, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
-                            const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec, const float* mask, uint32_t n_threads,
-                            float* out, float* residual) {
-    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
-    film_denoise_args_t a{};
-    if (const int rc = film_denoise_check(s, spec, a)) return rc;
-    try {
-        film_denoise_host(s->host.sensor, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, mask, n_threads, out, residual);
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
-}
 // what the guides say by themselves and against the pointers that come with them; gd: what the kernels and the host twin are told
 static int film_denoise_guides_check(const wtgpu_film_denoise_guides* guides, const void* guide, const void* ids, film_denoise_guides_t& gd) {
     static_assert(sizeof(wtgpu_film_denoise_guides) == sizeof(film_denoise_guides_t) && kDnMaxGuides == 8, "the public struct is the header's");
@@ -462,44 +428,70 @@ static int film_denoise_guides_check(const wtgpu_film_denoise_guides* guides, co
     return WTGPU_OK;
 }
 
+// The two device entries: `guides` (with d_guide, d_ids) where the call is the guided one.
+static int film_denoise_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                               const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec, bool guided,
+                               const wtgpu_film_denoise_guides* guides, const float* d_guide, const uint32_t* d_ids, const float* d_mask, float* d_out, float* d_residual) {
+    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || (guided && !guides) || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    film_denoise_args_t a{};
+    if (const int rc = film_denoise_check(s, spec, a)) return rc;
+    film_denoise_guides_t gd{};
+    if (guided)
+        if (const int rc = film_denoise_guides_check(guides, d_guide, d_ids, gd)) return rc;
+    return film_on_device(s, stream_, "film_denoise", [&](hipStream_t stream, uint64_t) -> int {
+        const sensor_t& sn = s->host.sensor;
+        // first use: the developed half-films, their variance, what one direction leaves for the other (the guides are read where the caller has
+        // them).  Nothing comes back to the host, so the call does not wait; calls on different streams would share the scratch memory and must be
+        // ordered by the caller.
+        if (!s->d_denoise)
+            if (const int rc = dmalloc(s, &s->d_denoise, film_denoise_scratch_floats(sn))) return rc;
+        // Both directions in one launch up to 4 planes, one launch each for 12, unless the knob says otherwise: film_denoise_launch has the measurement.
+        const uint32_t fused = s->knobs.film_denoise_fused == 2 ? (film_planes(sn) <= 4 ? 1u : 0u) : s->knobs.film_denoise_fused;
+        const int e = guided ? film_denoise_guided_launch(sn, stream, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, fused, gd,
+                                                          s->knobs.film_denoise_guide_lds, d_guide, d_ids, d_mask, s->d_denoise, d_out, d_residual)
+                             : film_denoise_launch(sn, stream, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, fused, d_mask, s->d_denoise, d_out,
+                                                   d_residual);
+        if (e) return fail(WTGPU_ERR_HIP, std::string(guided ? "k_denoise_filter (guided): " : "k_denoise_filter: ") + hipGetErrorString((hipError_t)e));
+        return WTGPU_OK;
+    });
+}
+static int film_denoise_on_host(const wtgpu_scene* s, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                                const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec, bool guided,
+                                const wtgpu_film_denoise_guides* guides, const float* guide, const uint32_t* ids, const float* mask, uint32_t n_threads, float* out,
+                                float* residual) {
+    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || (guided && !guides) || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    film_denoise_args_t a{};
+    if (const int rc = film_denoise_check(s, spec, a)) return rc;
+    film_denoise_guides_t gd{};
+    if (guided)
+        if (const int rc = film_denoise_guides_check(guides, guide, ids, gd)) return rc;
+    return film_on_host([&] {
+        film_denoise_host(s->host.sensor, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, mask, n_threads, out, residual, guided ? &gd : nullptr,
+                          guided ? guide : nullptr, guided ? ids : nullptr);
+    });
+}
+
+int wtgpu_film_denoise_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                              const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec, const float* d_mask, float* d_out,
+                              float* d_residual) {
+    return film_denoise_device(s, stream_, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec, false, nullptr, nullptr, nullptr, d_mask, d_out, d_residual);
+}
+int wtgpu_film_denoise_host(const wtgpu_scene* s, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                            const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec, const float* mask, uint32_t n_threads,
+                            float* out, float* residual) {
+    return film_denoise_on_host(s, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec, false, nullptr, nullptr, nullptr, mask, n_threads, out, residual);
+}
 int wtgpu_film_denoise_guided_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
                                      const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec,
                                      const wtgpu_film_denoise_guides* guides, const float* d_guide, const uint32_t* d_ids, const float* d_mask, float* d_out,
                                      float* d_residual) {
-    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !guides || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
-    film_denoise_args_t a{};
-    if (const int rc = film_denoise_check(s, spec, a)) return rc;
-    film_denoise_guides_t gd{};
-    if (const int rc = film_denoise_guides_check(guides, d_guide, d_ids, gd)) return rc;
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    const sensor_t& sn = s->host.sensor;
-    if ((uint64_t)sn.width * sn.height == 0) return fail(WTGPU_ERR_INVALID, "film_denoise: the film has no pixels");
-    device_guard_t guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // the unguided call's scratch memory and no more: the guides are read where the caller has them
-    if (!s->d_denoise)
-        if (const int rc = dmalloc(s, &s->d_denoise, film_denoise_scratch_floats(sn))) return rc;
-    const uint32_t fused = s->knobs.film_denoise_fused == 2 ? (film_planes(sn) <= 4 ? 1u : 0u) : s->knobs.film_denoise_fused;
-    const int e = film_denoise_guided_launch(sn, stream, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, fused, gd, s->knobs.film_denoise_guide_lds,
-                                             d_guide, d_ids, d_mask, s->d_denoise, d_out, d_residual);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_denoise_filter (guided): ") + hipGetErrorString((hipError_t)e));
-    return WTGPU_OK;
+    return film_denoise_device(s, stream_, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec, true, guides, d_guide, d_ids, d_mask, d_out, d_residual);
 }
 int wtgpu_film_denoise_guided_host(const wtgpu_scene* s, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
                                    const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_denoise_spec* spec,
                                    const wtgpu_film_denoise_guides* guides, const float* guide, const uint32_t* ids, const float* mask, uint32_t n_threads, float* out,
                                    float* residual) {
-    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !guides || !out) return fail(WTGPU_ERR_INVALID, "null argument");
-    film_denoise_args_t a{};
-    if (const int rc = film_denoise_check(s, spec, a)) return rc;
-    film_denoise_guides_t gd{};
-    if (const int rc = film_denoise_guides_check(guides, guide, ids, gd)) return rc;
-    try {
-        film_denoise_host(s->host.sensor, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, a, mask, n_threads, out, residual, &gd, guide, ids);
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
+    return film_denoise_on_host(s, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec, true, guides, guide, ids, mask, n_threads, out, residual);
 }
 int wtgpu_test_dn_exp2_neg(const float* t, uint64_t n, float* out) {
     if (!t || !out) return fail(WTGPU_ERR_INVALID, "null argument");

@@ -14,10 +14,11 @@
 //   kernels_firsthit.hip k_first_hit / k_first_hit_wave: first-hit maps of a perspective sensor — depth, position, normals, uv, ids (not part of a render)
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
-//   kernels_compare.hip k_film_compare / k_film_compare_finish: difference statistics of two films (not part of a render)
-//   kernels_polar.hip   k_film_polar / k_film_polar_finish: polarisation maps, Stokes sums and false-colour picture of a Stokes film (not part of a render)
+//   kernels_compare.hip k_film_compare (+ k_film_finish): difference statistics of two films (not part of a render)
+//   kernels_polar.hip   k_film_polar (+ k_film_finish): polarisation maps, Stokes sums and false-colour picture of a Stokes film (not part of a render)
 //   kernels_denoise.hip k_denoise_prepare / _variance / k_denoise_filter: the dual-buffer non-local-means filter of two half-films (not part of a render)
-//   kernels_film.h      what the last five share on the device and in their host twins: chunk geometry, level reduction, grid, dispatch, host threads
+//   kernels_film.h      what the last five share on the device and in their host twins: chunk geometry, level reduction, grid, dispatch, host threads; and what
+//                       a "sums + counts + best" pass (compare, polar) is besides its per-pixel arithmetic: wavefront records, k_film_finish, the host twin's scaffold
 // One translation unit per group: they compile in parallel (the single file took four minutes) and a kernel's registers are not at the mercy of
 // its neighbours' inlining decisions.  Kernels are launched across translation units through their host-side handles (external linkage: hence
 // the NAMED namespace).
@@ -636,9 +637,9 @@ void film_stats_host(const sensor_t& sn, const double* value, const double* weig
                      const float* edges, uint32_t bins, uint32_t n_threads, void* out_rec, unsigned long long* out_hist);
 // kernels_compare.hip: comparison of two films (wtgpu_film_compare_device / wtgpu_film_compare_host; wt/film_compare.h).  Two sets of films as wtgpu_render fills
 // them (the same pointers twice are fine); s: the Stokes component; flags: FS_ABS | FS_LUMINANCE; eps: finite, > 0.  d_rec: film_compare_rec_t per plane;
-// d_sums: kFsMaxPlanes x kFcSums x fs_scratch_len(pixels) doubles; d_wave: film_compare_wave_bytes(pixels, n_cus) bytes — none of them has to be
+// d_sums: kFsMaxPlanes x kFcSums x fs_scratch_len(pixels) doubles; d_wave: film_rec_wave_bytes(pixels, n_cus) bytes (the polarisation view's too) — none of them has to be
 // cleared; d_diff: null or [height][width][planes] f32.  Two kernels on `stream`; the launch returns a hipError_t.
-size_t film_compare_wave_bytes(uint64_t npix, uint32_t n_cus);
+size_t film_rec_wave_bytes(uint64_t npix, uint32_t n_cus);
 int film_compare_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
                         const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, uint32_t s, uint32_t flags, double eps, const float* d_mask,
                         void* d_rec, double* d_sums, void* d_wave, float* d_diff);
@@ -647,10 +648,9 @@ void film_compare_host(const sensor_t& sn, const double* a_value, const double* 
                        void* out_rec, float* diff);
 // kernels_polar.hip: the polarisation view of a Stokes film (wtgpu_film_polar_device / wtgpu_film_polar_host; wt/film_polar.h).  Films of a polarimetric
 // sensor as wtgpu_render fills them; flags: FP_LUMINANCE; a: the analyser, the maps' bits and the picture's plane, format and operator.  d_rec:
-// film_polar_rec_t per plane; d_sums: kFsMaxPlanes x kFpSums x fs_scratch_len(pixels) doubles; d_wave: film_polar_wave_bytes(pixels, n_cus) bytes — none of
+// film_polar_rec_t per plane; d_sums: kFsMaxPlanes x kFpSums x fs_scratch_len(pixels) doubles; d_wave: film_rec_wave_bytes(pixels, n_cus) bytes — none of
 // them has to be cleared; d_maps: null or [height][width][planes][a.n_maps] f32; d_picture: null or [height][width][3, or 4 with a mask] in a.format.
 // staged: the measured alternative (WTGPU_FILM_POLAR_STAGED).  Two kernels on `stream`; the launch returns a hipError_t.
-size_t film_polar_wave_bytes(uint64_t npix, uint32_t n_cus);
 int film_polar_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
                       uint32_t flags, const film_polar_args_t& a, uint32_t staged, const float* d_mask, void* d_rec, double* d_sums, void* d_wave, float* d_maps,
                       void* d_picture);
