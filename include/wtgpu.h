@@ -251,6 +251,57 @@ int wtgpu_first_hit(wtgpu_scene* scene, void* stream, const wtgpu_first_hit_spec
  * the result does not depend on n_threads.  No device needed. */
 int wtgpu_first_hit_host(const wtgpu_scene* scene, const wtgpu_first_hit_spec* spec, uint32_t n_threads, float* maps, uint32_t* ids);
 
+/* Line-of-sight maps: which emitters a sensor element — or a caller's point — can see.  LOS / NLOS is the basic partition of a propagation study,
+ * and from a perspective sensor's first-hit positions the same query is a noise-free shadow plane per lamp.
+ *   points   d_points == NULL: the elements of a VIRTUAL-PLANE sensor.  Sample s of element (px, py) is the point the sensor's own sampling forms
+ *            (virtual_plane_sensor.hpp, the point of sensor_t::sample) at the offset o = r2 - (.5, .5) drawn from the stream
+ *            (seed, (py W + px) samples + s) of the line-of-sight maps: origin + ((px + o.x + .5) element_extent.x) t + ((py + o.y + .5)
+ *            element_extent.y) b; samples == 0: the element's centre, o = (0, 0), no draw.  At most 4096.  The normal is the sensor's.
+ *            d_points [height][width][3] f32 (for example the POSITION map of wtgpu_first_hit): one point per element of the sensor's film
+ *            whatever its type, samples must be 0; d_normals [height][width][3] or NULL: their normals.
+ *   target   of selected emitter e from point p.  Point and spot emitters: v = position - p, dist = |v|, dir = v / dist, the ray's range is
+ *            [t_min, dist].  Directional emitters: dir = the direction to the emitter, range [t_min, inf), dist counts as 0.  Area emitters are
+ *            refused.  t_min >= 0 keeps a surface point from shadowing itself.
+ *   visible  a sample sees the emitter when dist is finite and > 0 (point and spot emitters), every coordinate of p is finite, with flag 1
+ *            FRONT_ONLY dot(dir, n) > 0, and the shadow query (ads_t::shadow) finds nothing in the range.  A sample that fails one of the first
+ *            two adds 0 to every sum.
+ *   maps     [height][width][E][K] f32 per element and selected emitter, K = the floats of the bits of `maps`, in bit order:
+ *              1  VISIBLE    1  float(n_visible) / float(samples) (samples == 0 counts as 1)
+ *              2  DISTANCE   1  dist
+ *              4  DIRECTION  3  dir (the mean is not renormalised)
+ *              8  COS        1  dot(dir, n); needs a normal
+ *            Every map but VISIBLE is the MEAN over ALL samples: an f32 sum in sample order, first term first, divided once by float(samples).
+ *   elem     [height][width][Ke] f32 per element: 1 POINT (3), the mean sample point; 2 NEAREST_DISTANCE (1), the DISTANCE of the NEAREST emitter
+ *            (0 without one).
+ *   ids      [height][width][Ki] u32 per element: 1 N_VISIBLE, the selected emitters with at least one visible sample; 2 NEAREST, the index
+ *            WITHIN THE SELECTION of the one of those with the smallest mean distance (the lowest index wins a tie, a directional emitter counts
+ *            with 0), 0xFFFFFFFF without one.
+ *   emitters n_emitters == 0: every emitter that is not an area emitter, in the scene's selection order (the emitter_list of
+ *            wtgpu_scene_stats_json); else emitters[0 .. n_emitters), indices in that order, at most 32, none twice.
+ *   d_mask   NULL, or [height][width] f32: an element with mask <= 0 traces nothing and holds 0 in every float, 0 / 0xFFFFFFFF in the ids — as an
+ *            element whose point is not finite does.
+ * Errors (WTGPU_ERR_INVALID with a message): no points and a sensor that is not virtual-plane, points with samples != 0, samples > 4096, more than
+ * 32 emitters, an emitter index out of range, repeated or of an area emitter, an empty selection, unknown bits, COS or FRONT_ONLY without a
+ * normal, t_min negative or not finite, a requested group whose pointer is NULL, nothing requested.  A group that is not requested may be NULL. */
+typedef struct wtgpu_los_spec {
+    uint32_t samples;
+    uint32_t maps /* 1 VISIBLE, 2 DISTANCE, 4 DIRECTION, 8 COS */, elem /* 1 POINT, 2 NEAREST_DISTANCE */, ids /* 1 N_VISIBLE, 2 NEAREST */;
+    uint32_t flags /* 1 FRONT_ONLY */, n_emitters;
+    uint32_t emitters[32];
+    float t_min;
+    uint32_t pad;
+    uint64_t seed;
+} wtgpu_los_spec;
+/* On the device, from and into the caller's DEVICE buffers, asynchronously on `stream`: one kernel — one lane per (element, sample) for the
+ * sensor's own elements at 1 .. 64 samples, one lane per (element, emitter) otherwise (WTGPU_LOS_PER_SAMPLE=0: always); the result does not
+ * depend on the form.  Needs an uploaded scene (WTGPU_ERR_INVALID otherwise); counts nothing and touches neither films nor counters. */
+int wtgpu_line_of_sight(wtgpu_scene* scene, void* stream, const wtgpu_los_spec* spec, const float* d_points, const float* d_normals, const float* d_mask,
+                        float* d_maps, float* d_elem, uint32_t* d_ids);
+/* The same on `n_threads` host threads (0: all cores) from the host description, from and into HOST memory: bit for bit what
+ * wtgpu_line_of_sight computes, and the result does not depend on n_threads.  No device needed. */
+int wtgpu_line_of_sight_host(const wtgpu_scene* scene, const wtgpu_los_spec* spec, const float* points, const float* normals, const float* mask,
+                             uint32_t n_threads, float* maps, float* elem, uint32_t* ids);
+
 /* Profiling aid: `repeats` launches of a streaming copy of n_dwords 32-bit words (one dword per lane, coalesced: the access width
  * of the SoA path state) with a known byte count, used to calibrate rocprofv3's FETCH_SIZE / WRITE_SIZE (tools/profile_round.sh). */
 int wtgpu_calibrate_copy(uint64_t n_dwords, int repeats);

@@ -41,6 +41,11 @@ class FirstHitSpec(C.Structure):     # wtgpu_first_hit_spec
     _fields_ = [("samples", C.c_uint32), ("maps", C.c_uint32), ("ids", C.c_uint32), ("pad", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class LosSpec(C.Structure):          # wtgpu_los_spec
+    _fields_ = [("samples", C.c_uint32), ("maps", C.c_uint32), ("elem", C.c_uint32), ("ids", C.c_uint32), ("flags", C.c_uint32), ("n_emitters", C.c_uint32),
+                ("emitters", C.c_uint32 * 32), ("t_min", C.c_float), ("pad", C.c_uint32), ("seed", C.c_uint64)]
+
+
 class TonemapSpec(C.Structure):      # wtgpu_tonemap_spec
     _fields_ = [("present", C.c_int32), ("op", C.c_int32), ("mode", C.c_int32), ("gamma", C.c_float), ("db_min", C.c_float), ("db_max", C.c_float),
                 ("colourmap", C.c_char_p), ("function", C.c_char_p)]
@@ -102,6 +107,12 @@ FILM_DENOISE_MAX_GUIDES = 8
 FIRST_HIT_MAPS = [("coverage", 1), ("depth", 1), ("position", 3), ("normal_geo", 3), ("normal_shading", 3), ("uv", 2), ("facing", 1)]
 FIRST_HIT_IDS = [("shape", 1), ("triangle", 1)]
 FIRST_HIT_MAX_SAMPLES = 4096
+# the same of wtgpu_los_spec.maps (per element and emitter), .elem and .ids (per element)
+LOS_MAPS = [("visible", 1), ("distance", 1), ("direction", 3), ("cos", 1)]
+LOS_ELEM = [("point", 3), ("nearest_distance", 1)]
+LOS_IDS = [("n_visible", 1), ("nearest", 1)]
+LOS_FRONT_ONLY = 1
+LOS_MAX_SAMPLES, LOS_MAX_EMITTERS = 4096, 32
 FILM_POLAR_MAPS = ["dolp", "dop", "docp", "aolp", "chi", "analyser"]      # bit i of wtgpu_film_polar_spec.maps, and the order of the maps in memory
 FILM_STATS_SCALES = ["linear", "dB"]
 FILM_STATS_ABS, FILM_STATS_LUMINANCE = 1, 2
@@ -137,7 +148,7 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_scene_stats_json", "wtgpu_calibrate_copy", "wtgpu_render_async", "wtgpu_join", "wtgpu_query_regions", "wtgpu_render_progressive",
            "wtgpu_cancel", "wtgpu_pause", "wtgpu_resume", "wtgpu_capture_intermediate", "wtgpu_comm_unique_id", "wtgpu_comm_create", "wtgpu_film_reduce", "wtgpu_comm_destroy", "wtgpu_scene_create_from_xml",
            "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host",
-           "wtgpu_first_hit", "wtgpu_first_hit_host",
+           "wtgpu_first_hit", "wtgpu_first_hit_host", "wtgpu_line_of_sight", "wtgpu_line_of_sight_host",
            "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host",
            "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host",
            "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host",
@@ -230,6 +241,8 @@ def load_library():
     lib.wtgpu_sensor_mask_host.argtypes = [vp, vp, u32, u64, u32, vp]
     lib.wtgpu_first_hit.argtypes = [vp, vp, C.POINTER(FirstHitSpec), vp, vp]
     lib.wtgpu_first_hit_host.argtypes = [vp, C.POINTER(FirstHitSpec), u32, vp, vp]
+    lib.wtgpu_line_of_sight.argtypes = [vp, vp, C.POINTER(LosSpec), vp, vp, vp, vp, vp, vp]
+    lib.wtgpu_line_of_sight_host.argtypes = [vp, C.POINTER(LosSpec), vp, vp, vp, u32, vp, vp, vp]
     lib.wtgpu_scene_tonemap_spec.argtypes = [vp, C.POINTER(TonemapSpec)]
     lib.wtgpu_develop_device.argtypes = [vp, vp, vp, vp, vp, u64, vp]
     lib.wtgpu_tonemap_device.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(Tonemap), u32, vp, u32, vp]
@@ -673,6 +686,92 @@ class Scene:
         i = np.zeros((self.height, self.width, Ki), np.uint32) if Ki else None
         _check(load_library().wtgpu_first_hit_host(self._h, C.byref(spec), int(threads), m.ctypes.data if K else None, i.ctypes.data if Ki else None))
         return self._first_hit_views({}, mlay, ilay, m, i)
+
+    def _los_args(self, samples, seed, emitters, maps, elem, ids, front_only, t_min):
+        """-> (wtgpu_los_spec, E, then per group [(name, offset, n)] and its floats / words); names in any order, memory in bit order."""
+        def group(names, table, what):
+            names = [names] if isinstance(names, str) else list(names)
+            known = [n for n, _ in table]
+            for n in names:
+                if n not in known:
+                    raise ValueError(f"line_of_sight: unknown {what} {n!r} (one of {known})")
+            bits, layout, off = 0, [], 0
+            for i, (n, k) in enumerate(table):
+                if n in names:
+                    bits |= 1 << i
+                    layout.append((n, off, k))
+                    off += k
+            return bits, layout, off
+        mbits, mlay, K = group(maps, LOS_MAPS, "map")
+        ebits, elay, Ke = group(elem, LOS_ELEM, "element map")
+        ibits, ilay, Ki = group(ids, LOS_IDS, "id")
+        if emitters is None:
+            sel = []
+            E = sum(1 for e in self.emitter_summary() if e["type"] != "area")
+        else:
+            sel = [int(e) for e in ([emitters] if isinstance(emitters, int) else emitters)]
+            E = len(sel)
+            if E == 0 or E > LOS_MAX_EMITTERS or min(sel) < 0:
+                raise ValueError(f"line_of_sight: 1 .. {LOS_MAX_EMITTERS} emitter indices expected (None: every emitter that is not an area emitter)")
+        spec = LosSpec(int(samples), mbits, ebits, ibits, LOS_FRONT_ONLY if front_only else 0, len(sel), (C.c_uint32 * 32)(*sel), float(t_min), 0, int(seed))
+        return spec, E, (mlay, K), (elay, Ke), (ilay, Ki)
+
+    @staticmethod
+    def _los_views(mlay, elay, ilay, m, e, i):
+        out = {}
+        for n, off, k in mlay:
+            out[n] = m[..., off] if k == 1 else m[..., off:off + k]
+        for n, off, k in elay:
+            out[n] = e[..., off] if k == 1 else e[..., off:off + k]
+        for n, off, k in ilay:
+            out[n] = i[..., off]
+        return out
+
+    def line_of_sight(self, samples=0, seed=1, emitters=None, maps=("visible", "distance"), elem=(), ids=("n_visible", "nearest"), front_only=True,
+                      points=None, normals=None, mask=None, t_min=0.0, stream=None):
+        """Line-of-sight maps on the scene's device (wtgpu_line_of_sight): which of the selected emitters every element sees.  {name: torch
+        tensor}: the pair maps [H, W, E] (visible: the share of the element's samples that see the emitter; distance; cos) or [H, W, E, 3]
+        (direction), means over all samples; the element maps point [H, W, 3] and nearest_distance [H, W]; the ids n_visible and nearest [H, W],
+        int32 holding the u32 bits (nearest: the index within the selection, -1 = 0xFFFFFFFF where no emitter is seen) — views of one
+        allocation per group.  emitters: None = every emitter that is not an area emitter, in the order of emitter_summary(), or indices in
+        that order.  points: None = the elements of the virtual-plane sensor (samples 0: their centres; n >= 1: n points per element drawn
+        from `seed`), or a contiguous f32 tensor [H, W, 3] on the device (Scene.first_hit's position), with normals the same or None;
+        front_only and cos need a normal.  mask: None or f32 [H, W] there, elements with mask <= 0 trace nothing and hold 0 / -1.  t_min: the
+        start of the rays' range (a surface point must not shadow itself).  Enqueued on `stream` (default: torch's current)."""
+        import torch
+        if self.device is None:
+            raise WtgpuError("line_of_sight: upload(device) first")
+        dev = torch.device("cuda", self.device)
+        n = self.width * self.height
+        for t, name, numel in ((points, "points", 3 * n), (normals, "normals", 3 * n), (mask, "mask", n)):
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.numel() == numel and t.is_contiguous()):
+                raise ValueError(f"line_of_sight: {name}: a contiguous torch.float32 tensor of {numel} elements on cuda:{self.device} expected")
+        spec, E, (mlay, K), (elay, Ke), (ilay, Ki) = self._los_args(samples, seed, emitters, maps, elem, ids, front_only, t_min)
+        m = torch.empty((self.height, self.width, E, K), dtype=torch.float32, device=dev) if K else None
+        e = torch.empty((self.height, self.width, Ke), dtype=torch.float32, device=dev) if Ke else None
+        i = torch.empty((self.height, self.width, Ki), dtype=torch.int32, device=dev) if Ki else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _check(load_library().wtgpu_line_of_sight(self._h, self._stream_arg(stream, dev), C.byref(spec), ptr(points), ptr(normals), ptr(mask), ptr(m), ptr(e),
+                                                  ptr(i)))
+        return self._los_views(mlay, elay, ilay, m, e, i)
+
+    def line_of_sight_host(self, samples=0, seed=1, emitters=None, maps=("visible", "distance"), elem=(), ids=("n_visible", "nearest"), front_only=True,
+                           points=None, normals=None, mask=None, t_min=0.0, threads=0):
+        """The same maps on host threads (wtgpu_line_of_sight_host; threads 0 = all cores) from numpy points / normals / mask, as numpy (ids:
+        uint32): bit for bit the device's."""
+        import numpy as np
+        n = self.width * self.height
+        points, normals, mask = (None if t is None else np.ascontiguousarray(t, dtype=np.float32) for t in (points, normals, mask))
+        for t, name, numel in ((points, "points", 3 * n), (normals, "normals", 3 * n), (mask, "mask", n)):
+            if t is not None and t.size != numel:
+                raise ValueError(f"line_of_sight_host: {name}: {numel} floats expected")
+        spec, E, (mlay, K), (elay, Ke), (ilay, Ki) = self._los_args(samples, seed, emitters, maps, elem, ids, front_only, t_min)
+        m = np.zeros((self.height, self.width, E, K), np.float32) if K else None
+        e = np.zeros((self.height, self.width, Ke), np.float32) if Ke else None
+        i = np.zeros((self.height, self.width, Ki), np.uint32) if Ki else None
+        ptr = lambda t: None if t is None else t.ctypes.data
+        _check(load_library().wtgpu_line_of_sight_host(self._h, C.byref(spec), ptr(points), ptr(normals), ptr(mask), int(threads), ptr(m), ptr(e), ptr(i)))
+        return self._los_views(mlay, elay, ilay, m, e, i)
 
     @property
     def tonemap_spec(self):

@@ -2008,7 +2008,9 @@ std::string scene_builder_t::stats() const {
           << ", \"position\": [" << e.position.x << ", " << e.position.y << ", " << e.position.z << "], \"direction\": [" << e.frame.n.x << ", " << e.frame.n.y
           << ", " << e.frame.n.z << "]}";
     }
-    o << "]}";
+    const auto fin = [](float x) { return std::isfinite(x) ? x : 0.f; };   // (a scene without triangles has no box: JSON has no inf)
+    o << "], \"world_min\": [" << fin(sc_.world_min.x) << ", " << fin(sc_.world_min.y) << ", " << fin(sc_.world_min.z) << "], \"world_max\": ["
+      << fin(sc_.world_max.x) << ", " << fin(sc_.world_max.y) << ", " << fin(sc_.world_max.z) << "]}";
     return o.str();
 }
 

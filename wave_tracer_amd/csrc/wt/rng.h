@@ -51,6 +51,7 @@ enum rng_stream_e : uint32_t {
     STREAM_EMITTER_WALK = 2,  // emitter subpath
     STREAM_CONNECT = 16,      // + t*32 + s : one stream per (s,t) connection
     STREAM_MASK = 0x80000000u,   // sensor masks (wtgpu_sensor_mask); far above every connection stream (bdpt.h: connect_stream)
+    STREAM_LOS = 0x80000001u,    // line-of-sight maps (wtgpu_line_of_sight, wt/los.h); connect_stream stays below 16 + 1024 + 4096 t + s, t and s at most a path's length
 };
 
 struct sampler_t {

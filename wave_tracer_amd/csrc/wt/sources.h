@@ -456,6 +456,12 @@ WT_HD sensor_sample_t sensor_sample(const scene_t& sc, uint32_t px, uint32_t py,
     }
     return r;
 }
+// The point of the virtual-plane branch of sensor_sample above for a given offset from the element's centre, in elements ((0, 0): the centre):
+// the same expressions in the same order (wt/los.h).
+WT_HD vec3 vplane_element_point(const sensor_t& s, uint32_t px, uint32_t py, vec2 element_offset) {
+    const vec2 local = vec2{float(px) + element_offset.x + .5f, float(py) + element_offset.y + .5f} * s.element_extent;
+    return s.origin + local.x * s.frame.t + local.y * s.frame.b;
+}
 // The mean ray of perspective_t::sample at k = 0 (perspective.hpp:229-262), which is what mask_t::create_mask traces (src/sensor/mask.cpp:49-50):
 // the ray part of the perspective branch of sensor_sample above, with the same draws in the same order and no beam (k = 0 has no sourcing
 // geometry).  A perspective beam's envelope starts at the sensor's position along `dir` (sg_envelope of a source without a surface).

@@ -12,6 +12,7 @@
 //   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
 //   kernels_mask.hip    k_sensor_mask_wave / k_sensor_mask_lane: by-geometry sensor masks (not part of a render)
 //   kernels_firsthit.hip k_first_hit / k_first_hit_wave: first-hit maps of a perspective sensor — depth, position, normals, uv, ids (not part of a render)
+//   kernels_los.hip     k_los_sample / k_los_pair: line-of-sight maps — which emitters a sensor element or a caller's point sees (not part of a render)
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
 //   kernels_compare.hip k_film_compare (+ k_film_finish): difference statistics of two films (not part of a render)
@@ -42,6 +43,7 @@ struct tonemap_args_t;   // wt/tonemap.h (kernels_develop.hip and the entry poin
 struct film_polar_args_t;   // wt/film_polar.h (kernels_polar.hip and its entry points)
 struct film_denoise_args_t;   // wt/film_denoise.h (kernels_denoise.hip and its entry points)
 struct film_denoise_guides_t;
+struct los_query_t;   // wt/los.h (kernels_los.hip and its entry points)
 }
 
 namespace wtk {
@@ -616,6 +618,12 @@ void sensor_mask_host(const scene_t& sc, const uint8_t* shape_matches, uint32_t 
 int first_hit_launch(const scene_t& sc, hipStream_t stream, uint32_t samples, uint64_t seed, uint32_t maps, uint32_t ids, uint32_t per_sample, float* d_maps,
                      uint32_t* d_ids);
 void first_hit_host(const scene_t& sc, uint32_t samples, uint64_t seed, uint32_t maps, uint32_t ids, uint32_t n_threads, float* out_maps, uint32_t* out_ids);
+// kernels_los.hip: line-of-sight maps (wtgpu_line_of_sight / wtgpu_line_of_sight_host; wt/los.h).  q: the spec after its checks, the selection resolved,
+// 1 .. 32 emitters; its points / normals / mask and d_maps [height][width][E][los_map_floats], d_elem [height][width][los_elem_floats], d_ids
+// [height][width][los_id_words] are device memory for the launch and host memory for the twin, each may be null when no bit of its group is set.
+// per_sample: the measured alternative (WTGPU_LOS_PER_SAMPLE).  The launch returns a hipError_t.
+int los_launch(const scene_t& sc, hipStream_t stream, const los_query_t& q, uint32_t per_sample, float* d_maps, float* d_elem, uint32_t* d_ids);
+void los_host(const scene_t& sc, const los_query_t& q, uint32_t n_threads, float* out_maps, float* out_elem, uint32_t* out_ids);
 // kernels_develop.hip: film development and tonemapping (wtgpu_develop_device / wtgpu_tonemap_device / wtgpu_tonemap_host).  Films as wtgpu_render
 // fills them; `t.table` is a DEVICE pointer for the launch and a host pointer for the host twin; s: the Stokes component; d_mask: null, or one
 // f32 per pixel that becomes the fourth component.  per_pixel / lds_table: the measured alternatives (WTGPU_DEVELOP_PER_PIXEL, WTGPU_TONEMAP_LDS_TABLE).

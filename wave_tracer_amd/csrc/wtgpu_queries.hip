@@ -1,8 +1,9 @@
 // wave_tracer_amd — entry points that are neither a render nor read a film (wtgpu_film.hip): ray / cone / region queries, by-geometry sensor
-// masks, first-hit maps, the probes of the kernel tests (wtgpu_test_hooks.h), the PMC calibration copy.
+// masks, first-hit maps, line-of-sight maps, the probes of the kernel tests (wtgpu_test_hooks.h), the PMC calibration copy.
 #include "wtgpu_host.h"
 #include "wt/first_hit.h"
 #include "wt/flux_probe.h"
+#include "wt/los.h"
 #include "wt/sources_probe.h"
 
 extern "C" {
@@ -131,6 +132,74 @@ int wtgpu_first_hit_host(const wtgpu_scene* s, const wtgpu_first_hit_spec* spec,
     if (const int rc = first_hit_check(s, spec, maps, ids)) return rc;
     try {
         first_hit_host(s->host, spec->samples, spec->seed, spec->maps, spec->ids, n_threads, maps, ids);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+
+// ---- line-of-sight maps (wt/los.h, kernels_los.hip) ------------------------------------------------------------------------------------------
+// the checks both forms share, and the query the kernels and the host twin take
+static int los_check(const wtgpu_scene* s, const wtgpu_los_spec* spec, const float* points, const float* normals, const float* mask, const float* maps,
+                     const float* elem, const uint32_t* ids, los_query_t& q) {
+    if (!s || !spec) return fail(WTGPU_ERR_INVALID, "null argument");
+    const scene_t& sc = s->host;
+    if (!points && sc.sensor.type != SENSOR_VIRTUAL_PLANE)
+        return fail(WTGPU_ERR_INVALID, "line of sight: without points the elements of a virtual-plane sensor are meant, and this sensor is not one (pass points, for example the POSITION map of wtgpu_first_hit)");
+    if (points && spec->samples != 0) return fail(WTGPU_ERR_INVALID, "line of sight: caller points take samples = 0 (a point is not sampled)");
+    if (spec->samples > kLosMaxSamples) return fail(WTGPU_ERR_INVALID, "line of sight: 0 .. 4096 samples per element expected");
+    if (spec->maps & ~(uint32_t)LOS_ALL_MAPS) return fail(WTGPU_ERR_INVALID, "line of sight: unknown map bits (1 VISIBLE, 2 DISTANCE, 4 DIRECTION, 8 COS)");
+    if (spec->elem & ~(uint32_t)LOS_ALL_ELEM) return fail(WTGPU_ERR_INVALID, "line of sight: unknown element bits (1 POINT, 2 NEAREST_DISTANCE)");
+    if (spec->ids & ~(uint32_t)LOS_ALL_IDS) return fail(WTGPU_ERR_INVALID, "line of sight: unknown id bits (1 N_VISIBLE, 2 NEAREST)");
+    if (spec->flags & ~(uint32_t)LOS_ALL_FLAGS) return fail(WTGPU_ERR_INVALID, "line of sight: unknown flag bits (1 FRONT_ONLY)");
+    if (!spec->maps && !spec->elem && !spec->ids) return fail(WTGPU_ERR_INVALID, "line of sight: nothing requested (no map, no element and no id bit)");
+    if (spec->maps && !maps) return fail(WTGPU_ERR_INVALID, "line of sight: maps requested, but the maps pointer is NULL");
+    if (spec->elem && !elem) return fail(WTGPU_ERR_INVALID, "line of sight: element floats requested, but the elem pointer is NULL");
+    if (spec->ids && !ids) return fail(WTGPU_ERR_INVALID, "line of sight: ids requested, but the ids pointer is NULL");
+    const bool has_normal = !points || normals;
+    if ((spec->maps & LOS_COS) && !has_normal) return fail(WTGPU_ERR_INVALID, "line of sight: COS needs a normal (caller points without normals)");
+    if ((spec->flags & LOS_FRONT_ONLY) && !has_normal) return fail(WTGPU_ERR_INVALID, "line of sight: FRONT_ONLY needs a normal (caller points without normals)");
+    if (!(spec->t_min >= 0.f) || !finitef(spec->t_min)) return fail(WTGPU_ERR_INVALID, "line of sight: t_min must be finite and >= 0");
+    if (spec->n_emitters > kLosMaxEmitters) return fail(WTGPU_ERR_INVALID, "line of sight: at most 32 emitters per call");
+    q.samples = spec->samples, q.maps = spec->maps, q.elem = spec->elem, q.ids = spec->ids, q.flags = spec->flags;
+    q.t_min = spec->t_min, q.seed = spec->seed;
+    q.points = points, q.normals = points ? normals : nullptr, q.mask = mask;
+    q.n_emitters = 0;
+    for (uint32_t i = 0; i < kLosMaxEmitters; ++i) q.emitters[i] = 0;
+    if (spec->n_emitters == 0) {
+        for (uint32_t i = 0; i < sc.n_emitters; ++i) {
+            if (sc.emitters[i].type == EMIT_AREA) continue;
+            if (q.n_emitters == kLosMaxEmitters) return fail(WTGPU_ERR_INVALID, "line of sight: the scene has more than 32 emitters that are not area emitters: select at most 32 per call");
+            q.emitters[q.n_emitters++] = i;
+        }
+        if (!q.n_emitters) return fail(WTGPU_ERR_INVALID, "line of sight: empty selection (the scene has no point, spot or directional emitter)");
+    } else
+        for (uint32_t k = 0; k < spec->n_emitters; ++k) {
+            const uint32_t i = spec->emitters[k];
+            if (i >= sc.n_emitters) return fail(WTGPU_ERR_INVALID, "line of sight: emitter index " + std::to_string(i) + " out of range (the scene has " + std::to_string(sc.n_emitters) + ")");
+            if (sc.emitters[i].type == EMIT_AREA) return fail(WTGPU_ERR_INVALID, "line of sight: emitter " + std::to_string(i) + " is an area emitter (point, spot and directional emitters only)");
+            for (uint32_t j = 0; j < k; ++j)
+                if (spec->emitters[j] == i) return fail(WTGPU_ERR_INVALID, "line of sight: emitter " + std::to_string(i) + " is selected twice");
+            q.emitters[q.n_emitters++] = i;
+        }
+    return WTGPU_OK;
+}
+int wtgpu_line_of_sight(wtgpu_scene* s, void* stream, const wtgpu_los_spec* spec, const float* d_points, const float* d_normals, const float* d_mask,
+                        float* d_maps, float* d_elem, uint32_t* d_ids) {
+    los_query_t q;
+    if (const int rc = los_check(s, spec, d_points, d_normals, d_mask, d_maps, d_elem, d_ids, q)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    device_guard_t guard(s->device);
+    const int e = los_launch(s->dev, static_cast<hipStream_t>(stream), q, s->knobs.los_per_sample, d_maps, d_elem, d_ids);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_los: ") + hipGetErrorString((hipError_t)e));
+    return WTGPU_OK;
+}
+int wtgpu_line_of_sight_host(const wtgpu_scene* s, const wtgpu_los_spec* spec, const float* points, const float* normals, const float* mask,
+                             uint32_t n_threads, float* maps, float* elem, uint32_t* ids) {
+    los_query_t q;
+    if (const int rc = los_check(s, spec, points, normals, mask, maps, elem, ids, q)) return rc;
+    try {
+        los_host(s->host, q, n_threads, maps, elem, ids);
     } catch (const std::exception& e) {
         return fail(WTGPU_ERR_INVALID, e.what());
     }

@@ -107,6 +107,49 @@ def first_hit_guides(scene, samples=0, seed=1, scales=None, same_shape=True, hos
     return guide, scales, (fh["shape"].contiguous() if same_shape else None)
 
 
+def los_masks(scene, emitter=None, samples=0, seed=1, host=False):
+    """The LOS / NLOS partition of a coverage map (Scene.line_of_sight on the scene's device; host=True: Scene.line_of_sight_host, numpy, no
+    device needed): (los, nlos), two f32 arrays [H, W] of 1 and 0 that add up to 1 everywhere, ready for film_stats_device(mask=...) and the
+    other film passes.  emitter: an index in the order of emitter_summary() — los is 1 where at least one of the element's samples sees that
+    emitter (its VISIBLE > 0) —, or None: where it sees any emitter that is not an area emitter (N_VISIBLE > 0).  samples 0: the elements' centres."""
+    query = scene.line_of_sight_host if host else scene.line_of_sight
+    if emitter is None:
+        seen = query(samples, seed, maps=(), ids=("n_visible",))["n_visible"] > 0
+    else:
+        seen = query(samples, seed, emitters=[int(emitter)], maps=("visible",), ids=())["visible"][..., 0] > 0
+    if host:
+        los = np.ascontiguousarray(seen, dtype=np.float32)
+        return los, np.float32(1) - los
+    los = seen.float().contiguous()
+    return los, (1.0 - los).contiguous()
+
+
+SHADOW_GUIDE_SCALE = 1.0 / FIRST_HIT_GUIDE_KF ** 2   # shadow_guides' default scale for every plane: first_hit_guides' 2.78.  UNTUNED.
+SHADOW_GUIDE_T_MIN = 1e-4                            # shadow_guides' default t_min, in diagonals of the scene's bounding box
+
+
+def shadow_guides(scene, samples=0, seed=1, scales=None, t_min=None, emitters=None, host=False):
+    """Noise-free shadow planes of a perspective sensor as guides of a feature-guided denoise(): from every pixel's first-hit position
+    (Scene.first_hit's position and normal_geo over `samples` primary rays, its coverage as the mask), is each lamp visible
+    (Scene.line_of_sight(points=..., normals=..., t_min=...), front_only off: a first-hit normal is not turned towards the camera)?  Returns (guide,
+    scales, None) as denoise(guides=...) takes it: guide [H, W, E] f32 on the scene's device (host=True: numpy from the host twins, no device
+    needed), 1 where pixel and lamp see each other, 0 in the lamp's shadow and where the pixel sees nothing; E: the emitters that are not area
+    emitters (or `emitters`), at most 8 for the denoiser.  t_min defaults to 1e-4 x the diagonal of the scene's bounding box.  The scales
+    default to 2.78 for every plane as first_hit_guides' do and are UNTUNED: nobody has measured a denoise with these guides.  A sensor that is
+    not perspective is refused by first_hit itself."""
+    fh = (scene.first_hit_host if host else scene.first_hit)(samples, seed, maps=("coverage", "position", "normal_geo"), ids=())
+    if t_min is None:
+        st = scene.stats()
+        t_min = SHADOW_GUIDE_T_MIN * float(np.linalg.norm(np.asarray(st["world_max"], dtype=np.float64) - np.asarray(st["world_min"], dtype=np.float64)))
+    points, normals, mask = ((np.ascontiguousarray(fh[k]) if host else fh[k].contiguous()) for k in ("position", "normal_geo", "coverage"))
+    guide = (scene.line_of_sight_host if host else scene.line_of_sight)(0, seed, emitters=emitters, maps=("visible",), ids=(), front_only=False, points=points,
+                                                                        normals=normals, mask=mask, t_min=t_min)["visible"]
+    guide = np.ascontiguousarray(guide) if host else guide.contiguous()
+    if scales is None:
+        scales = SHADOW_GUIDE_SCALE
+    return guide, [float(s) for s in np.broadcast_to(np.asarray(scales, dtype=np.float64), (guide.shape[-1],))], None
+
+
 def denoise(scene, films_a, films_b, spe, guides=None, **kw):
     """Denoises the film that the half-films A and B add up to (render_to_noise(..., halves=True); `spe` samples per element each): films_a / films_b
     are (value, weight, light), torch tensors on the scene's device (Scene.film_denoise_device: everything stays there) or numpy arrays
