@@ -251,6 +251,53 @@ int wtgpu_first_hit(wtgpu_scene* scene, void* stream, const wtgpu_first_hit_spec
  * the result does not depend on n_threads.  No device needed. */
 int wtgpu_first_hit_host(const wtgpu_scene* scene, const wtgpu_first_hit_spec* spec, uint32_t n_threads, float* maps, uint32_t* ids);
 
+/* First-hit material maps of a perspective sensor: what the MATERIAL under a pixel is at chosen wavenumbers — the albedo guide of a feature-aware
+ * filter (a checkerboard, a bitmap or a mask pattern on a flat wall is constant in every geometric map) and, for a radio scene, the specular
+ * reflectance of the wall under a pixel at the carrier.
+ *   rays     exactly those of the first-hit maps above for the same `samples` and `seed` (samples == 0: the ray through the pixel's centre),
+ *            with the same hit, wp and surface record.  At most 4096.
+ *   sample   of a ray that hits shape S, with direction d: mat = S's material, uv = the surface's, wi = -d in the shading frame.  Per requested
+ *            wavenumber k[j], j < n_k <= 4, in 1/mm: the wrappers of mat are followed down to a leaf BSDF m at k[j] (composite bins, masks,
+ *            scale and two_sided wrappers, textured roughness); ok = there is one.  wi' = wi mirrored to z >= 0 if m is two-sided, else wi;
+ *            a = the accumulated mask opacity, 1 without a mask.
+ *   maps     [height][width][K] f32, K = n_k x the number of set bits of `maps`; the maps in bit order, the n_k values of a map adjacent:
+ *              1  ALBEDO     m diffuse and wi'.z > 0: clamp01(reflectance spectrum(k) x texture(uv, k)) x m's scale x a, else 0
+ *              2  SPECULAR   m dielectric or surface_spm and wi'.z != 0: the unpolarised power reflectance of the SMOOTH interface for wi' x
+ *                            m's reflection scale x m's scale x a, else 0.  With eta = the relative IOR at k[j]: where the material transmits
+ *                            (Im(eta)^2 / |eta|^2 <= 0.01) 1 - (Ts + Tp) / 2 of the Fresnel equations at Re(eta), the reflection share the
+ *                            BSDF's own sampling uses; otherwise (a conductor, a lossy wall) (|rs|^2 + |rp|^2) / 2 at the complex eta,
+ *                            which is 0 from behind.
+ *              4  OPACITY    a
+ *              8  ROUGHNESS  m surface_spm: its perceptual roughness (after a roughness texture), else 0
+ *             16  EMISSION   S carries an area emitter and dot(-d, geometric normal) > 0: its spectral radiance at uv and k[j], else 0
+ *            Every float but EMISSION is 0 when !ok.  Every value is the MEAN over the hitting samples: an f32 sum in sample order, first term
+ *            first, divided once by float(n_hit).  A pixel that no sample hits holds 0.  A value is a point sample at k[j], not an integral
+ *            over a channel's response.
+ *   ids      [height][width][Ki] u32, of the first sample in order that hits: 1 MATERIAL, the index of S's material; 2 TYPE, the leaf type at
+ *            k[0] (0 diffuse, 1 dielectric, 2 surface_spm), 0xFFFFFFFF without a BSDF at k[0].  0xFFFFFFFF for a pixel without a hit.
+ * Function textures whose programs use libm (pow, sin, ...) are evaluated, but only the others are bit-identical between device and host.
+ * A wavenumber outside the support of a material's tabulated IOR meets the table's 0 there: SPECULAR is then not finite (the renderer never
+ * draws such a wavenumber; a caller can).
+ * Errors (WTGPU_ERR_INVALID with a message): a sensor that is not perspective, unknown map or id bits, n_k outside 1 .. 4, a k[j] that is not
+ * finite and > 0, samples > 4096, a requested group whose pointer is NULL, nothing requested.  A group that is not requested may be NULL. */
+typedef struct wtgpu_first_hit_material_spec {
+    uint32_t samples;
+    uint32_t maps /* 1 ALBEDO, 2 SPECULAR, 4 OPACITY, 8 ROUGHNESS, 16 EMISSION */, ids /* 1 MATERIAL, 2 TYPE */, n_k /* 1 .. 4 */;
+    float k[4];
+    uint64_t seed;
+} wtgpu_first_hit_material_spec;
+/* On the device, into the caller's DEVICE buffers, asynchronously on `stream`: one kernel, in the two lane shapes of the first-hit maps
+ * (WTGPU_FIRST_HIT_PER_SAMPLE chooses, the result does not depend on it).  Needs an uploaded scene (WTGPU_ERR_INVALID otherwise); counts nothing
+ * and touches neither films nor counters. */
+int wtgpu_first_hit_material(wtgpu_scene* scene, void* stream, const wtgpu_first_hit_material_spec* spec, float* d_maps, uint32_t* d_ids);
+/* The same on `n_threads` host threads (0: all cores) from the host description, into HOST memory: bit for bit what the device call computes,
+ * and the result does not depend on n_threads.  No device needed. */
+int wtgpu_first_hit_material_host(const wtgpu_scene* scene, const wtgpu_first_hit_material_spec* spec, uint32_t n_threads, float* maps, uint32_t* ids);
+/* One wavenumber [1/mm] per spectral channel of the sensor, k[c] for c < channels and 0 beyond — a natural choice of k above: the line of a
+ * discrete response; for a tabulated response the response-weighted mean sum(k_i R_i) / sum(R_i) over the table's own knots, in f64, rounded
+ * to f32.  A constant or all-zero response singles out no wavenumber: WTGPU_ERR_INVALID with a message. */
+int wtgpu_scene_channel_wavenumbers(const wtgpu_scene* scene, float k[4]);
+
 /* Line-of-sight maps: which emitters a sensor element — or a caller's point — can see.  LOS / NLOS is the basic partition of a propagation study,
  * and from a perspective sensor's first-hit positions the same query is a noise-free shadow plane per lamp.
  *   points   d_points == NULL: the elements of a VIRTUAL-PLANE sensor.  Sample s of element (px, py) is the point the sensor's own sampling forms

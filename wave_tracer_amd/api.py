@@ -41,6 +41,10 @@ class FirstHitSpec(C.Structure):     # wtgpu_first_hit_spec
     _fields_ = [("samples", C.c_uint32), ("maps", C.c_uint32), ("ids", C.c_uint32), ("pad", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class FirstHitMaterialSpec(C.Structure):   # wtgpu_first_hit_material_spec
+    _fields_ = [("samples", C.c_uint32), ("maps", C.c_uint32), ("ids", C.c_uint32), ("n_k", C.c_uint32), ("k", C.c_float * 4), ("seed", C.c_uint64)]
+
+
 class LosSpec(C.Structure):          # wtgpu_los_spec
     _fields_ = [("samples", C.c_uint32), ("maps", C.c_uint32), ("elem", C.c_uint32), ("ids", C.c_uint32), ("flags", C.c_uint32), ("n_emitters", C.c_uint32),
                 ("emitters", C.c_uint32 * 32), ("t_min", C.c_float), ("pad", C.c_uint32), ("seed", C.c_uint64)]
@@ -107,6 +111,10 @@ FILM_DENOISE_MAX_GUIDES = 8
 FIRST_HIT_MAPS = [("coverage", 1), ("depth", 1), ("position", 3), ("normal_geo", 3), ("normal_shading", 3), ("uv", 2), ("facing", 1)]
 FIRST_HIT_IDS = [("shape", 1), ("triangle", 1)]
 FIRST_HIT_MAX_SAMPLES = 4096
+# bit i of wtgpu_first_hit_material_spec.maps (n_k floats each, in this order in memory) / .ids
+FIRST_HIT_MATERIAL_MAPS = ["albedo", "specular", "opacity", "roughness", "emission"]
+FIRST_HIT_MATERIAL_IDS = ["material", "type"]
+FIRST_HIT_MATERIAL_MAX_K = 4
 # the same of wtgpu_los_spec.maps (per element and emitter), .elem and .ids (per element)
 LOS_MAPS = [("visible", 1), ("distance", 1), ("direction", 3), ("cos", 1)]
 LOS_ELEM = [("point", 3), ("nearest_distance", 1)]
@@ -149,6 +157,7 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_cancel", "wtgpu_pause", "wtgpu_resume", "wtgpu_capture_intermediate", "wtgpu_comm_unique_id", "wtgpu_comm_create", "wtgpu_film_reduce", "wtgpu_comm_destroy", "wtgpu_scene_create_from_xml",
            "wtgpu_scene_shape_id", "wtgpu_scene_sensor_mask_spec", "wtgpu_sensor_mask", "wtgpu_sensor_mask_host",
            "wtgpu_first_hit", "wtgpu_first_hit_host", "wtgpu_line_of_sight", "wtgpu_line_of_sight_host",
+           "wtgpu_first_hit_material", "wtgpu_first_hit_material_host", "wtgpu_scene_channel_wavenumbers",
            "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host",
            "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host",
            "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host",
@@ -241,6 +250,9 @@ def load_library():
     lib.wtgpu_sensor_mask_host.argtypes = [vp, vp, u32, u64, u32, vp]
     lib.wtgpu_first_hit.argtypes = [vp, vp, C.POINTER(FirstHitSpec), vp, vp]
     lib.wtgpu_first_hit_host.argtypes = [vp, C.POINTER(FirstHitSpec), u32, vp, vp]
+    lib.wtgpu_first_hit_material.argtypes = [vp, vp, C.POINTER(FirstHitMaterialSpec), vp, vp]
+    lib.wtgpu_first_hit_material_host.argtypes = [vp, C.POINTER(FirstHitMaterialSpec), u32, vp, vp]
+    lib.wtgpu_scene_channel_wavenumbers.argtypes = [vp, vp]
     lib.wtgpu_line_of_sight.argtypes = [vp, vp, C.POINTER(LosSpec), vp, vp, vp, vp, vp, vp]
     lib.wtgpu_line_of_sight_host.argtypes = [vp, C.POINTER(LosSpec), vp, vp, vp, u32, vp, vp, vp]
     lib.wtgpu_scene_tonemap_spec.argtypes = [vp, C.POINTER(TonemapSpec)]
@@ -686,6 +698,66 @@ class Scene:
         i = np.zeros((self.height, self.width, Ki), np.uint32) if Ki else None
         _check(load_library().wtgpu_first_hit_host(self._h, C.byref(spec), int(threads), m.ctypes.data if K else None, i.ctypes.data if Ki else None))
         return self._first_hit_views({}, mlay, ilay, m, i)
+
+    def channel_wavenumbers(self):
+        """One wavenumber [1/mm] per spectral channel (wtgpu_scene_channel_wavenumbers), numpy f32 [spectral_channels]: the line of a discrete
+        response, the response-weighted mean over the knots of a tabulated one.  A constant or all-zero response is refused."""
+        import numpy as np
+        k = np.zeros(4, np.float32)
+        _check(load_library().wtgpu_scene_channel_wavenumbers(self._h, k.ctypes.data))
+        return k[:self.spectral_channels].copy()
+
+    def _first_hit_material_args(self, samples, seed, k, maps, ids):
+        """-> (wtgpu_first_hit_material_spec, the map names in memory order, n_k, the id names in memory order); names in any order."""
+        import numpy as np
+        def group(names, known, what):
+            names = [names] if isinstance(names, str) else list(names)
+            for n in names:
+                if n not in known:
+                    raise ValueError(f"first_hit_material: unknown {what} {n!r} (one of {known})")
+            return sum(1 << i for i, n in enumerate(known) if n in names), [n for n in known if n in names]
+        mbits, mnames = group(maps, FIRST_HIT_MATERIAL_MAPS, "map")
+        ibits, inames = group(ids, FIRST_HIT_MATERIAL_IDS, "id")
+        k = self.channel_wavenumbers() if k is None else np.atleast_1d(np.asarray(k, dtype=np.float32))
+        if k.ndim != 1:
+            raise ValueError("first_hit_material: k: a sequence of wavenumbers [1/mm] expected")
+        kk = (C.c_float * 4)(*[float(x) for x in k[:4]])
+        return FirstHitMaterialSpec(int(samples), mbits, ibits, int(k.size), kk, int(seed)), mnames, int(k.size), inames
+
+    def first_hit_material(self, samples=0, seed=1, k=None, maps=("albedo", "specular", "opacity", "roughness", "emission"), ids=("material", "type"),
+                           stream=None):
+        """First-hit material maps of the perspective sensor on the scene's device (wtgpu_first_hit_material): {name: torch tensor}, f32 maps
+        [H, W, n_k] (albedo, specular reflectance of the smooth interface, mask opacity, roughness, emitted radiance — one value per wavenumber
+        of `k`, 1 .. 4 of them in 1/mm; None: channel_wavenumbers()) and int32 ids [H, W] holding the u32 bits (material: its index; type: the
+        leaf type at k[0]; -1 = 0xFFFFFFFF without a hit) — views of one allocation per group.  The rays are first_hit's for the same samples and
+        seed; the maps are means over the rays that hit, the ids the first hitting ray's.  Enqueued on `stream` (default: torch's current)."""
+        import torch
+        if self.device is None:
+            raise WtgpuError("first_hit_material: upload(device) first")
+        dev = torch.device("cuda", self.device)
+        spec, mnames, n_k, inames = self._first_hit_material_args(samples, seed, k, maps, ids)
+        K, Ki = len(mnames) * n_k, len(inames)
+        m = torch.empty((self.height, self.width, K), dtype=torch.float32, device=dev) if K else None
+        i = torch.empty((self.height, self.width, Ki), dtype=torch.int32, device=dev) if Ki else None
+        _check(load_library().wtgpu_first_hit_material(self._h, self._stream_arg(stream, dev), C.byref(spec), m.data_ptr() if K else None,
+                                                       i.data_ptr() if Ki else None))
+        out = {n: m[..., j * n_k:(j + 1) * n_k] for j, n in enumerate(mnames)}
+        out.update({n: i[..., j] for j, n in enumerate(inames)})
+        return out
+
+    def first_hit_material_host(self, samples=0, seed=1, k=None, maps=("albedo", "specular", "opacity", "roughness", "emission"),
+                                ids=("material", "type"), threads=0):
+        """The same maps on host threads (wtgpu_first_hit_material_host; threads 0 = all cores), as numpy (ids: uint32): bit for bit the device's."""
+        import numpy as np
+        spec, mnames, n_k, inames = self._first_hit_material_args(samples, seed, k, maps, ids)
+        K, Ki = len(mnames) * n_k, len(inames)
+        m = np.zeros((self.height, self.width, K), np.float32) if K else None
+        i = np.zeros((self.height, self.width, Ki), np.uint32) if Ki else None
+        _check(load_library().wtgpu_first_hit_material_host(self._h, C.byref(spec), int(threads), m.ctypes.data if K else None,
+                                                            i.ctypes.data if Ki else None))
+        out = {n: m[..., j * n_k:(j + 1) * n_k] for j, n in enumerate(mnames)}
+        out.update({n: i[..., j] for j, n in enumerate(inames)})
+        return out
 
     def _los_args(self, samples, seed, emitters, maps, elem, ids, front_only, t_min):
         """-> (wtgpu_los_spec, E, then per group [(name, offset, n)] and its floats / words); names in any order, memory in bit order."""

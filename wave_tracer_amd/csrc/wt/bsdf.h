@@ -287,6 +287,12 @@ WT_HD bool material_is_delta_only(const scene_t& sc, int mat, float k) {
     return profile_is_delta_only(m);
 }
 
+// The reflectance of a resolved diffuse leaf at wavenumber k: the one expression of material_f's diffuse branch below, for callers that want
+// the albedo itself and no direction pair (wt/first_hit_material.h).
+WT_HD float material_reflectance(const scene_t& sc, const material_t& m, float k, vec2 uv) {
+    return clamp01(spectrum_f(sc, m.refl_spec, k) * m.refl_tex_scale * (m.refl_tex ? texture_spectral(sc, (int)m.refl_tex - 1, uv, k) : 1.f));
+}
+
 // bsdf_t::f — includes the cosine foreshortening; only non-delta lobes
 // `uv`: the surface's texture coordinates (intersection_surface_t::texture_query), used by textured reflectances and masks
 WT_HD mueller_t material_f(const scene_t& sc, int mat, vec3 wi, vec3 wo, float k, uint32_t transport, vec2 uv = vec2{0.f, 0.f}) {

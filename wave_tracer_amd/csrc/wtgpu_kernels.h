@@ -12,6 +12,7 @@
 //   kernels_test.hip    test entry points of the wave-cooperative Fraunhofer / UTD forms and of the material layer (wtgpu_test_hooks.h)
 //   kernels_mask.hip    k_sensor_mask_wave / k_sensor_mask_lane: by-geometry sensor masks (not part of a render)
 //   kernels_firsthit.hip k_first_hit / k_first_hit_wave: first-hit maps of a perspective sensor — depth, position, normals, uv, ids (not part of a render)
+//   kernels_firsthit_material.hip k_first_hit_material / k_first_hit_material_wave: first-hit material maps — albedo, specular reflectance, opacity, roughness, emission, material ids (not part of a render)
 //   kernels_los.hip     k_los_sample / k_los_pair: line-of-sight maps — which emitters a sensor element or a caller's point sees (not part of a render)
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
@@ -44,6 +45,7 @@ struct film_polar_args_t;   // wt/film_polar.h (kernels_polar.hip and its entry 
 struct film_denoise_args_t;   // wt/film_denoise.h (kernels_denoise.hip and its entry points)
 struct film_denoise_guides_t;
 struct los_query_t;   // wt/los.h (kernels_los.hip and its entry points)
+struct fhm_query_t;   // wt/first_hit_material.h (kernels_firsthit_material.hip and its entry points)
 }
 
 namespace wtk {
@@ -618,6 +620,12 @@ void sensor_mask_host(const scene_t& sc, const uint8_t* shape_matches, uint32_t 
 int first_hit_launch(const scene_t& sc, hipStream_t stream, uint32_t samples, uint64_t seed, uint32_t maps, uint32_t ids, uint32_t per_sample, float* d_maps,
                      uint32_t* d_ids);
 void first_hit_host(const scene_t& sc, uint32_t samples, uint64_t seed, uint32_t maps, uint32_t ids, uint32_t n_threads, float* out_maps, uint32_t* out_ids);
+// kernels_firsthit_material.hip: first-hit material maps of a perspective sensor (wtgpu_first_hit_material / wtgpu_first_hit_material_host;
+// wt/first_hit_material.h).  q: the spec after its checks; d_maps: [height][width][fhm_map_floats(q.maps, q.n_k)] f32, d_ids:
+// [height][width][fhm_id_words(q.ids)] u32, each may be null when no bit of its group is set.  per_sample: WTGPU_FIRST_HIT_PER_SAMPLE, as
+// first_hit_launch.  The launch returns a hipError_t.
+int first_hit_material_launch(const scene_t& sc, hipStream_t stream, const fhm_query_t& q, uint32_t per_sample, float* d_maps, uint32_t* d_ids);
+void first_hit_material_host(const scene_t& sc, const fhm_query_t& q, uint32_t n_threads, float* out_maps, uint32_t* out_ids);
 // kernels_los.hip: line-of-sight maps (wtgpu_line_of_sight / wtgpu_line_of_sight_host; wt/los.h).  q: the spec after its checks, the selection resolved,
 // 1 .. 32 emitters; its points / normals / mask and d_maps [height][width][E][los_map_floats], d_elem [height][width][los_elem_floats], d_ids
 // [height][width][los_id_words] are device memory for the launch and host memory for the twin, each may be null when no bit of its group is set.

@@ -73,7 +73,7 @@ const knob_t kKnobs[] = {
     {"WTGPU_FILM_POLAR_STAGED", K(film_polar_staged), KNOB_U32, 1, 0, 1, "k_film_polar: 1 a wavefront loads its chunk's planes contiguously, develops them and hands them to the pixels' lanes through LDS; 0 every lane loads its own pixels' planes (A/B: tools/bench_film_polar.py)"},
     {"WTGPU_FILM_DENOISE_FUSED", K(film_denoise_fused), KNOB_U32, 2, 0, 2, "k_denoise_filter: 1 a block filters both directions (A by B's weights, B by A's) in one launch and keeps the first in registers; 0 one launch per direction, the first leaving its result in scratch memory; 2 whichever was measured faster for the film's planes: 1 up to 4 planes, 0 for 12 (A/B: tools/bench_film_denoise.py)"},
     {"WTGPU_FILM_DENOISE_GUIDE_LDS", K(film_denoise_guide_lds), KNOB_U32, 0, 0, 1, "k_denoise_filter, guided: 1 the guide planes of the candidate square go into LDS beside the halo where the sum fits 64 KB (from global memory where it does not); 0 every lane reads g(q) from global memory where it reads x(q) (A/B: tools/bench_film_denoise_guided.py; the results do not depend on it)"},
-    {"WTGPU_FIRST_HIT_PER_SAMPLE", K(first_hit_per_sample), KNOB_U32, 1, 0, 1, "k_first_hit: 1 one lane per sample where a pixel's samples fit a wavefront (k_first_hit_wave: the lanes of a pixel exchange their samples through LDS, lane j sums float j in sample order); 0 one lane per pixel always (A/B: tools/bench_first_hit.py; the results do not depend on it)"},
+    {"WTGPU_FIRST_HIT_PER_SAMPLE", K(first_hit_per_sample), KNOB_U32, 1, 0, 1, "k_first_hit: 1 one lane per sample where a pixel's samples fit a wavefront (k_first_hit_wave: the lanes of a pixel exchange their samples through LDS, lane j sums float j in sample order); 0 one lane per pixel always (A/B: tools/bench_first_hit.py; the results do not depend on it); k_first_hit_material / k_first_hit_material_wave follow it too (tools/bench_first_hit_material.py)"},
     {"WTGPU_LOS_PER_SAMPLE", K(los_per_sample), KNOB_U32, 1, 0, 1, "wtgpu_line_of_sight: 1 one lane per (element, sample) where the sensor's own elements are sampled and an element's samples fit a wavefront (k_los_sample: the lanes walk the emitters together and exchange their samples through LDS, lane j sums float j in sample order); 0 one lane per (element, emitter) always (k_los_pair) (A/B: tools/bench_los.py; the results do not depend on it)"},
     // ---- diagnostics and bring-up aids
     {"WTGPU_DEBUG_STAGE", K(dbg_stage), KNOB_INT, 1 << 30, INT_MIN, INT_MAX, "bring-up aid: stops launching the round kernels after stage n (INVALID RESULTS)"},

@@ -1,7 +1,8 @@
 // wave_tracer_amd — entry points that are neither a render nor read a film (wtgpu_film.hip): ray / cone / region queries, by-geometry sensor
-// masks, first-hit maps, line-of-sight maps, the probes of the kernel tests (wtgpu_test_hooks.h), the PMC calibration copy.
+// masks, first-hit maps, first-hit material maps, line-of-sight maps, the probes of the kernel tests (wtgpu_test_hooks.h), the PMC calibration copy.
 #include "wtgpu_host.h"
 #include "wt/first_hit.h"
+#include "wt/first_hit_material.h"
 #include "wt/flux_probe.h"
 #include "wt/los.h"
 #include "wt/sources_probe.h"
@@ -134,6 +135,72 @@ int wtgpu_first_hit_host(const wtgpu_scene* s, const wtgpu_first_hit_spec* spec,
         first_hit_host(s->host, spec->samples, spec->seed, spec->maps, spec->ids, n_threads, maps, ids);
     } catch (const std::exception& e) {
         return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+
+// ---- first-hit material maps (wt/first_hit_material.h, kernels_firsthit_material.hip) ------------------------------------------------------
+// the checks both forms share, and the query the kernels and the host twin take
+static int first_hit_material_check(const wtgpu_scene* s, const wtgpu_first_hit_material_spec* spec, const float* maps, const uint32_t* ids, fhm_query_t& q) {
+    if (!s || !spec) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (s->host.sensor.type != SENSOR_PERSPECTIVE)
+        return fail(WTGPU_ERR_INVALID, "first-hit material maps need a perspective sensor (a virtual-plane sensor has no primary ray through a pixel)");
+    if (spec->maps & ~(uint32_t)FHM_ALL_MAPS) return fail(WTGPU_ERR_INVALID, "first-hit material maps: unknown map bits (1 ALBEDO .. 16 EMISSION)");
+    if (spec->ids & ~(uint32_t)FHM_ALL_IDS) return fail(WTGPU_ERR_INVALID, "first-hit material maps: unknown id bits (1 MATERIAL, 2 TYPE)");
+    if (spec->n_k < 1 || spec->n_k > kFhmMaxK) return fail(WTGPU_ERR_INVALID, "first-hit material maps: 1 .. 4 wavenumbers expected (n_k)");
+    for (uint32_t j = 0; j < spec->n_k; ++j)
+        if (!finitef(spec->k[j]) || !(spec->k[j] > 0.f))
+            return fail(WTGPU_ERR_INVALID, "first-hit material maps: wavenumber " + std::to_string(j) + " is not finite and > 0 (k in 1/mm)");
+    if (spec->samples > kFhMaxSamples) return fail(WTGPU_ERR_INVALID, "first-hit material maps: 0 .. 4096 samples per pixel expected");
+    if (!spec->maps && !spec->ids) return fail(WTGPU_ERR_INVALID, "first-hit material maps: nothing requested (no map and no id bit)");
+    if (spec->maps && !maps) return fail(WTGPU_ERR_INVALID, "first-hit material maps: maps requested, but the maps pointer is NULL");
+    if (spec->ids && !ids) return fail(WTGPU_ERR_INVALID, "first-hit material maps: ids requested, but the ids pointer is NULL");
+    q.samples = spec->samples, q.maps = spec->maps, q.ids = spec->ids, q.n_k = spec->n_k, q.seed = spec->seed;
+    for (uint32_t j = 0; j < kFhmMaxK; ++j) q.k[j] = j < spec->n_k ? spec->k[j] : 0.f;
+    return WTGPU_OK;
+}
+int wtgpu_first_hit_material(wtgpu_scene* s, void* stream, const wtgpu_first_hit_material_spec* spec, float* d_maps, uint32_t* d_ids) {
+    fhm_query_t q;
+    if (const int rc = first_hit_material_check(s, spec, d_maps, d_ids, q)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    device_guard_t guard(s->device);
+    const int e = first_hit_material_launch(s->dev, static_cast<hipStream_t>(stream), q, s->knobs.first_hit_per_sample, d_maps, d_ids);
+    if (e) return fail(WTGPU_ERR_HIP, std::string("k_first_hit_material: ") + hipGetErrorString((hipError_t)e));
+    return WTGPU_OK;
+}
+int wtgpu_first_hit_material_host(const wtgpu_scene* s, const wtgpu_first_hit_material_spec* spec, uint32_t n_threads, float* maps, uint32_t* ids) {
+    fhm_query_t q;
+    if (const int rc = first_hit_material_check(s, spec, maps, ids, q)) return rc;
+    try {
+        first_hit_material_host(s->host, q, n_threads, maps, ids);
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+// One wavenumber per spectral channel of the sensor: the line of a discrete response, the response-weighted mean over the knots of a table.
+int wtgpu_scene_channel_wavenumbers(const wtgpu_scene* s, float k[4]) {
+    if (!s || !k) return fail(WTGPU_ERR_INVALID, "null argument");
+    const scene_t& sc = s->host;
+    for (uint32_t c = 0; c < 4; ++c) k[c] = 0.f;
+    for (uint32_t c = 0; c < sc.sensor.channels && c < 4; ++c) {
+        const int id = sc.sensor.response_spec[c];
+        const std::string ch = "channel wavenumbers: channel " + std::to_string(c);
+        if (id < 0 || (uint32_t)id >= sc.n_spectra) return fail(WTGPU_ERR_INVALID, ch + " has no response spectrum");
+        const spectrum_t sp = sc.spectra[id];
+        if (sp.type == SPEC_DISCRETE) {
+            k[c] = sp.kmin;
+            continue;
+        }
+        if (sp.type != SPEC_TABLE) return fail(WTGPU_ERR_INVALID, ch + " has a constant response: it singles out no wavenumber");
+        double num = 0., den = 0.;
+        for (uint32_t i = 0; i < sp.count; ++i) {
+            const double ki = sp.count > 1 ? (double)sp.kmin + ((double)sp.kmax - (double)sp.kmin) * (double)i / (double)(sp.count - 1) : (double)sp.kmin;
+            const double R = sc.spectra_data[sp.offset + i];
+            num += ki * R, den += R;
+        }
+        if (!(den > 0.)) return fail(WTGPU_ERR_INVALID, ch + " has an all-zero response: it singles out no wavenumber");
+        k[c] = (float)(num / den);
     }
     return WTGPU_OK;
 }

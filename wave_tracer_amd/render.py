@@ -150,6 +150,50 @@ def shadow_guides(scene, samples=0, seed=1, scales=None, t_min=None, emitters=No
     return guide, [float(s) for s in np.broadcast_to(np.asarray(scales, dtype=np.float64), (guide.shape[-1],))], None
 
 
+MATERIAL_GUIDE_SCALE = 1.0 / FIRST_HIT_GUIDE_KF ** 2   # material_guides' default scale for every plane: first_hit_guides' 2.78.  UNTUNED.
+
+
+def material_guides(scene, samples=0, seed=1, scales=None, host=False):
+    """A noise-free reflectance plane per spectral channel as guides of a feature-guided denoise(): albedo + specular + emission of
+    Scene.first_hit_material at Scene.channel_wavenumbers(), clamped to [0, 1] — what a checkerboard, a bitmap or a mask pattern on a flat wall
+    changes while every geometric guide stays constant.  Returns (guide, scales, None) as denoise(guides=...) takes it: guide [H, W, C] f32 on the
+    scene's device (host=True: numpy from the host twin, no device needed), C the spectral channels.  The scales default to 2.78 for every plane
+    as first_hit_guides' do and are UNTUNED.  A sensor that is not perspective is refused by first_hit_material itself."""
+    fm = (scene.first_hit_material_host if host else scene.first_hit_material)(samples, seed, None, ("albedo", "specular", "emission"), ())
+    total = fm["albedo"] + fm["specular"] + fm["emission"]
+    guide = np.ascontiguousarray(np.clip(total, np.float32(0), np.float32(1)), dtype=np.float32) if host else total.clamp(0.0, 1.0).contiguous()
+    if scales is None:
+        scales = MATERIAL_GUIDE_SCALE
+    return guide, [float(s) for s in np.broadcast_to(np.asarray(scales, dtype=np.float64), (guide.shape[-1],))], None
+
+
+def join_guides(*triples):
+    """Joins (guide, scales, ids) triples — first_hit_guides, shadow_guides, material_guides, or a caller's — into one for denoise(guides=...): the
+    planes and their scales concatenated in the order given, the ids of the first triple that has any.  All on the host (numpy) or all on one
+    device (torch).  More than 8 planes are refused: the guided filter takes no more."""
+    from .api import FILM_DENOISE_MAX_GUIDES
+    if not triples:
+        raise ValueError("join_guides: at least one (guide, scales, ids) triple expected")
+    planes, scales, ids = [], [], None
+    for guide, sc, i in triples:
+        if guide is not None:
+            guide = guide if guide.ndim == 3 else guide[..., None]
+            if len(sc) != guide.shape[-1]:
+                raise ValueError(f"join_guides: {guide.shape[-1]} planes with {len(sc)} scales")
+            planes.append(guide)
+            scales += [float(s) for s in sc]
+        if ids is None and i is not None:
+            ids = i
+    if len(scales) > FILM_DENOISE_MAX_GUIDES:
+        raise ValueError(f"join_guides: {len(scales)} planes, the guided filter takes at most {FILM_DENOISE_MAX_GUIDES}")
+    if not planes:
+        return None, [], ids
+    if isinstance(planes[0], np.ndarray):
+        return np.ascontiguousarray(np.concatenate(planes, axis=-1), dtype=np.float32), scales, ids
+    import torch
+    return torch.cat(planes, dim=-1).contiguous(), scales, ids
+
+
 def denoise(scene, films_a, films_b, spe, guides=None, **kw):
     """Denoises the film that the half-films A and B add up to (render_to_noise(..., halves=True); `spe` samples per element each): films_a / films_b
     are (value, weight, light), torch tensors on the scene's device (Scene.film_denoise_device: everything stays there) or numpy arrays
@@ -267,6 +311,21 @@ def first_hit(scene, samples=0, seed=1, maps=("coverage", "depth", "position", "
         out = scene.first_hit(samples, seed, maps, ids)
         torch.cuda.synchronize(dev)
     return {k: v.cpu().numpy().view(np.uint32) if v.dtype == torch.int32 else v.cpu().numpy() for k, v in out.items()}
+
+
+def first_hit_material(scene, samples=0, seed=1, k=None, maps=("albedo", "specular", "opacity", "roughness", "emission"), ids=("material", "type"),
+                       device=0):
+    """The scene's first-hit material maps (Scene.first_hit_material: albedo, specular reflectance, opacity, roughness and emission per pixel and
+    wavenumber, material index and leaf type) computed on one GPU, as {name: numpy array} (ids: uint32, 0xFFFFFFFF without a hit).  Uploads the
+    scene like render()."""
+    import torch
+    if scene.device is None:
+        scene.upload(device)
+    dev = torch.device("cuda", scene.device)
+    with torch.cuda.device(dev):
+        out = scene.first_hit_material(samples, seed, k, maps, ids)
+        torch.cuda.synchronize(dev)
+    return {n: v.cpu().numpy().view(np.uint32) if v.dtype == torch.int32 else v.cpu().numpy() for n, v in out.items()}
 
 
 def shard_samples(spp, rank, world):
