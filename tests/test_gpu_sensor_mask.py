@@ -22,7 +22,7 @@ def _same(sc, **kw):
     return dev
 
 
-@pytest.mark.parametrize("samples", [32, 7])
+@pytest.mark.parametrize("samples", [32, 7, 1, 64])   # (1: sixty-four pixels per wavefront; 64: the wavefront is one pixel)
 def test_device_mask_equals_host(built, tmp_path, samples):
     from wave_tracer_amd import Scene
     # the analytic scene: ground rectangles A (matches) and B, sky beyond

@@ -142,6 +142,12 @@ def test_analytic_scene(built, tmp_path):
     assert len(np.unique(m24[:, edge])) > 2 and (m24[:, full] == _seq_sum(24, 24)).all() and (m24[:, none] == 0).all()
     # seven samples per pixel: 1/7 does not add up to 1 exactly, the fully covered pixels hold the f32 sum of seven sevenths
     assert (sc.sensor_mask_host(samples=7)[:, full] == _seq_sum(7, 7)).all()
+    # one sample per pixel: 0 or 1, nothing between; sixty-four: 1/64 adds up exactly, so every value is n/64 and the full pixels are 1
+    m1 = sc.sensor_mask_host(samples=1, seed=5)
+    assert np.isin(m1, [0, 1]).all() and (m1[:, full] == 1).all() and (m1[:, none] == 0).all() and len(np.unique(m1[:, edge])) == 2
+    m64 = sc.sensor_mask_host(samples=64, seed=5)
+    assert np.isin(m64, np.arange(65, dtype=np.float32) / np.float32(64)).all() and (m64[:, full] == 1).all() and (m64[:, none] == 0).all()
+    assert len(np.unique(m64[:, edge])) > 2
 
 
 def test_unnamed_shapes_are_numbered_like_the_reference(built, tmp_path):

@@ -290,6 +290,43 @@ def _check(rc):
         raise WtgpuError(f"wtgpu error {rc}: {load_library().wtgpu_last_error().decode(errors='replace')}")
 
 
+def _bit_groups(names, table, what, who, n_k=None):
+    """One group of a map spec -> (bits, layout, total): `names` in any order, bit i and the memory order from table[i] = (name, n) or name.
+    layout: [(name, offset, width)], width 0 = one value without an axis of its own.  n_k: every entry is n_k values (the material maps)."""
+    names = [names] if isinstance(names, str) else list(names)
+    table = [(e, 1) if isinstance(e, str) else e for e in table]
+    known = [n for n, _ in table]
+    for n in names:
+        if n not in known:
+            raise ValueError(f"{who}: unknown {what} {n!r} (one of {known})")
+    bits, layout, off = 0, [], 0
+    for i, (n, k) in enumerate(table):
+        if n in names:
+            k = k if n_k is None else k * n_k
+            bits |= 1 << i
+            layout.append((n, off, 0 if k == 1 and n_k is None else k))
+            off += k
+    return bits, layout, off
+
+
+def _views(layouts, arrays):
+    """{name: view} of one array [..., K] per group (None where K = 0) by the group's layout (_bit_groups)."""
+    return {n: a[..., off:off + k] if k else a[..., off] for layout, a in zip(layouts, arrays) for n, off, k in layout}
+
+
+def _map_outputs(shapes, dev=None):
+    """One array per group of shape `shape` (None where its last extent is 0), the last group the ids: torch tensors on `dev` (ids int32), or
+    zeroed numpy arrays (ids uint32).  -> the arrays and their addresses."""
+    ids = len(shapes) - 1
+    if dev is not None:
+        import torch
+        arrays = [torch.empty(s, dtype=torch.int32 if g == ids else torch.float32, device=dev) if s[-1] else None for g, s in enumerate(shapes)]
+        return arrays, [None if a is None else a.data_ptr() for a in arrays]
+    import numpy as np
+    arrays = [np.zeros(s, np.uint32 if g == ids else np.float32) if s[-1] else None for g, s in enumerate(shapes)]
+    return arrays, [None if a is None else a.ctypes.data for a in arrays]
+
+
 class Scene:
     """Handle of a flattened scene (host-baked; optionally uploaded to one GPU)."""
 
@@ -626,9 +663,7 @@ class Scene:
         primary rays whose first hit is on a shape that does NOT match the mask.  samples: None = the scene file's (32).  shapes: None = the
         scene file's flags, else one flag per shape (true = matches the regex: not counted).  Enqueued on `stream` (default: torch's current)."""
         import torch
-        if self.device is None:
-            raise WtgpuError("sensor_mask: upload(device) first")
-        dev = torch.device("cuda", self.device)
+        dev = self._uploaded_device("sensor_mask")
         n, flags = self._mask_args(samples, shapes)
         out = torch.empty((self.height, self.width), dtype=torch.float32, device=dev)
         _check(load_library().wtgpu_sensor_mask(self._h, self._stream_arg(stream, dev), None if flags is None else flags.ctypes.data, n, int(seed),
@@ -643,33 +678,18 @@ class Scene:
         _check(load_library().wtgpu_sensor_mask_host(self._h, None if flags is None else flags.ctypes.data, n, int(seed), int(threads), out.ctypes.data))
         return out
 
-    @staticmethod
-    def _first_hit_args(samples, seed, maps, ids):
-        """-> (wtgpu_first_hit_spec, [(name, offset, n)] of the maps, K, the same of the ids, Ki); names in any order, memory in bit order."""
-        def group(names, table, what):
-            names = [names] if isinstance(names, str) else list(names)
-            known = [n for n, _ in table]
-            for n in names:
-                if n not in known:
-                    raise ValueError(f"first_hit: unknown {what} {n!r} (one of {known})")
-            bits, layout, off = 0, [], 0
-            for i, (n, k) in enumerate(table):
-                if n in names:
-                    bits |= 1 << i
-                    layout.append((n, off, k))
-                    off += k
-            return bits, layout, off
-        mbits, mlay, K = group(maps, FIRST_HIT_MAPS, "map")
-        ibits, ilay, Ki = group(ids, FIRST_HIT_IDS, "id")
-        return FirstHitSpec(int(samples), mbits, ibits, 0, int(seed)), mlay, K, ilay, Ki
+    def _uploaded_device(self, who):
+        import torch
+        if self.device is None:
+            raise WtgpuError(f"{who}: upload(device) first")
+        return torch.device("cuda", self.device)
 
     @staticmethod
-    def _first_hit_views(out, mlay, ilay, m, i):
-        for n, off, k in mlay:
-            out[n] = m[..., off] if k == 1 else m[..., off:off + k]
-        for n, off, k in ilay:
-            out[n] = i[..., off]
-        return out
+    def _first_hit_args(samples, seed, maps, ids):
+        """-> (wtgpu_first_hit_spec, the layouts of the maps and of the ids, (K, Ki)); names in any order, memory in bit order."""
+        mbits, mlay, K = _bit_groups(maps, FIRST_HIT_MAPS, "map", "first_hit")
+        ibits, ilay, Ki = _bit_groups(ids, FIRST_HIT_IDS, "id", "first_hit")
+        return FirstHitSpec(int(samples), mbits, ibits, 0, int(seed)), (mlay, ilay), (K, Ki)
 
     def first_hit(self, samples=0, seed=1, maps=("coverage", "depth", "position", "normal_geo", "normal_shading", "uv", "facing"), ids=("shape", "triangle"),
                   stream=None):
@@ -678,26 +698,19 @@ class Scene:
         shape_ids is listed by; triangle: within the shape; -1 = 0xFFFFFFFF without a hit) — views of one allocation per group.  samples 0:
         the ray through every pixel's centre; n >= 1: the n rays of sensor_mask(samples=n, seed), the maps their means over the rays that hit,
         the ids the first hitting ray's.  Enqueued on `stream` (default: torch's current)."""
-        import torch
-        if self.device is None:
-            raise WtgpuError("first_hit: upload(device) first")
-        dev = torch.device("cuda", self.device)
-        spec, mlay, K, ilay, Ki = self._first_hit_args(samples, seed, maps, ids)
-        m = torch.empty((self.height, self.width, K), dtype=torch.float32, device=dev) if K else None
-        i = torch.empty((self.height, self.width, Ki), dtype=torch.int32, device=dev) if Ki else None
-        _check(load_library().wtgpu_first_hit(self._h, self._stream_arg(stream, dev), C.byref(spec), m.data_ptr() if K else None,
-                                              i.data_ptr() if Ki else None))
-        return self._first_hit_views({}, mlay, ilay, m, i)
+        dev = self._uploaded_device("first_hit")
+        spec, layouts, Ks = self._first_hit_args(samples, seed, maps, ids)
+        arrays, (m, i) = _map_outputs([(self.height, self.width, K) for K in Ks], dev)
+        _check(load_library().wtgpu_first_hit(self._h, self._stream_arg(stream, dev), C.byref(spec), m, i))
+        return _views(layouts, arrays)
 
     def first_hit_host(self, samples=0, seed=1, maps=("coverage", "depth", "position", "normal_geo", "normal_shading", "uv", "facing"),
                        ids=("shape", "triangle"), threads=0):
         """The same maps on host threads (wtgpu_first_hit_host; threads 0 = all cores), as numpy (ids: uint32): bit for bit the device's."""
-        import numpy as np
-        spec, mlay, K, ilay, Ki = self._first_hit_args(samples, seed, maps, ids)
-        m = np.zeros((self.height, self.width, K), np.float32) if K else None
-        i = np.zeros((self.height, self.width, Ki), np.uint32) if Ki else None
-        _check(load_library().wtgpu_first_hit_host(self._h, C.byref(spec), int(threads), m.ctypes.data if K else None, i.ctypes.data if Ki else None))
-        return self._first_hit_views({}, mlay, ilay, m, i)
+        spec, layouts, Ks = self._first_hit_args(samples, seed, maps, ids)
+        arrays, (m, i) = _map_outputs([(self.height, self.width, K) for K in Ks])
+        _check(load_library().wtgpu_first_hit_host(self._h, C.byref(spec), int(threads), m, i))
+        return _views(layouts, arrays)
 
     def channel_wavenumbers(self):
         """One wavenumber [1/mm] per spectral channel (wtgpu_scene_channel_wavenumbers), numpy f32 [spectral_channels]: the line of a discrete
@@ -708,21 +721,15 @@ class Scene:
         return k[:self.spectral_channels].copy()
 
     def _first_hit_material_args(self, samples, seed, k, maps, ids):
-        """-> (wtgpu_first_hit_material_spec, the map names in memory order, n_k, the id names in memory order); names in any order."""
+        """-> (wtgpu_first_hit_material_spec, the layouts of the maps and of the ids, (K, Ki)); names in any order, memory in bit order."""
         import numpy as np
-        def group(names, known, what):
-            names = [names] if isinstance(names, str) else list(names)
-            for n in names:
-                if n not in known:
-                    raise ValueError(f"first_hit_material: unknown {what} {n!r} (one of {known})")
-            return sum(1 << i for i, n in enumerate(known) if n in names), [n for n in known if n in names]
-        mbits, mnames = group(maps, FIRST_HIT_MATERIAL_MAPS, "map")
-        ibits, inames = group(ids, FIRST_HIT_MATERIAL_IDS, "id")
         k = self.channel_wavenumbers() if k is None else np.atleast_1d(np.asarray(k, dtype=np.float32))
         if k.ndim != 1:
             raise ValueError("first_hit_material: k: a sequence of wavenumbers [1/mm] expected")
+        mbits, mlay, K = _bit_groups(maps, FIRST_HIT_MATERIAL_MAPS, "map", "first_hit_material", n_k=int(k.size))
+        ibits, ilay, Ki = _bit_groups(ids, FIRST_HIT_MATERIAL_IDS, "id", "first_hit_material")
         kk = (C.c_float * 4)(*[float(x) for x in k[:4]])
-        return FirstHitMaterialSpec(int(samples), mbits, ibits, int(k.size), kk, int(seed)), mnames, int(k.size), inames
+        return FirstHitMaterialSpec(int(samples), mbits, ibits, int(k.size), kk, int(seed)), (mlay, ilay), (K, Ki)
 
     def first_hit_material(self, samples=0, seed=1, k=None, maps=("albedo", "specular", "opacity", "roughness", "emission"), ids=("material", "type"),
                            stream=None):
@@ -731,52 +738,26 @@ class Scene:
         of `k`, 1 .. 4 of them in 1/mm; None: channel_wavenumbers()) and int32 ids [H, W] holding the u32 bits (material: its index; type: the
         leaf type at k[0]; -1 = 0xFFFFFFFF without a hit) — views of one allocation per group.  The rays are first_hit's for the same samples and
         seed; the maps are means over the rays that hit, the ids the first hitting ray's.  Enqueued on `stream` (default: torch's current)."""
-        import torch
-        if self.device is None:
-            raise WtgpuError("first_hit_material: upload(device) first")
-        dev = torch.device("cuda", self.device)
-        spec, mnames, n_k, inames = self._first_hit_material_args(samples, seed, k, maps, ids)
-        K, Ki = len(mnames) * n_k, len(inames)
-        m = torch.empty((self.height, self.width, K), dtype=torch.float32, device=dev) if K else None
-        i = torch.empty((self.height, self.width, Ki), dtype=torch.int32, device=dev) if Ki else None
-        _check(load_library().wtgpu_first_hit_material(self._h, self._stream_arg(stream, dev), C.byref(spec), m.data_ptr() if K else None,
-                                                       i.data_ptr() if Ki else None))
-        out = {n: m[..., j * n_k:(j + 1) * n_k] for j, n in enumerate(mnames)}
-        out.update({n: i[..., j] for j, n in enumerate(inames)})
-        return out
+        dev = self._uploaded_device("first_hit_material")
+        spec, layouts, Ks = self._first_hit_material_args(samples, seed, k, maps, ids)
+        arrays, (m, i) = _map_outputs([(self.height, self.width, K) for K in Ks], dev)
+        _check(load_library().wtgpu_first_hit_material(self._h, self._stream_arg(stream, dev), C.byref(spec), m, i))
+        return _views(layouts, arrays)
 
     def first_hit_material_host(self, samples=0, seed=1, k=None, maps=("albedo", "specular", "opacity", "roughness", "emission"),
                                 ids=("material", "type"), threads=0):
         """The same maps on host threads (wtgpu_first_hit_material_host; threads 0 = all cores), as numpy (ids: uint32): bit for bit the device's."""
-        import numpy as np
-        spec, mnames, n_k, inames = self._first_hit_material_args(samples, seed, k, maps, ids)
-        K, Ki = len(mnames) * n_k, len(inames)
-        m = np.zeros((self.height, self.width, K), np.float32) if K else None
-        i = np.zeros((self.height, self.width, Ki), np.uint32) if Ki else None
-        _check(load_library().wtgpu_first_hit_material_host(self._h, C.byref(spec), int(threads), m.ctypes.data if K else None,
-                                                            i.ctypes.data if Ki else None))
-        out = {n: m[..., j * n_k:(j + 1) * n_k] for j, n in enumerate(mnames)}
-        out.update({n: i[..., j] for j, n in enumerate(inames)})
-        return out
+        spec, layouts, Ks = self._first_hit_material_args(samples, seed, k, maps, ids)
+        arrays, (m, i) = _map_outputs([(self.height, self.width, K) for K in Ks])
+        _check(load_library().wtgpu_first_hit_material_host(self._h, C.byref(spec), int(threads), m, i))
+        return _views(layouts, arrays)
 
     def _los_args(self, samples, seed, emitters, maps, elem, ids, front_only, t_min):
-        """-> (wtgpu_los_spec, E, then per group [(name, offset, n)] and its floats / words); names in any order, memory in bit order."""
-        def group(names, table, what):
-            names = [names] if isinstance(names, str) else list(names)
-            known = [n for n, _ in table]
-            for n in names:
-                if n not in known:
-                    raise ValueError(f"line_of_sight: unknown {what} {n!r} (one of {known})")
-            bits, layout, off = 0, [], 0
-            for i, (n, k) in enumerate(table):
-                if n in names:
-                    bits |= 1 << i
-                    layout.append((n, off, k))
-                    off += k
-            return bits, layout, off
-        mbits, mlay, K = group(maps, LOS_MAPS, "map")
-        ebits, elay, Ke = group(elem, LOS_ELEM, "element map")
-        ibits, ilay, Ki = group(ids, LOS_IDS, "id")
+        """-> (wtgpu_los_spec, the layouts of the pair maps, the element maps and the ids, their [H, W, ...] shapes); names in any order, memory
+        in bit order."""
+        mbits, mlay, K = _bit_groups(maps, LOS_MAPS, "map", "line_of_sight")
+        ebits, elay, Ke = _bit_groups(elem, LOS_ELEM, "element map", "line_of_sight")
+        ibits, ilay, Ki = _bit_groups(ids, LOS_IDS, "id", "line_of_sight")
         if emitters is None:
             sel = []
             E = sum(1 for e in self.emitter_summary() if e["type"] != "area")
@@ -786,18 +767,7 @@ class Scene:
             if E == 0 or E > LOS_MAX_EMITTERS or min(sel) < 0:
                 raise ValueError(f"line_of_sight: 1 .. {LOS_MAX_EMITTERS} emitter indices expected (None: every emitter that is not an area emitter)")
         spec = LosSpec(int(samples), mbits, ebits, ibits, LOS_FRONT_ONLY if front_only else 0, len(sel), (C.c_uint32 * 32)(*sel), float(t_min), 0, int(seed))
-        return spec, E, (mlay, K), (elay, Ke), (ilay, Ki)
-
-    @staticmethod
-    def _los_views(mlay, elay, ilay, m, e, i):
-        out = {}
-        for n, off, k in mlay:
-            out[n] = m[..., off] if k == 1 else m[..., off:off + k]
-        for n, off, k in elay:
-            out[n] = e[..., off] if k == 1 else e[..., off:off + k]
-        for n, off, k in ilay:
-            out[n] = i[..., off]
-        return out
+        return spec, (mlay, elay, ilay), [(self.height, self.width, E, K), (self.height, self.width, Ke), (self.height, self.width, Ki)]
 
     def line_of_sight(self, samples=0, seed=1, emitters=None, maps=("visible", "distance"), elem=(), ids=("n_visible", "nearest"), front_only=True,
                       points=None, normals=None, mask=None, t_min=0.0, stream=None):
@@ -811,21 +781,16 @@ class Scene:
         front_only and cos need a normal.  mask: None or f32 [H, W] there, elements with mask <= 0 trace nothing and hold 0 / -1.  t_min: the
         start of the rays' range (a surface point must not shadow itself).  Enqueued on `stream` (default: torch's current)."""
         import torch
-        if self.device is None:
-            raise WtgpuError("line_of_sight: upload(device) first")
-        dev = torch.device("cuda", self.device)
+        dev = self._uploaded_device("line_of_sight")
         n = self.width * self.height
         for t, name, numel in ((points, "points", 3 * n), (normals, "normals", 3 * n), (mask, "mask", n)):
             if t is not None and not (t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.numel() == numel and t.is_contiguous()):
                 raise ValueError(f"line_of_sight: {name}: a contiguous torch.float32 tensor of {numel} elements on cuda:{self.device} expected")
-        spec, E, (mlay, K), (elay, Ke), (ilay, Ki) = self._los_args(samples, seed, emitters, maps, elem, ids, front_only, t_min)
-        m = torch.empty((self.height, self.width, E, K), dtype=torch.float32, device=dev) if K else None
-        e = torch.empty((self.height, self.width, Ke), dtype=torch.float32, device=dev) if Ke else None
-        i = torch.empty((self.height, self.width, Ki), dtype=torch.int32, device=dev) if Ki else None
+        spec, layouts, shapes = self._los_args(samples, seed, emitters, maps, elem, ids, front_only, t_min)
+        arrays, (m, e, i) = _map_outputs(shapes, dev)
         ptr = lambda t: None if t is None else t.data_ptr()
-        _check(load_library().wtgpu_line_of_sight(self._h, self._stream_arg(stream, dev), C.byref(spec), ptr(points), ptr(normals), ptr(mask), ptr(m), ptr(e),
-                                                  ptr(i)))
-        return self._los_views(mlay, elay, ilay, m, e, i)
+        _check(load_library().wtgpu_line_of_sight(self._h, self._stream_arg(stream, dev), C.byref(spec), ptr(points), ptr(normals), ptr(mask), m, e, i))
+        return _views(layouts, arrays)
 
     def line_of_sight_host(self, samples=0, seed=1, emitters=None, maps=("visible", "distance"), elem=(), ids=("n_visible", "nearest"), front_only=True,
                            points=None, normals=None, mask=None, t_min=0.0, threads=0):
@@ -837,13 +802,11 @@ class Scene:
         for t, name, numel in ((points, "points", 3 * n), (normals, "normals", 3 * n), (mask, "mask", n)):
             if t is not None and t.size != numel:
                 raise ValueError(f"line_of_sight_host: {name}: {numel} floats expected")
-        spec, E, (mlay, K), (elay, Ke), (ilay, Ki) = self._los_args(samples, seed, emitters, maps, elem, ids, front_only, t_min)
-        m = np.zeros((self.height, self.width, E, K), np.float32) if K else None
-        e = np.zeros((self.height, self.width, Ke), np.float32) if Ke else None
-        i = np.zeros((self.height, self.width, Ki), np.uint32) if Ki else None
+        spec, layouts, shapes = self._los_args(samples, seed, emitters, maps, elem, ids, front_only, t_min)
+        arrays, (m, e, i) = _map_outputs(shapes)
         ptr = lambda t: None if t is None else t.ctypes.data
-        _check(load_library().wtgpu_line_of_sight_host(self._h, C.byref(spec), ptr(points), ptr(normals), ptr(mask), int(threads), ptr(m), ptr(e), ptr(i)))
-        return self._los_views(mlay, elay, ilay, m, e, i)
+        _check(load_library().wtgpu_line_of_sight_host(self._h, C.byref(spec), ptr(points), ptr(normals), ptr(mask), int(threads), m, e, i))
+        return _views(layouts, arrays)
 
     @property
     def tonemap_spec(self):

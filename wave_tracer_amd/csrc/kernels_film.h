@@ -1,6 +1,6 @@
 // wave_tracer_amd — what the film kernels (kernels_develop.hip, kernels_stats.hip, kernels_compare.hip, kernels_polar.hip, kernels_denoise.hip) and their host twins share beyond the
 // arithmetic of wt/film_stats.h: the chunk geometry of the fixed summation order on a wavefront, the reduction of the chunk sums, the grid that
-// follows the film, the choice of a kernel by (channels, luminance), and the host threads of the twins (kernels_mask.hip's too).
+// follows the film, the choice of a kernel by (channels, luminance), and the host threads of the twins (the sensor-element maps' too: kernels_maps.h).
 //
 // Chunk geometry.  A block is kFilmBlock = 256 threads, four wavefronts; a wavefront owns whole chunks of kFsChunk = 256 elements.  Wavefront g
 // of the grid takes chunks g, g + waves, ... (film_first_chunk, film_waves); of chunk k lane l holds elements 256 k + 64 j + l, j = 0 .. 3 (four

@@ -4,7 +4,7 @@
 // (a miss counts as nothing).  The reference accumulates 1 / float(samples) per such sample in a float: the integer count is reproduced
 // here as that same sequential f32 sum (mask_value), so the device, the host threads and the reference agree bit for bit.
 // No render kernel is compiled here.
-#include "kernels_film.h"   // (on_threads)
+#include "kernels_maps.h"
 
 namespace wtk {
 
@@ -28,41 +28,32 @@ WT_HD float mask_value(uint32_t n, uint32_t samples) {
     return v;
 }
 
-// One lane per pixel: the lane traces the pixel's samples one after the other.
+// One lane per pixel (kernels_maps.h: on_lane_element): the lane traces the pixel's samples one after the other.
 __global__ void __launch_bounds__(kBlock) k_sensor_mask_lane(scene_t sc, const uint8_t* shape_matches, uint32_t samples, uint64_t seed, float* out) {
     __shared__ stack_entry_t lds[kLdsStack * kBlock];
-    const uint32_t W = sc.sensor.width, npix = W * sc.sensor.height;
-    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-    if (p >= npix) return;
-    stack_entry_t spill[kSpillStack];
-    stack_ref_t stack;
-    lds_stack(lds, spill, stack);
-    uint32_t n = 0;
-    for (uint32_t s = 0; s < samples; ++s) n += mask_sample_counts(sc, shape_matches, p % W, p / W, samples, s, seed, stack) ? 1u : 0u;
-    out[p] = mask_value(n, samples);
+    const uint32_t W = sc.sensor.width;
+    on_lane_element(lds, W * sc.sensor.height, [&](uint32_t p, const stack_ref_t& stack) {
+        uint32_t n = 0;
+        for (uint32_t s = 0; s < samples; ++s) n += mask_sample_counts(sc, shape_matches, p % W, p / W, samples, s, seed, stack) ? 1u : 0u;
+        out[p] = mask_value(n, samples);
+    });
 }
 
-// One lane per sample (samples <= 64): a wavefront holds 64 / samples pixels, lanes [g * samples, (g + 1) * samples) the samples of its g-th;
-// the count of a pixel is the popcount of its lanes' bits in one ballot, written by the pixel's first lane.  Every lane reaches the ballot.
+// One lane per sample (samples <= 64; kernels_maps.h: sample_lane): the count of a pixel is the popcount of its lanes' bits in one ballot,
+// written by the pixel's first lane.  Every lane reaches the ballot.
 __global__ void __launch_bounds__(kBlock) k_sensor_mask_wave(scene_t sc, const uint8_t* shape_matches, uint32_t samples, uint64_t seed, float* out) {
     __shared__ stack_entry_t lds[kLdsStack * kBlock];
-    const uint32_t W = sc.sensor.width, npix = W * sc.sensor.height;
-    const uint32_t per_wave = 64u / samples;
-    const uint32_t lane = threadIdx.x & 63u, g = lane / samples, s = lane - g * samples;
-    const uint64_t p = ((blockIdx.x * (uint64_t)kBlock + threadIdx.x) >> 6) * per_wave + g;
-    const bool active = g < per_wave && p < npix;
+    const uint32_t W = sc.sensor.width;
+    const sample_lane_t l = sample_lane(samples, W * sc.sensor.height);
     bool counts = false;
-    if (active) {
+    if (l.active) {
         stack_entry_t spill[kSpillStack];
         stack_ref_t stack;
         lds_stack(lds, spill, stack);
-        counts = mask_sample_counts(sc, shape_matches, (uint32_t)(p % W), (uint32_t)(p / W), samples, s, seed, stack);
+        counts = mask_sample_counts(sc, shape_matches, (uint32_t)(l.p % W), (uint32_t)(l.p / W), samples, l.s, seed, stack);
     }
     const unsigned long long bits = __ballot(counts);
-    if (active && s == 0) {
-        const unsigned long long mine = samples == 64u ? bits : (bits >> (g * samples)) & ((1ull << samples) - 1ull);
-        out[p] = mask_value((uint32_t)__popcll(mine), samples);
-    }
+    if (l.active && l.s == 0) out[l.p] = mask_value((uint32_t)__popcll(group_bits(bits, l, samples)), samples);
 }
 
 int sensor_mask_launch(const scene_t& sc, hipStream_t stream, const uint8_t* d_shape_matches, uint32_t samples, uint64_t seed, float* d_out) {
@@ -70,29 +61,19 @@ int sensor_mask_launch(const scene_t& sc, hipStream_t stream, const uint8_t* d_s
     if (npix == 0 || samples == 0) return 0;
     // one lane per sample wherever a pixel's samples fit one wavefront: on the MI355X the radio overview (1440 x 1080, 32 samples) takes
     // 1.90 ms against 2.44 ms with one lane per pixel (median of 15 calls each, alternated); beyond 64 samples one lane per pixel
-    if (samples <= 64u) {
-        const uint64_t waves = (npix + 64u / samples - 1) / (64u / samples);
-        const uint64_t blocks = (waves * 64u + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(k_sensor_mask_wave, dim3((uint32_t)blocks), dim3(kBlock), 0, stream, sc, d_shape_matches, samples, seed, d_out);
-    } else
-        hipLaunchKernelGGL(k_sensor_mask_lane, dim3((uint32_t)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, sc, d_shape_matches, samples, seed,
-                           d_out);
+    if (samples <= 64u)
+        hipLaunchKernelGGL(k_sensor_mask_wave, dim3(sample_blocks(npix, samples)), dim3(kBlock), 0, stream, sc, d_shape_matches, samples, seed, d_out);
+    else
+        hipLaunchKernelGGL(k_sensor_mask_lane, dim3(lane_blocks(npix)), dim3(kBlock), 0, stream, sc, d_shape_matches, samples, seed, d_out);
     return (int)hipGetLastError();
 }
 
-// The same computation on host threads, from the host description (the reference's own CPU job: one task per row, mask.cpp:44-61).  The
-// stack holds 64 entries like the device's (kLdsStack + kSpillStack): a full stack drops the same children on both.
+// The same computation on host threads, from the host description (kernels_maps.h: on_elements).
 void sensor_mask_host(const scene_t& sc, const uint8_t* shape_matches, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out) {
-    const uint32_t W = sc.sensor.width, H = sc.sensor.height;
-    on_threads(H, n_threads, [&](auto claim) {
-        stack_entry_t entries[kLdsStack + kSpillStack];
-        const stack_ref_t stack = make_stack_ref(entries, 1, kLdsStack + kSpillStack, kLdsStack + kSpillStack, nullptr);
-        for (uint32_t y = (uint32_t)claim(); y < H; y = (uint32_t)claim())
-            for (uint32_t x = 0; x < W; ++x) {
-                uint32_t n = 0;
-                for (uint32_t s = 0; s < samples; ++s) n += mask_sample_counts(sc, shape_matches, x, y, samples, s, seed, stack) ? 1u : 0u;
-                out[(size_t)y * W + x] = mask_value(n, samples);
-            }
+    on_elements(sc, n_threads, [&](uint32_t x, uint32_t y, size_t p, const stack_ref_t& stack) {
+        uint32_t n = 0;
+        for (uint32_t s = 0; s < samples; ++s) n += mask_sample_counts(sc, shape_matches, x, y, samples, s, seed, stack) ? 1u : 0u;
+        out[p] = mask_value(n, samples);
     });
 }
 

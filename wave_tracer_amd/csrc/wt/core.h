@@ -65,6 +65,8 @@ WT_HD bool finitef(float x) {
     return (u & 0x7f800000u) != 0x7f800000u;
 }
 WT_HD float fractf(float x) { return x - floorf(x); }
+// one more term of a sequential f32 sum, first term first (the element maps' means: wt/first_hit.h, wt/first_hit_material.h, wt/los.h)
+WT_HD float seq_add(bool first, float sum, float x) { return first ? x : sum + x; }
 
 // ---- error-free transforms (include/wt/math/eft/eft.hpp) ------------------------------------
 // a*b - c*d with one fma-based correction (Kahan).

@@ -2,7 +2,7 @@
 // primary rays see first — coverage, depth, position, the geometric and the shading normal, uv, facing, shape and triangle ids.  The rays are
 // the sensor mask's (wt/sources.h: persp_sample_mean_ray; `samples` = 0: the one ray through the pixel's centre, no draw), the hit is the ray
 // query's (wt/bvh.h: ads_intersect_ray) and the surface is the integrators' (wt/beam.h: make_surface, normal maps included): nothing is
-// restated here.  The device kernels and the host twin run fh_sample, fh_add and fh_mean, so they agree bit for bit.
+// restated here.  The device kernels and the host twin run fh_sample, seq_add and fh_mean, so they agree bit for bit.
 #pragma once
 #include "beam.h"
 #include "bvh.h"
@@ -83,12 +83,11 @@ WT_HD bool fh_sample(const scene_t& sc, uint32_t px, uint32_t py, uint32_t sampl
     return true;
 }
 
-// one more term of a sequential f32 sum, first term first
-WT_HD float fh_add(bool first, float sum, float x) { return first ? x : sum + x; }
-// float j of a pixel from its sum over n_hit hitting samples of `samples`: the coverage, or the mean (0 without a hit: the sum is 0)
+// the mean of a sum (wt/core.h: seq_add) over n_hit hitting samples (0 without a hit: the sum is 0)
+WT_HD float fh_hit_mean(float sum, uint32_t n_hit) { return sum / (n_hit ? float(n_hit) : 1.f); }
+// float j of a pixel from its sum over n_hit hitting samples of `samples`: the coverage, or the mean
 WT_HD float fh_mean(uint32_t j, float sum, uint32_t n_hit, uint32_t samples) {
-    if (j == 0) return float(n_hit) / float(samples ? samples : 1u);
-    return sum / (n_hit ? float(n_hit) : 1.f);
+    return j == 0 ? float(n_hit) / float(samples ? samples : 1u) : fh_hit_mean(sum, n_hit);
 }
 
 // A pixel by one thread: its samples in order, each hit added to the sums.
@@ -105,7 +104,7 @@ WT_HD fh_sums_t fh_pixel(const scene_t& sc, uint32_t px, uint32_t py, uint32_t s
         const bool first = a.n_hit == 0;
         if (first) a.shape = r.shape, a.tri = r.tri;
 #pragma unroll
-        for (uint32_t j = 1; j < kFhFloats; ++j) a.v[j] = fh_add(first, a.v[j], r.v[j]);
+        for (uint32_t j = 1; j < kFhFloats; ++j) a.v[j] = seq_add(first, a.v[j], r.v[j]);
         ++a.n_hit;
     }
     return a;

@@ -3,7 +3,7 @@
 // smooth interface for the view direction, mask opacity, roughness, emitted radiance, and the material's index and leaf type.  The rays, the hit
 // and the surface are wt/first_hit.h's (fh_ray, ads_intersect_ray, make_surface), the material is the integrators' (wt/bsdf.h: material_resolve,
 // material_reflectance, material_IOR; wt/polar.h: fresnel, fresnel_reflection) and the radiance is the emitters' (wt/sources.h:
-// area_spectral_radiance): nothing is restated here.  The device kernels and the host twin run fhm_sample, fh_add and fhm_mean, so they agree
+// area_spectral_radiance): nothing is restated here.  The device kernels and the host twin run fhm_sample, seq_add and fh_hit_mean, so they agree
 // bit for bit (a function texture with libm opcodes excepted: wt/scene.h texture_function).
 #pragma once
 #include "bsdf.h"
@@ -127,9 +127,6 @@ WT_HD bool fhm_sample(const scene_t& sc, const fhm_query_t& q, uint32_t px, uint
     return true;
 }
 
-// a pixel's float from its sum over n_hit hitting samples: the mean, formed as fh_mean forms it (0 without a hit: the sum is 0)
-WT_HD float fhm_mean(float sum, uint32_t n_hit) { return fh_mean(1u, sum, n_hit, 1u); }
-
 // A pixel by one thread: its samples in order, each hit added to the sums.
 template <bool specular>
 WT_HD fhm_sums_t fhm_pixel(const scene_t& sc, const fhm_query_t& q, uint32_t px, uint32_t py, const stack_ref_t& stack) {
@@ -145,7 +142,7 @@ WT_HD fhm_sums_t fhm_pixel(const scene_t& sc, const fhm_query_t& q, uint32_t px,
         const bool first = a.n_hit == 0;
         if (first) a.material = r.material, a.type = r.type;
 #pragma unroll
-        for (uint32_t j = 0; j < kFhmFloats; ++j) a.v[j] = fh_add(first, a.v[j], r.v[j]);
+        for (uint32_t j = 0; j < kFhmFloats; ++j) a.v[j] = seq_add(first, a.v[j], r.v[j]);
         ++a.n_hit;
     }
     return a;
@@ -157,7 +154,7 @@ WT_HD void fhm_write(const fhm_sums_t& a, const fhm_query_t& q, float* m, uint32
     for (uint32_t i = 0; i < kFhmMaps; ++i)
 #pragma unroll
         for (uint32_t j = 0; j < kFhmMaxK; ++j)
-            if (((q.maps >> i) & 1u) && j < q.n_k) *m++ = fhm_mean(a.v[i * kFhmMaxK + j], a.n_hit);   // (the slots come in this order)
+            if (((q.maps >> i) & 1u) && j < q.n_k) *m++ = fh_hit_mean(a.v[i * kFhmMaxK + j], a.n_hit);   // (the slots come in this order)
     if (q.ids & FHM_MATERIAL) *id++ = a.material;
     if (q.ids & FHM_TYPE) *id++ = a.type;
 }

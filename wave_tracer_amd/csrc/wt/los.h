@@ -2,7 +2,7 @@
 // or a caller's point, can see.  The points of a virtual-plane sensor are those of its own sampling (wt/sources.h: vplane_element_point), the
 // visibility test is the integrators' (wt/bvh.h: ads_shadow_ray): nothing is restated here.  f32 + - x /, comparisons and sqrtf only (no libm
 // call: spot_falloff's acosf is deliberately not part of this), so the device kernels and the host twin, which run los_point, los_sample,
-// los_add, los_mean and los_nearest_step, agree bit for bit.
+// seq_add, los_mean and los_nearest_step, agree bit for bit.
 #pragma once
 #include "bvh.h"
 #include "sources.h"
@@ -119,9 +119,7 @@ WT_HD los_sample_t los_sample(const scene_t& sc, const los_query_t& q, const los
     return r;
 }
 
-// one more term of a sequential f32 sum, first term first (fh_add's rule)
-WT_HD float los_add(bool first, float sum, float x) { return first ? x : sum + x; }
-// float j of a pair from its sum over ALL samples: the visible share, or the mean; the same division serves the mean point
+// float j of a pair from its sum (wt/core.h: seq_add) over ALL samples: the visible share, or the mean; the same division serves the mean point
 WT_HD float los_mean(float sum, uint32_t samples) { return sum / float(samples ? samples : 1u); }
 WT_HD float los_visible(uint32_t n_visible, uint32_t samples) { return float(n_visible) / float(samples ? samples : 1u); }
 
@@ -140,10 +138,10 @@ WT_HD los_sums_t los_pair(const scene_t& sc, const los_query_t& q, uint32_t px, 
         const los_point_t pt = los_point(sc, q, px, py, s);
         const los_sample_t r = los_sample(sc, q, pt, e, stack);
         a.n_visible += r.visible ? 1u : 0u;
-        a.v[1] = los_add(s == 0, a.v[1], r.v[1]);
+        a.v[1] = seq_add(s == 0, a.v[1], r.v[1]);
         if (vectors) {
 #pragma unroll
-            for (uint32_t j = 2; j < kLosFloats; ++j) a.v[j] = los_add(s == 0, a.v[j], r.v[j]);
+            for (uint32_t j = 2; j < kLosFloats; ++j) a.v[j] = seq_add(s == 0, a.v[j], r.v[j]);
         }
     }
     return a;
@@ -160,7 +158,7 @@ WT_HD vec3 los_point_sum(const scene_t& sc, const los_query_t& q, uint32_t px, u
     const uint32_t n = q.samples ? q.samples : 1u;
     for (uint32_t s = 0; s < n; ++s) {
         const los_point_t pt = los_point(sc, q, px, py, s);
-        sum = vec3{los_add(s == 0, sum.x, pt.p.x), los_add(s == 0, sum.y, pt.p.y), los_add(s == 0, sum.z, pt.p.z)};
+        sum = vec3{seq_add(s == 0, sum.x, pt.p.x), seq_add(s == 0, sum.y, pt.p.y), seq_add(s == 0, sum.z, pt.p.z)};
     }
     return sum;
 }

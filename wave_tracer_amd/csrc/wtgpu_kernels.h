@@ -14,6 +14,8 @@
 //   kernels_firsthit.hip k_first_hit / k_first_hit_wave: first-hit maps of a perspective sensor — depth, position, normals, uv, ids (not part of a render)
 //   kernels_firsthit_material.hip k_first_hit_material / k_first_hit_material_wave: first-hit material maps — albedo, specular reflectance, opacity, roughness, emission, material ids (not part of a render)
 //   kernels_los.hip     k_los_sample / k_los_pair: line-of-sight maps — which emitters a sensor element or a caller's point sees (not part of a render)
+//   kernels_maps.h      what the last four share on the device and in their host twins: the two lane shapes (one lane per element, one lane per sample) with
+//                       their grids, a group's share of a ballot, the exchange through the LDS of the stacks and its sums in sample order, the host twins' loop
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
 //   kernels_compare.hip k_film_compare (+ k_film_finish): difference statistics of two films (not part of a render)

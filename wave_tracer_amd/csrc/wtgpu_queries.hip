@@ -7,6 +7,46 @@
 #include "wt/los.h"
 #include "wt/sources_probe.h"
 
+// ---- what the entries of the sensor-element maps (mask, first hit, first-hit material, line of sight) share ----------------------------------
+// One group of bits of a map spec with the caller's array for it (out_name NULL: flags, which select no output).
+struct spec_group_t {
+    uint32_t bits, known;
+    const char* unknown;   // "map bits (1 COVERAGE .. 64 FACING)"
+    const void* out;
+    const char *requested, *out_name;   // "maps", "maps"
+};
+// The checks the specs share, in this order: no unknown bit in any group, something requested (none: "no map and no id bit"), and an array for
+// every group that is.  who: the feature's name in the messages.
+static int check_groups(const std::string& who, const char* none, std::initializer_list<spec_group_t> groups) {
+    bool any = false;
+    for (const spec_group_t& g : groups) {
+        if (g.bits & ~g.known) return fail(WTGPU_ERR_INVALID, who + ": unknown " + g.unknown);
+        any = any || (g.out_name && g.bits);
+    }
+    if (!any) return fail(WTGPU_ERR_INVALID, who + ": nothing requested (" + none + ")");
+    for (const spec_group_t& g : groups)
+        if (g.out_name && g.bits && !g.out) return fail(WTGPU_ERR_INVALID, who + ": " + g.requested + " requested, but the " + g.out_name + " pointer is NULL");
+    return WTGPU_OK;
+}
+// The tail of a device entry: body() runs with the uploaded scene's device current; launch_rc() turns what a launcher returns into the entry's code.
+template <class F>
+static int on_scene_device(wtgpu_scene* s, F&& body) {
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
+    device_guard_t guard(s->device);
+    return body();
+}
+static int launch_rc(const char* kernel, int e) { return e ? fail(WTGPU_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString((hipError_t)e)) : WTGPU_OK; }
+// The tail of a host entry: the twin's exceptions (a thread that cannot start, an allocation) become the entry's code.
+template <class F>
+static int on_host(F&& twin) {
+    try {
+        twin();
+    } catch (const std::exception& e) {
+        return fail(WTGPU_ERR_INVALID, e.what());
+    }
+    return WTGPU_OK;
+}
+
 extern "C" {
 
 int wtgpu_trace_rays(wtgpu_scene* s, void* stream_, const float* d_rays, uint32_t n, float* d_dist, uint32_t* d_tuid, float* d_bary, uint32_t* d_front) {
@@ -75,35 +115,29 @@ int wtgpu_sensor_mask(wtgpu_scene* s, void* stream_, const uint8_t* shape_flags,
     if (!s || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
     const uint8_t* flags = nullptr;
     if (const int rc = mask_flags_for(s, shape_flags, samples, &flags)) return rc;
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    device_guard_t guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const size_t n = std::max<size_t>(1, s->host.n_shapes);
-    if (!s->ev_mask) {
-        uint8_t* d = nullptr;
-        if (const int rc = dmalloc(s, &d, n)) return rc;
-        HIP_CHECK(hipHostMalloc((void**)&s->h_mask_flags, n, hipHostMallocDefault));
-        HIP_CHECK(hipEventCreateWithFlags(&s->ev_mask, hipEventDisableTiming));
-        s->d_mask_flags = d;
-    } else
-        HIP_CHECK(hipEventSynchronize(s->ev_mask));   // the previous call's kernel has read the buffers
-    if (s->host.n_shapes) std::memcpy(s->h_mask_flags, flags, s->host.n_shapes);
-    HIP_CHECK(hipMemcpyAsync(s->d_mask_flags, s->h_mask_flags, n, hipMemcpyHostToDevice, stream));
-    const int e = sensor_mask_launch(s->dev, stream, s->d_mask_flags, samples, seed, d_out);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_sensor_mask: ") + hipGetErrorString((hipError_t)e));
-    HIP_CHECK(hipEventRecord(s->ev_mask, stream));
-    return WTGPU_OK;
+    return on_scene_device(s, [&]() -> int {
+        hipStream_t stream = static_cast<hipStream_t>(stream_);
+        const size_t n = std::max<size_t>(1, s->host.n_shapes);
+        if (!s->ev_mask) {
+            uint8_t* d = nullptr;
+            if (const int rc = dmalloc(s, &d, n)) return rc;
+            HIP_CHECK(hipHostMalloc((void**)&s->h_mask_flags, n, hipHostMallocDefault));
+            HIP_CHECK(hipEventCreateWithFlags(&s->ev_mask, hipEventDisableTiming));
+            s->d_mask_flags = d;
+        } else
+            HIP_CHECK(hipEventSynchronize(s->ev_mask));   // the previous call's kernel has read the buffers
+        if (s->host.n_shapes) std::memcpy(s->h_mask_flags, flags, s->host.n_shapes);
+        HIP_CHECK(hipMemcpyAsync(s->d_mask_flags, s->h_mask_flags, n, hipMemcpyHostToDevice, stream));
+        if (const int rc = launch_rc("k_sensor_mask", sensor_mask_launch(s->dev, stream, s->d_mask_flags, samples, seed, d_out))) return rc;
+        HIP_CHECK(hipEventRecord(s->ev_mask, stream));
+        return WTGPU_OK;
+    });
 }
 int wtgpu_sensor_mask_host(const wtgpu_scene* s, const uint8_t* shape_flags, uint32_t samples, uint64_t seed, uint32_t n_threads, float* out) {
     if (!s || !out) return fail(WTGPU_ERR_INVALID, "null argument");
     const uint8_t* flags = nullptr;
     if (const int rc = mask_flags_for(s, shape_flags, samples, &flags)) return rc;
-    try {
-        sensor_mask_host(s->host, flags, samples, seed, n_threads, out);
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
+    return on_host([&] { sensor_mask_host(s->host, flags, samples, seed, n_threads, out); });
 }
 
 // ---- first-hit maps (wt/first_hit.h, kernels_firsthit.hip) ---------------------------------------------------------------------------------
@@ -112,31 +146,20 @@ static int first_hit_check(const wtgpu_scene* s, const wtgpu_first_hit_spec* spe
     if (!s || !spec) return fail(WTGPU_ERR_INVALID, "null argument");
     if (s->host.sensor.type != SENSOR_PERSPECTIVE)
         return fail(WTGPU_ERR_INVALID, "first-hit maps need a perspective sensor (a virtual-plane sensor has no primary ray through a pixel)");
-    if (spec->maps & ~(uint32_t)FH_ALL_MAPS) return fail(WTGPU_ERR_INVALID, "first-hit maps: unknown map bits (1 COVERAGE .. 64 FACING)");
-    if (spec->ids & ~(uint32_t)FH_ALL_IDS) return fail(WTGPU_ERR_INVALID, "first-hit maps: unknown id bits (1 SHAPE, 2 TRIANGLE)");
     if (spec->samples > kFhMaxSamples) return fail(WTGPU_ERR_INVALID, "first-hit maps: 0 .. 4096 samples per pixel expected");
-    if (!spec->maps && !spec->ids) return fail(WTGPU_ERR_INVALID, "first-hit maps: nothing requested (no map and no id bit)");
-    if (spec->maps && !maps) return fail(WTGPU_ERR_INVALID, "first-hit maps: maps requested, but the maps pointer is NULL");
-    if (spec->ids && !ids) return fail(WTGPU_ERR_INVALID, "first-hit maps: ids requested, but the ids pointer is NULL");
-    return WTGPU_OK;
+    return check_groups("first-hit maps", "no map and no id bit", {{spec->maps, FH_ALL_MAPS, "map bits (1 COVERAGE .. 64 FACING)", maps, "maps", "maps"},
+                                                                  {spec->ids, FH_ALL_IDS, "id bits (1 SHAPE, 2 TRIANGLE)", ids, "ids", "ids"}});
 }
 int wtgpu_first_hit(wtgpu_scene* s, void* stream, const wtgpu_first_hit_spec* spec, float* d_maps, uint32_t* d_ids) {
     if (const int rc = first_hit_check(s, spec, d_maps, d_ids)) return rc;
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    device_guard_t guard(s->device);
-    const int e = first_hit_launch(s->dev, static_cast<hipStream_t>(stream), spec->samples, spec->seed, spec->maps, spec->ids,
-                                   s->knobs.first_hit_per_sample, d_maps, d_ids);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_first_hit: ") + hipGetErrorString((hipError_t)e));
-    return WTGPU_OK;
+    return on_scene_device(s, [&] {
+        return launch_rc("k_first_hit", first_hit_launch(s->dev, static_cast<hipStream_t>(stream), spec->samples, spec->seed, spec->maps, spec->ids,
+                                                        s->knobs.first_hit_per_sample, d_maps, d_ids));
+    });
 }
 int wtgpu_first_hit_host(const wtgpu_scene* s, const wtgpu_first_hit_spec* spec, uint32_t n_threads, float* maps, uint32_t* ids) {
     if (const int rc = first_hit_check(s, spec, maps, ids)) return rc;
-    try {
-        first_hit_host(s->host, spec->samples, spec->seed, spec->maps, spec->ids, n_threads, maps, ids);
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
+    return on_host([&] { first_hit_host(s->host, spec->samples, spec->seed, spec->maps, spec->ids, n_threads, maps, ids); });
 }
 
 // ---- first-hit material maps (wt/first_hit_material.h, kernels_firsthit_material.hip) ------------------------------------------------------
@@ -145,16 +168,15 @@ static int first_hit_material_check(const wtgpu_scene* s, const wtgpu_first_hit_
     if (!s || !spec) return fail(WTGPU_ERR_INVALID, "null argument");
     if (s->host.sensor.type != SENSOR_PERSPECTIVE)
         return fail(WTGPU_ERR_INVALID, "first-hit material maps need a perspective sensor (a virtual-plane sensor has no primary ray through a pixel)");
-    if (spec->maps & ~(uint32_t)FHM_ALL_MAPS) return fail(WTGPU_ERR_INVALID, "first-hit material maps: unknown map bits (1 ALBEDO .. 16 EMISSION)");
-    if (spec->ids & ~(uint32_t)FHM_ALL_IDS) return fail(WTGPU_ERR_INVALID, "first-hit material maps: unknown id bits (1 MATERIAL, 2 TYPE)");
     if (spec->n_k < 1 || spec->n_k > kFhmMaxK) return fail(WTGPU_ERR_INVALID, "first-hit material maps: 1 .. 4 wavenumbers expected (n_k)");
     for (uint32_t j = 0; j < spec->n_k; ++j)
         if (!finitef(spec->k[j]) || !(spec->k[j] > 0.f))
             return fail(WTGPU_ERR_INVALID, "first-hit material maps: wavenumber " + std::to_string(j) + " is not finite and > 0 (k in 1/mm)");
     if (spec->samples > kFhMaxSamples) return fail(WTGPU_ERR_INVALID, "first-hit material maps: 0 .. 4096 samples per pixel expected");
-    if (!spec->maps && !spec->ids) return fail(WTGPU_ERR_INVALID, "first-hit material maps: nothing requested (no map and no id bit)");
-    if (spec->maps && !maps) return fail(WTGPU_ERR_INVALID, "first-hit material maps: maps requested, but the maps pointer is NULL");
-    if (spec->ids && !ids) return fail(WTGPU_ERR_INVALID, "first-hit material maps: ids requested, but the ids pointer is NULL");
+    if (const int rc = check_groups("first-hit material maps", "no map and no id bit",
+                                    {{spec->maps, FHM_ALL_MAPS, "map bits (1 ALBEDO .. 16 EMISSION)", maps, "maps", "maps"},
+                                     {spec->ids, FHM_ALL_IDS, "id bits (1 MATERIAL, 2 TYPE)", ids, "ids", "ids"}}))
+        return rc;
     q.samples = spec->samples, q.maps = spec->maps, q.ids = spec->ids, q.n_k = spec->n_k, q.seed = spec->seed;
     for (uint32_t j = 0; j < kFhmMaxK; ++j) q.k[j] = j < spec->n_k ? spec->k[j] : 0.f;
     return WTGPU_OK;
@@ -162,21 +184,14 @@ static int first_hit_material_check(const wtgpu_scene* s, const wtgpu_first_hit_
 int wtgpu_first_hit_material(wtgpu_scene* s, void* stream, const wtgpu_first_hit_material_spec* spec, float* d_maps, uint32_t* d_ids) {
     fhm_query_t q;
     if (const int rc = first_hit_material_check(s, spec, d_maps, d_ids, q)) return rc;
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    device_guard_t guard(s->device);
-    const int e = first_hit_material_launch(s->dev, static_cast<hipStream_t>(stream), q, s->knobs.first_hit_per_sample, d_maps, d_ids);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_first_hit_material: ") + hipGetErrorString((hipError_t)e));
-    return WTGPU_OK;
+    return on_scene_device(s, [&] {
+        return launch_rc("k_first_hit_material", first_hit_material_launch(s->dev, static_cast<hipStream_t>(stream), q, s->knobs.first_hit_per_sample, d_maps, d_ids));
+    });
 }
 int wtgpu_first_hit_material_host(const wtgpu_scene* s, const wtgpu_first_hit_material_spec* spec, uint32_t n_threads, float* maps, uint32_t* ids) {
     fhm_query_t q;
     if (const int rc = first_hit_material_check(s, spec, maps, ids, q)) return rc;
-    try {
-        first_hit_material_host(s->host, q, n_threads, maps, ids);
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
+    return on_host([&] { first_hit_material_host(s->host, q, n_threads, maps, ids); });
 }
 // One wavenumber per spectral channel of the sensor: the line of a discrete response, the response-weighted mean over the knots of a table.
 int wtgpu_scene_channel_wavenumbers(const wtgpu_scene* s, float k[4]) {
@@ -215,14 +230,12 @@ static int los_check(const wtgpu_scene* s, const wtgpu_los_spec* spec, const flo
         return fail(WTGPU_ERR_INVALID, "line of sight: without points the elements of a virtual-plane sensor are meant, and this sensor is not one (pass points, for example the POSITION map of wtgpu_first_hit)");
     if (points && spec->samples != 0) return fail(WTGPU_ERR_INVALID, "line of sight: caller points take samples = 0 (a point is not sampled)");
     if (spec->samples > kLosMaxSamples) return fail(WTGPU_ERR_INVALID, "line of sight: 0 .. 4096 samples per element expected");
-    if (spec->maps & ~(uint32_t)LOS_ALL_MAPS) return fail(WTGPU_ERR_INVALID, "line of sight: unknown map bits (1 VISIBLE, 2 DISTANCE, 4 DIRECTION, 8 COS)");
-    if (spec->elem & ~(uint32_t)LOS_ALL_ELEM) return fail(WTGPU_ERR_INVALID, "line of sight: unknown element bits (1 POINT, 2 NEAREST_DISTANCE)");
-    if (spec->ids & ~(uint32_t)LOS_ALL_IDS) return fail(WTGPU_ERR_INVALID, "line of sight: unknown id bits (1 N_VISIBLE, 2 NEAREST)");
-    if (spec->flags & ~(uint32_t)LOS_ALL_FLAGS) return fail(WTGPU_ERR_INVALID, "line of sight: unknown flag bits (1 FRONT_ONLY)");
-    if (!spec->maps && !spec->elem && !spec->ids) return fail(WTGPU_ERR_INVALID, "line of sight: nothing requested (no map, no element and no id bit)");
-    if (spec->maps && !maps) return fail(WTGPU_ERR_INVALID, "line of sight: maps requested, but the maps pointer is NULL");
-    if (spec->elem && !elem) return fail(WTGPU_ERR_INVALID, "line of sight: element floats requested, but the elem pointer is NULL");
-    if (spec->ids && !ids) return fail(WTGPU_ERR_INVALID, "line of sight: ids requested, but the ids pointer is NULL");
+    if (const int rc = check_groups("line of sight", "no map, no element and no id bit",
+                                    {{spec->maps, LOS_ALL_MAPS, "map bits (1 VISIBLE, 2 DISTANCE, 4 DIRECTION, 8 COS)", maps, "maps", "maps"},
+                                     {spec->elem, LOS_ALL_ELEM, "element bits (1 POINT, 2 NEAREST_DISTANCE)", elem, "element floats", "elem"},
+                                     {spec->ids, LOS_ALL_IDS, "id bits (1 N_VISIBLE, 2 NEAREST)", ids, "ids", "ids"},
+                                     {spec->flags, LOS_ALL_FLAGS, "flag bits (1 FRONT_ONLY)", nullptr, nullptr, nullptr}}))
+        return rc;
     const bool has_normal = !points || normals;
     if ((spec->maps & LOS_COS) && !has_normal) return fail(WTGPU_ERR_INVALID, "line of sight: COS needs a normal (caller points without normals)");
     if ((spec->flags & LOS_FRONT_ONLY) && !has_normal) return fail(WTGPU_ERR_INVALID, "line of sight: FRONT_ONLY needs a normal (caller points without normals)");
@@ -255,22 +268,13 @@ int wtgpu_line_of_sight(wtgpu_scene* s, void* stream, const wtgpu_los_spec* spec
                         float* d_maps, float* d_elem, uint32_t* d_ids) {
     los_query_t q;
     if (const int rc = los_check(s, spec, d_points, d_normals, d_mask, d_maps, d_elem, d_ids, q)) return rc;
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    device_guard_t guard(s->device);
-    const int e = los_launch(s->dev, static_cast<hipStream_t>(stream), q, s->knobs.los_per_sample, d_maps, d_elem, d_ids);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_los: ") + hipGetErrorString((hipError_t)e));
-    return WTGPU_OK;
+    return on_scene_device(s, [&] { return launch_rc("k_los", los_launch(s->dev, static_cast<hipStream_t>(stream), q, s->knobs.los_per_sample, d_maps, d_elem, d_ids)); });
 }
 int wtgpu_line_of_sight_host(const wtgpu_scene* s, const wtgpu_los_spec* spec, const float* points, const float* normals, const float* mask,
                              uint32_t n_threads, float* maps, float* elem, uint32_t* ids) {
     los_query_t q;
     if (const int rc = los_check(s, spec, points, normals, mask, maps, elem, ids, q)) return rc;
-    try {
-        los_host(s->host, q, n_threads, maps, elem, ids);
-    } catch (const std::exception& e) {
-        return fail(WTGPU_ERR_INVALID, e.what());
-    }
-    return WTGPU_OK;
+    return on_host([&] { los_host(s->host, q, n_threads, maps, elem, ids); });
 }
 
 int wtgpu_test_fsd_apertures(wtgpu_scene* s, void* stream, const float* d_cones, const float* d_sk, const uint32_t* d_ids, const uint32_t* d_n_ids,
