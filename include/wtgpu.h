@@ -531,6 +531,41 @@ int wtgpu_film_polar_device(wtgpu_scene* scene, void* stream, const double* d_va
 int wtgpu_film_polar_host(const wtgpu_scene* scene, const double* value, const double* weight, const double* light, uint64_t spe,
                           const wtgpu_film_polar_spec* spec, const float* mask, uint32_t n_threads, wtgpu_film_polar* out, float* maps, void* picture);
 
+/* The four film passes above on either kind of film: the accumulators, or a DEVELOPED film — what wtgpu_develop_device and the denoisers
+ * (wtgpu_film_denoise_device, its guided form; the filtered film and the residual) write, so that a denoised film is shown, measured and compared
+ * where it lies.  A source is exactly one of the two forms:
+ *   value, weight, light + spe   the accumulators as wtgpu_render fills them; an element is wtgpu_develop's value of them;
+ *   developed                    [height][width][channels][stokes] f32; an element is the f32 as it lies there — any f32: NaNs of any payload,
+ *                                infinities, -0 and subnormals are what each pass's rules above say they are.  spe is not read.  No alignment
+ *                                beyond a float's is asked of the pointer.
+ * Both forms set, neither, or a partly set accumulator triple: WTGPU_ERR_INVALID with a message.  Everything behind the element value — planes,
+ * luminance, ABS, classes, the sums' fixed order, extrema, records, maps, operator, mode, table, quantisation, mask — is the same code, so a pass
+ * on wtgpu_develop's output of a set of accumulators gives what it gives on the accumulators, bit for bit.  The remaining arguments, the errors
+ * and their messages are the sibling's; the *_device forms take DEVICE memory in the sources, the *_host forms HOST memory.  The comparison takes
+ * two sources in any combination (a denoised film against a long render's accumulators; the same memory twice is fine).  The entry points above
+ * are these with accumulator sources. */
+typedef struct wtgpu_film_source {
+    const double *value, *weight, *light;   /* the accumulators, with spe ... */
+    uint64_t spe;
+    const float* developed;                 /* ... or a developed film */
+} wtgpu_film_source;
+int wtgpu_tonemap_source_device(wtgpu_scene* scene, void* stream, const wtgpu_film_source* film, const wtgpu_tonemap* tm, uint32_t stokes_component,
+                                const float* d_mask, uint32_t format, void* d_out);
+int wtgpu_tonemap_source_host(const wtgpu_scene* scene, const wtgpu_film_source* film, const wtgpu_tonemap* tm, uint32_t stokes_component, const float* mask,
+                              uint32_t format, uint32_t n_threads, void* out);
+int wtgpu_film_stats_source_device(wtgpu_scene* scene, void* stream, const wtgpu_film_source* film, const wtgpu_film_stats_spec* spec, const float* d_mask,
+                                   wtgpu_film_stats* out, uint64_t* hist);
+int wtgpu_film_stats_source_host(const wtgpu_scene* scene, const wtgpu_film_source* film, const wtgpu_film_stats_spec* spec, const float* mask, uint32_t n_threads,
+                                 wtgpu_film_stats* out, uint64_t* hist);
+int wtgpu_film_compare_source_device(wtgpu_scene* scene, void* stream, const wtgpu_film_source* a, const wtgpu_film_source* b, const wtgpu_film_compare_spec* spec,
+                                     const float* d_mask, wtgpu_film_compare* out, float* d_diff);
+int wtgpu_film_compare_source_host(const wtgpu_scene* scene, const wtgpu_film_source* a, const wtgpu_film_source* b, const wtgpu_film_compare_spec* spec,
+                                   const float* mask, uint32_t n_threads, wtgpu_film_compare* out, float* diff);
+int wtgpu_film_polar_source_device(wtgpu_scene* scene, void* stream, const wtgpu_film_source* film, const wtgpu_film_polar_spec* spec, const float* d_mask,
+                                   wtgpu_film_polar* out, float* d_maps, void* d_picture);
+int wtgpu_film_polar_source_host(const wtgpu_scene* scene, const wtgpu_film_source* film, const wtgpu_film_polar_spec* spec, const float* mask, uint32_t n_threads,
+                                 wtgpu_film_polar* out, float* maps, void* picture);
+
 /* Denoising a film from its two half-films A and B (two renders of disjoint sample ranges, as render_to_noise keeps them) without the films leaving
  * the device: the dual-buffer non-local-means filter of Rousselle, Knaus and Zwicker 2012 — the weights that filter one half are computed from the
  * other, the per-pixel variance comes from (a - b)^2, and the difference of the two filtered halves estimates the error that is left.

@@ -60,6 +60,10 @@ class Tonemap(C.Structure):          # wtgpu_tonemap
                 ("table", C.POINTER(C.c_float)), ("table_n", C.c_uint32)]
 
 
+class FilmSource(C.Structure):       # wtgpu_film_source: the accumulators with spe, or a developed f32 film
+    _fields_ = [("value", C.c_void_p), ("weight", C.c_void_p), ("light", C.c_void_p), ("spe", C.c_uint64), ("developed", C.c_void_p)]
+
+
 class FilmStatsSpec(C.Structure):    # wtgpu_film_stats_spec
     _fields_ = [("stokes_component", C.c_uint32), ("scale", C.c_uint32), ("bins", C.c_uint32), ("flags", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float)]
 
@@ -161,6 +165,8 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_scene_tonemap_spec", "wtgpu_develop_device", "wtgpu_tonemap_device", "wtgpu_tonemap_host",
            "wtgpu_film_stats_edges", "wtgpu_film_stats_device", "wtgpu_film_stats_host",
            "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host",
+           "wtgpu_tonemap_source_device", "wtgpu_tonemap_source_host", "wtgpu_film_stats_source_device", "wtgpu_film_stats_source_host",
+           "wtgpu_film_compare_source_device", "wtgpu_film_compare_source_host", "wtgpu_film_polar_source_device", "wtgpu_film_polar_source_host",
            "wtgpu_film_denoise_device", "wtgpu_film_denoise_host",
            "wtgpu_film_denoise_guided_device", "wtgpu_film_denoise_guided_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
@@ -266,6 +272,15 @@ def load_library():
     lib.wtgpu_film_compare_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmCompareSpec), vp, u32, vp, vp]
     lib.wtgpu_film_polar_device.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(FilmPolarSpec), vp, vp, vp, vp]
     lib.wtgpu_film_polar_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(FilmPolarSpec), vp, u32, vp, vp, vp]
+    src = C.POINTER(FilmSource)
+    lib.wtgpu_tonemap_source_device.argtypes = [vp, vp, src, C.POINTER(Tonemap), u32, vp, u32, vp]
+    lib.wtgpu_tonemap_source_host.argtypes = [vp, src, C.POINTER(Tonemap), u32, vp, u32, u32, vp]
+    lib.wtgpu_film_stats_source_device.argtypes = [vp, vp, src, C.POINTER(FilmStatsSpec), vp, vp, vp]
+    lib.wtgpu_film_stats_source_host.argtypes = [vp, src, C.POINTER(FilmStatsSpec), vp, u32, vp, vp]
+    lib.wtgpu_film_compare_source_device.argtypes = [vp, vp, src, src, C.POINTER(FilmCompareSpec), vp, vp, vp]
+    lib.wtgpu_film_compare_source_host.argtypes = [vp, src, src, C.POINTER(FilmCompareSpec), vp, u32, vp, vp]
+    lib.wtgpu_film_polar_source_device.argtypes = [vp, vp, src, C.POINTER(FilmPolarSpec), vp, vp, vp, vp]
+    lib.wtgpu_film_polar_source_host.argtypes = [vp, src, C.POINTER(FilmPolarSpec), vp, u32, vp, vp, vp]
     lib.wtgpu_film_denoise_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmDenoiseSpec), vp, vp, vp]
     lib.wtgpu_film_denoise_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmDenoiseSpec), vp, u32, vp, vp]
     lib.wtgpu_film_denoise_guided_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(FilmDenoiseSpec), C.POINTER(FilmDenoiseGuides), vp, vp, vp, vp, vp]
@@ -864,6 +879,42 @@ class Scene:
                 raise ValueError(f"{what}: {name}: a contiguous {dtype} tensor of {numel} elements on cuda:{self.device} expected")
         return torch.device("cuda", self.device)
 
+    # ---- a film source (wtgpu_film_source): the accumulators (value, weight, light) with spe, or ONE developed f32 film ----
+    def _device_source(self, what, films, spe, mask=None):
+        """films: the (value, weight, light) f64 tensors with spe, or one developed f32 tensor of the scene's planes (develop_device's, the
+        denoiser's "film" or "residual") -> (FilmSource, torch device).  A film of another dtype, size, device or layout is refused here."""
+        import torch
+        if isinstance(films, (tuple, list)):
+            value, weight, light = films
+            dev = self._device_films(what, value, weight, light, mask)
+            return FilmSource(value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe), None), dev
+        if self.device is None:
+            raise WtgpuError(f"{what}: upload(device) first")
+        n = self.width * self.height
+        if not (isinstance(films, torch.Tensor) and films.is_cuda and films.device.index == self.device and films.dtype == torch.float32
+                and films.numel() == n * self.channels and films.is_contiguous()):
+            raise ValueError(f"{what}: film: a contiguous torch.float32 tensor [{self.height}, {self.width}, {self.spectral_channels}, {self.stokes}] "
+                             f"({n * self.channels} elements) on cuda:{self.device} expected")
+        if mask is not None and not (mask.is_cuda and mask.device.index == self.device and mask.dtype == torch.float32 and mask.numel() == n and mask.is_contiguous()):
+            raise ValueError(f"{what}: mask: a contiguous torch.float32 tensor of {n} elements on cuda:{self.device} expected")
+        return FilmSource(None, None, None, 0, films.data_ptr()), torch.device("cuda", self.device)
+
+    def _host_source(self, what, films, spe, mask=None):
+        """_device_source's numpy mirror for the host twins -> (FilmSource, the f32 mask or None, the arrays the pointers live in).  A developed film
+        is taken as it is — a contiguous float32 array of the scene's planes — never converted: its bits are the input."""
+        import numpy as np
+        if isinstance(films, (tuple, list)):
+            v, w, l, m = self._host_films(what, *films, mask)
+            return FilmSource(v.ctypes.data, w.ctypes.data, l.ctypes.data, int(spe), None), m, (v, w, l, m)
+        n = self.width * self.height
+        if not (isinstance(films, np.ndarray) and films.dtype == np.float32 and films.size == n * self.channels and films.flags.c_contiguous):
+            raise ValueError(f"{what}: film: a contiguous float32 array [{self.height}, {self.width}, {self.spectral_channels}, {self.stokes}] "
+                             f"({n * self.channels} elements) expected")
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+        if m is not None and m.size != n:
+            raise ValueError(f"{what}: a mask of the scene's size expected")
+        return FilmSource(None, None, None, 0, films.ctypes.data), m, (films, m)
+
     def develop_device(self, value, weight, light, spe, stream=None):
         """wtgpu_develop on the scene's device (wtgpu_develop_device): value / weight / light are the torch f64 films there; returns the developed
         film as a torch f32 tensor shaped like `value`, bit for bit render.develop's.  Enqueued on `stream` (default: torch's current)."""
@@ -874,33 +925,48 @@ class Scene:
                                                    out.data_ptr()))
         return out
 
+    def _tonemap_device(self, what, films, spe, tm, stokes_component, mask, fmt, stream):
+        import torch
+        src, dev = self._device_source(what, films, spe, mask)
+        st_tm, keep = self._tonemap_struct(tm)
+        dtype = {"f32": torch.float32, "u8": torch.uint8, "u16": torch.int16}[fmt]
+        out = torch.empty((self.height, self.width, 4 if mask is not None else 3), dtype=dtype, device=dev)
+        _check(load_library().wtgpu_tonemap_source_device(self._h, self._stream_arg(stream, dev), C.byref(src), None if st_tm is None else C.byref(st_tm),
+                                                          int(stokes_component), None if mask is None else mask.data_ptr(), TONEMAP_FORMATS[fmt], out.data_ptr()))
+        del keep
+        return out
+
+    def _tonemap_host(self, what, films, spe, tm, stokes_component, mask, fmt, threads):
+        import numpy as np
+        src, m, keep_films = self._host_source(what, films, spe, mask)
+        st_tm, keep = self._tonemap_struct(tm)
+        out = np.zeros((self.height, self.width, 4 if m is not None else 3), {"f32": np.float32, "u8": np.uint8, "u16": np.uint16}[fmt])
+        _check(load_library().wtgpu_tonemap_source_host(self._h, C.byref(src), None if st_tm is None else C.byref(st_tm), int(stokes_component),
+                                                        None if m is None else m.ctypes.data, TONEMAP_FORMATS[fmt], int(threads), out.ctypes.data))
+        del keep, keep_films
+        return out
+
     def tonemap_device(self, value, weight, light, spe, tm=None, stokes_component=0, mask=None, fmt="f32", stream=None):
         """Develops and tonemaps one Stokes component of the films on the scene's device in one kernel (wtgpu_tonemap_device).  tm: None = the
         scene's own tonemap_spec, else a dict {op, mode, gamma, db_range, table} (table: [n,3] f32 colour map, imageio.colour_table).  mask: an
         H x W f32 torch tensor on the device (sensor_mask) that becomes the alpha.  fmt: f32 | u8 | u16.  Returns a torch tensor H x W x 3 (x 4
         with a mask) of float32 / uint8 / int16 (the 16-bit codes: view them as unsigned)."""
-        import torch
-        dev = self._device_films("tonemap_device", value, weight, light, mask)
-        st_tm, keep = self._tonemap_struct(tm)
-        dtype = {"f32": torch.float32, "u8": torch.uint8, "u16": torch.int16}[fmt]
-        out = torch.empty((self.height, self.width, 4 if mask is not None else 3), dtype=dtype, device=dev)
-        _check(load_library().wtgpu_tonemap_device(self._h, self._stream_arg(stream, dev), value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
-                                                   None if st_tm is None else C.byref(st_tm), int(stokes_component),
-                                                   None if mask is None else mask.data_ptr(), TONEMAP_FORMATS[fmt], out.data_ptr()))
-        del keep
-        return out
+        return self._tonemap_device("tonemap_device", (value, weight, light), spe, tm, stokes_component, mask, fmt, stream)
 
     def tonemap_host(self, value, weight, light, spe, tm=None, stokes_component=0, mask=None, fmt="f32", threads=0):
         """The same computation on host threads from numpy films (wtgpu_tonemap_host; threads 0 = all cores): a numpy array H x W x 3 (x 4 with
         a mask) of float32 / uint8 / uint16.  No device needed."""
-        import numpy as np
-        v, w, l, m = self._host_films("tonemap_host", value, weight, light, mask)
-        st_tm, keep = self._tonemap_struct(tm)
-        out = np.zeros((self.height, self.width, 4 if m is not None else 3), {"f32": np.float32, "u8": np.uint8, "u16": np.uint16}[fmt])
-        _check(load_library().wtgpu_tonemap_host(self._h, v.ctypes.data, w.ctypes.data, l.ctypes.data, int(spe), None if st_tm is None else C.byref(st_tm),
-                                                 int(stokes_component), None if m is None else m.ctypes.data, TONEMAP_FORMATS[fmt], int(threads), out.ctypes.data))
-        del keep
-        return out
+        return self._tonemap_host("tonemap_host", (value, weight, light), spe, tm, stokes_component, mask, fmt, threads)
+
+    def tonemap_developed_device(self, film, tm=None, stokes_component=0, mask=None, fmt="f32", stream=None):
+        """tonemap_device of a DEVELOPED film where it is (wtgpu_tonemap_source_device): film a torch f32 tensor [H, W, channels, stokes] on the scene's
+        device — develop_device's result, film_denoise_device's "film" or "residual".  The other arguments and the result are tonemap_device's; on
+        develop_device's output of a set of accumulators the picture is tonemap_device's of those accumulators."""
+        return self._tonemap_device("tonemap_developed_device", film, 0, tm, stokes_component, mask, fmt, stream)
+
+    def tonemap_developed_host(self, film, tm=None, stokes_component=0, mask=None, fmt="f32", threads=0):
+        """tonemap_developed_device's twin on host threads (wtgpu_tonemap_source_host): film a contiguous numpy float32 array of the scene's planes."""
+        return self._tonemap_host("tonemap_developed_host", film, 0, tm, stokes_component, mask, fmt, threads)
 
     # ---- film statistics (wtgpu_film_stats_*; csrc/wt/film_stats.h) ----
     def _film_stats(self, what, call, stokes_component, scale, range, bins, abs, luminance):
@@ -942,6 +1008,25 @@ class Scene:
         out.update(hist=hist, edges=edges, scale=scale, range=(float(spec.lo), float(spec.hi)), bins=int(spec.bins))
         return out
 
+    def _film_stats_device(self, what, films, spe, stokes_component, scale, range, bins, abs, luminance, mask, stream):
+        src, dev = self._device_source(what, films, spe, mask)
+        st = self._stream_arg(stream, dev)
+        lib = load_library()
+
+        def call(spec, rec, hist):
+            _check(lib.wtgpu_film_stats_source_device(self._h, st, C.byref(src), C.byref(spec), None if mask is None else mask.data_ptr(), C.cast(rec, C.c_void_p), hist))
+        return self._film_stats(what, call, stokes_component, scale, range, bins, abs, luminance)
+
+    def _film_stats_host(self, what, films, spe, stokes_component, scale, range, bins, abs, luminance, mask, threads):
+        src, m, keep = self._host_source(what, films, spe, mask)
+        lib = load_library()
+
+        def call(spec, rec, hist):
+            _check(lib.wtgpu_film_stats_source_host(self._h, C.byref(src), C.byref(spec), None if m is None else m.ctypes.data, int(threads), C.cast(rec, C.c_void_p), hist))
+        out = self._film_stats(what, call, stokes_component, scale, range, bins, abs, luminance)
+        del keep
+        return out
+
     def film_stats_device(self, value, weight, light, spe, *, stokes_component=0, scale="dB", range=None, bins=256, abs=False, luminance=False, mask=None,
                           stream=None):
         """Range, histogram and sum of the developed planes of one Stokes component, computed where the films are (wtgpu_film_stats_device): value /
@@ -951,26 +1036,23 @@ class Scene:
         range=None: two passes, the first without bins for the smallest positive (dB) or smallest (linear) and the largest element.
         Returns a dict of numpy arrays indexed by plane: n, n_nan, n_negative, n_zero, n_below, n_above (uint64), min, max, min_positive
         (float32), sum (float64), hist [planes, bins] uint64; and edges [bins + 1] float32, scale, range, bins.  imageio.percentiles reads it."""
-        dev = self._device_films("film_stats_device", value, weight, light, mask)
-        st = self._stream_arg(stream, dev)
-        lib = load_library()
-
-        def call(spec, rec, hist):
-            _check(lib.wtgpu_film_stats_device(self._h, st, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe),
-                                               C.byref(spec), None if mask is None else mask.data_ptr(), C.cast(rec, C.c_void_p), hist))
-        return self._film_stats("film_stats_device", call, stokes_component, scale, range, bins, abs, luminance)
+        return self._film_stats_device("film_stats_device", (value, weight, light), spe, stokes_component, scale, range, bins, abs, luminance, mask, stream)
 
     def film_stats_host(self, value, weight, light, spe, *, stokes_component=0, scale="dB", range=None, bins=256, abs=False, luminance=False, mask=None,
                         threads=0):
         """film_stats_device's twin on host threads from numpy films (wtgpu_film_stats_host; threads 0 = all cores): the same dict, every field bit
         for bit the device's.  No device needed."""
-        v, w, l, m = self._host_films("film_stats_host", value, weight, light, mask)
-        lib = load_library()
+        return self._film_stats_host("film_stats_host", (value, weight, light), spe, stokes_component, scale, range, bins, abs, luminance, mask, threads)
 
-        def call(spec, rec, hist):
-            _check(lib.wtgpu_film_stats_host(self._h, v.ctypes.data, w.ctypes.data, l.ctypes.data, int(spe), C.byref(spec), None if m is None else m.ctypes.data,
-                                             int(threads), C.cast(rec, C.c_void_p), hist))
-        return self._film_stats("film_stats_host", call, stokes_component, scale, range, bins, abs, luminance)
+    def film_stats_developed_device(self, film, *, stokes_component=0, scale="dB", range=None, bins=256, abs=False, luminance=False, mask=None, stream=None):
+        """film_stats_device of a DEVELOPED film where it is (wtgpu_film_stats_source_device): film a torch f32 tensor [H, W, channels, stokes] on the
+        scene's device (develop_device's result, film_denoise_device's "film" or "residual"); the elements are its values as they lie there.  The
+        other arguments and the dict are film_stats_device's."""
+        return self._film_stats_device("film_stats_developed_device", film, 0, stokes_component, scale, range, bins, abs, luminance, mask, stream)
+
+    def film_stats_developed_host(self, film, *, stokes_component=0, scale="dB", range=None, bins=256, abs=False, luminance=False, mask=None, threads=0):
+        """film_stats_developed_device's twin on host threads (wtgpu_film_stats_source_host): film a contiguous numpy float32 array of the scene's planes."""
+        return self._film_stats_host("film_stats_developed_host", film, 0, stokes_component, scale, range, bins, abs, luminance, mask, threads)
 
     # ---- film comparison (wtgpu_film_compare_*; csrc/wt/film_compare.h) ----
     def _film_compare(self, call, stokes_component, abs, luminance, eps):
@@ -997,28 +1079,32 @@ class Scene:
         n_differ, argmax (uint64; the row-major pixel of max_abs, 2^64 - 1 where nothing differs), max_abs, sum_abs, sum_sq, sum_a_sq, sum_b_sq, sum_rel
         (float64; over the pairs of finite values, d = xa - xb) and, derived here from the sums, rmse, mean_abs, rel_l2 = sqrt(sum_sq / sum_b_sq) and
         rel_mse = sum_rel / (n - n_nonfinite) with sum_rel's addends d d / (xb xb + eps) (NaN where there is nothing to divide by).  diff=True adds
-        "diff": xa - xb as a torch f32 tensor H x W x planes on the device, 0 where the mask excludes."""
+        "diff": xa - xb as a torch f32 tensor H x W x planes on the device, 0 where the mask excludes.
+        Either operand may instead be ONE developed film, a torch f32 tensor [H, W, channels, stokes] there (develop_device's result, the denoiser's
+        "film"): its values are compared as they lie there and its spe is not read (None will do) — a denoised film against a long render's
+        accumulators (wtgpu_film_compare_source_device)."""
         import torch
-        dev = self._device_films("film_compare_device", *films_a, mask)
-        self._device_films("film_compare_device", *films_b)
+        src_a, dev = self._device_source("film_compare_device", films_a, spe_a or 0, mask)
+        src_b, _ = self._device_source("film_compare_device", films_b, spe_b or 0)
         st = self._stream_arg(stream, dev)
         d = {}
 
         def call(spec, rec, planes):
             if diff:
                 d["diff"] = torch.empty((self.height, self.width, planes), dtype=torch.float32, device=dev)
-            _check(load_library().wtgpu_film_compare_device(self._h, st, *(t.data_ptr() for t in films_a), int(spe_a),
-                                                            *(t.data_ptr() for t in films_b), int(spe_b), C.byref(spec), None if mask is None else mask.data_ptr(),
-                                                            C.cast(rec, C.c_void_p), d["diff"].data_ptr() if diff else None))
+            _check(load_library().wtgpu_film_compare_source_device(self._h, st, C.byref(src_a), C.byref(src_b), C.byref(spec), None if mask is None else mask.data_ptr(),
+                                                                   C.cast(rec, C.c_void_p), d["diff"].data_ptr() if diff else None))
         out = self._film_compare(call, stokes_component, abs, luminance, eps)
         out.update(d)
         return out
 
     def film_compare_host(self, films_a, spe_a, films_b, spe_b, *, stokes_component=0, abs=False, luminance=False, mask=None, eps=1e-4, diff=False, threads=0):
         """film_compare_device's twin on host threads from numpy films (wtgpu_film_compare_host; threads 0 = all cores): the same dict, every field bit
-        for bit the device's, "diff" a numpy array.  No device needed."""
+        for bit the device's, "diff" a numpy array.  No device needed.  Either operand may be one developed film, a contiguous numpy float32 array of the scene's
+        planes, as film_compare_device's (wtgpu_film_compare_source_host)."""
         import numpy as np
-        sets = [self._host_films("film_compare_host", *films)[:3] for films in (films_a, films_b)]
+        src_a, _, keep_a = self._host_source("film_compare_host", films_a, spe_a or 0)
+        src_b, _, keep_b = self._host_source("film_compare_host", films_b, spe_b or 0)
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
         if m is not None and m.size != self.width * self.height:
             raise ValueError("film_compare_host: a mask of the scene's size expected")
@@ -1027,11 +1113,11 @@ class Scene:
         def call(spec, rec, planes):
             if diff:
                 d["diff"] = np.zeros((self.height, self.width, planes), dtype=np.float32)
-            _check(load_library().wtgpu_film_compare_host(self._h, *(t.ctypes.data for t in sets[0]), int(spe_a), *(t.ctypes.data for t in sets[1]), int(spe_b),
-                                                          C.byref(spec), None if m is None else m.ctypes.data, int(threads), C.cast(rec, C.c_void_p),
-                                                          d["diff"].ctypes.data if diff else None))
+            _check(load_library().wtgpu_film_compare_source_host(self._h, C.byref(src_a), C.byref(src_b), C.byref(spec), None if m is None else m.ctypes.data,
+                                                                 int(threads), C.cast(rec, C.c_void_p), d["diff"].ctypes.data if diff else None))
         out = self._film_compare(call, stokes_component, abs, luminance, eps)
         out.update(d)
+        del keep_a, keep_b
         return out
 
     # ---- the polarisation view of a Stokes film (wtgpu_film_polar_*; csrc/wt/film_polar.h) ----
@@ -1064,6 +1150,33 @@ class Scene:
         out["picture"] = got_picture
         return out
 
+    def _film_polar_device(self, what, films, spe, luminance, maps, analyser, c2s2, mask, picture, picture_plane, tm, fmt, sat_gain, stream):
+        import torch
+        src, dev = self._device_source(what, films, spe, mask)
+        st = self._stream_arg(stream, dev)
+
+        def call(spec, rec, maps_shape, picture_shape):
+            m = None if maps_shape is None else torch.empty(maps_shape, dtype=torch.float32, device=dev)
+            p = None if picture_shape is None else torch.empty(picture_shape, dtype={"f32": torch.float32, "u8": torch.uint8, "u16": torch.int16}[fmt], device=dev)
+            _check(load_library().wtgpu_film_polar_source_device(self._h, st, C.byref(src), C.byref(spec), None if mask is None else mask.data_ptr(),
+                                                                 C.cast(rec, C.c_void_p), None if m is None else m.data_ptr(), None if p is None else p.data_ptr()))
+            return m, p
+        return self._film_polar(what, call, luminance, maps, analyser, c2s2, picture, picture_plane, tm, fmt, sat_gain, mask is not None)
+
+    def _film_polar_host(self, what, films, spe, luminance, maps, analyser, c2s2, mask, picture, picture_plane, tm, fmt, sat_gain, threads):
+        import numpy as np
+        src, m, keep = self._host_source(what, films, spe, mask)
+
+        def call(spec, rec, maps_shape, picture_shape):
+            mp = None if maps_shape is None else np.zeros(maps_shape, dtype=np.float32)
+            p = None if picture_shape is None else np.zeros(picture_shape, dtype={"f32": np.float32, "u8": np.uint8, "u16": np.uint16}[fmt])
+            _check(load_library().wtgpu_film_polar_source_host(self._h, C.byref(src), C.byref(spec), None if m is None else m.ctypes.data, int(threads),
+                                                               C.cast(rec, C.c_void_p), None if mp is None else mp.ctypes.data, None if p is None else p.ctypes.data))
+            return mp, p
+        out = self._film_polar(what, call, luminance, maps, analyser, c2s2, picture, picture_plane, tm, fmt, sat_gain, m is not None)
+        del keep
+        return out
+
     def film_polar_device(self, value, weight, light, spe, *, luminance=False, maps=(), analyser=0.0, c2s2=None, mask=None, picture=False, picture_plane=0, tm=None,
                           fmt="f32", sat_gain=1.0, stream=None):
         """The polarisation view of a polarimetric film where it is (wtgpu_film_polar_device): value / weight / light are the torch f64 films on the
@@ -1076,34 +1189,25 @@ class Scene:
         analyser: the analyser's angle theta in radians (c2s2 = (cos 2 theta, sin 2 theta) overrides it).  picture=True adds "picture": the false-colour
         view of plane picture_plane (hue: the angle of linear polarisation, saturation: dolp x sat_gain, value: the intensity through the operator of
         tm = {op, gamma, db_range}), a torch tensor H x W x 3 (x 4 with a mask) of float32 / uint8 / int16 as tonemap_device's."""
-        import torch
-        dev = self._device_films("film_polar_device", value, weight, light, mask)
-        st = self._stream_arg(stream, dev)
-
-        def call(spec, rec, maps_shape, picture_shape):
-            m = None if maps_shape is None else torch.empty(maps_shape, dtype=torch.float32, device=dev)
-            p = None if picture_shape is None else torch.empty(picture_shape, dtype={"f32": torch.float32, "u8": torch.uint8, "u16": torch.int16}[fmt], device=dev)
-            _check(load_library().wtgpu_film_polar_device(self._h, st, value.data_ptr(), weight.data_ptr(), light.data_ptr(), int(spe), C.byref(spec),
-                                                          None if mask is None else mask.data_ptr(), C.cast(rec, C.c_void_p),
-                                                          None if m is None else m.data_ptr(), None if p is None else p.data_ptr()))
-            return m, p
-        return self._film_polar("film_polar_device", call, luminance, maps, analyser, c2s2, picture, picture_plane, tm, fmt, sat_gain, mask is not None)
+        return self._film_polar_device("film_polar_device", (value, weight, light), spe, luminance, maps, analyser, c2s2, mask, picture, picture_plane, tm, fmt, sat_gain, stream)
 
     def film_polar_host(self, value, weight, light, spe, *, luminance=False, maps=(), analyser=0.0, c2s2=None, mask=None, picture=False, picture_plane=0, tm=None,
                         fmt="f32", sat_gain=1.0, threads=0):
         """film_polar_device's twin on host threads from numpy films (wtgpu_film_polar_host; threads 0 = all cores): the same dict, every field and every
         map bit for bit the device's, the maps and the picture numpy arrays (the picture of float32 / uint8 / uint16).  No device needed."""
-        import numpy as np
-        v, w, l, m = self._host_films("film_polar_host", value, weight, light, mask)
+        return self._film_polar_host("film_polar_host", (value, weight, light), spe, luminance, maps, analyser, c2s2, mask, picture, picture_plane, tm, fmt, sat_gain, threads)
 
-        def call(spec, rec, maps_shape, picture_shape):
-            mp = None if maps_shape is None else np.zeros(maps_shape, dtype=np.float32)
-            p = None if picture_shape is None else np.zeros(picture_shape, dtype={"f32": np.float32, "u8": np.uint8, "u16": np.uint16}[fmt])
-            _check(load_library().wtgpu_film_polar_host(self._h, v.ctypes.data, w.ctypes.data, l.ctypes.data, int(spe), C.byref(spec),
-                                                        None if m is None else m.ctypes.data, int(threads), C.cast(rec, C.c_void_p),
-                                                        None if mp is None else mp.ctypes.data, None if p is None else p.ctypes.data))
-            return mp, p
-        return self._film_polar("film_polar_host", call, luminance, maps, analyser, c2s2, picture, picture_plane, tm, fmt, sat_gain, m is not None)
+    def film_polar_developed_device(self, film, *, luminance=False, maps=(), analyser=0.0, c2s2=None, mask=None, picture=False, picture_plane=0, tm=None, fmt="f32",
+                                    sat_gain=1.0, stream=None):
+        """film_polar_device of a DEVELOPED polarimetric film where it is (wtgpu_film_polar_source_device): film a torch f32 tensor [H, W, channels, 4]
+        on the scene's device (develop_device's result, film_denoise_device's "film": how much polarisation the filter left).  The other arguments
+        and the dict are film_polar_device's."""
+        return self._film_polar_device("film_polar_developed_device", film, 0, luminance, maps, analyser, c2s2, mask, picture, picture_plane, tm, fmt, sat_gain, stream)
+
+    def film_polar_developed_host(self, film, *, luminance=False, maps=(), analyser=0.0, c2s2=None, mask=None, picture=False, picture_plane=0, tm=None, fmt="f32",
+                                  sat_gain=1.0, threads=0):
+        """film_polar_developed_device's twin on host threads (wtgpu_film_polar_source_host): film a contiguous numpy float32 array of the scene's planes."""
+        return self._film_polar_host("film_polar_developed_host", film, 0, luminance, maps, analyser, c2s2, mask, picture, picture_plane, tm, fmt, sat_gain, threads)
 
     # ---- denoising a film from its two half-films (wtgpu_film_denoise_*; csrc/wt/film_denoise.h) ----
     @staticmethod

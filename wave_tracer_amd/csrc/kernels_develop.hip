@@ -3,7 +3,8 @@
 // done where the films are.  k_develop writes the developed f32 film; k_develop_tonemap develops the planes of one Stokes component, applies the
 // operator, the mode and the colour table, appends an optional mask as alpha and writes f32 / 8-bit / 16-bit pixels — the developed values
 // never reach memory.  The arithmetic is wt/tonemap.h's, shared with the host twins at the end of the file.  Both kernels stream: every film
-// byte is read once, and the time is the memory system's.  No render kernel is compiled here.
+// byte is read once, and the time is the memory system's.  k_develop_tonemap is also compiled for a developed f32 film as its source (what k_develop
+// or a denoiser wrote; wt/film_stats.h: film_src_t).  No render kernel is compiled here.
 #include "kernels_film.h"
 
 namespace wtk {
@@ -34,8 +35,11 @@ __global__ void __launch_bounds__(kDevelopBlock) k_develop(const double* __restr
 // A pixel's C = 1 or 3 developed values (planes c * stokes + s) meet in one lane — the luminance, the table lookup and the pixel's single 4- to
 // 16-byte store need them together — so the lane-per-plane mapping of k_develop has nothing to offer here.  kLdsTable: the block copies the
 // colour table (at most kTableLdsEntries entries) to LDS first; otherwise the lanes read it through the caches.
-template <uint32_t C, bool kLdsTable>
-__global__ void __launch_bounds__(kDevelopBlock) k_develop_tonemap(const double* __restrict__ value, const double* __restrict__ weight,
+// kDev (a developed film, in `value`; wt/film_stats.h: film_src): the same lane per pixel, its C floats by 4-byte loads `stokes` floats apart —
+// contiguous across the wavefront for a monochromatic or RGB film (12 bytes a lane, which no 16-byte load fits); of a polarimetric film one
+// component in four is wanted, and a vector load per lane would fetch the same lines for the same bytes.  No alignment is asked of the film.
+template <bool kDev, uint32_t C, bool kLdsTable>
+__global__ void __launch_bounds__(kDevelopBlock) k_develop_tonemap(const film_elem_t<kDev>* __restrict__ value, const double* __restrict__ weight,
                                                                    const double* __restrict__ light, double sl, uint32_t stokes, uint32_t s, tonemap_args_t t,
                                                                    const float* __restrict__ mask, uint32_t format, uint64_t npix, void* __restrict__ out) {
     __shared__ float lds_table[kLdsTable ? 3 * kTableLdsEntries : 1];
@@ -47,7 +51,7 @@ __global__ void __launch_bounds__(kDevelopBlock) k_develop_tonemap(const double*
     const uint64_t p = blockIdx.x * (uint64_t)kDevelopBlock + threadIdx.x;
     if (p >= npix) return;
     float v[C], rgb[3];
-    fs_planes(value, light, weight[p], sl, p, C, stokes, s, false, 0u, v);
+    fs_planes(film_src(value, weight, light, sl), p, C, stokes, s, false, 0u, v);
     tm_pixel(t, v, C, rgb);
     if (!mask) {
         tm_store(out, p, format, 3, rgb, 0.f);
@@ -91,19 +95,17 @@ int develop_launch(const sensor_t& sn, hipStream_t stream, const double* d_value
     return (int)hipGetLastError();
 }
 
-template <uint32_t C>
-static void tonemap_launch_c(hipStream_t stream, const double* v, const double* w, const double* l, double sl, uint32_t stokes, uint32_t s, const tonemap_args_t& t,
+template <bool kDev, uint32_t C>
+static void tonemap_launch_c(hipStream_t stream, const film_elem_t<kDev>* v, const double* w, const double* l, double sl, uint32_t stokes, uint32_t s, const tonemap_args_t& t,
                              const float* mask, uint32_t format, bool lds_table, uint64_t npix, void* out) {
     if (lds_table)
-        hipLaunchKernelGGL((k_develop_tonemap<C, true>), dim3(blocks_for(npix)), dim3(kDevelopBlock), 0, stream, v, w, l, sl, stokes, s, t, mask, format, npix, out);
+        hipLaunchKernelGGL((k_develop_tonemap<kDev, C, true>), dim3(blocks_for(npix)), dim3(kDevelopBlock), 0, stream, v, w, l, sl, stokes, s, t, mask, format, npix, out);
     else
-        hipLaunchKernelGGL((k_develop_tonemap<C, false>), dim3(blocks_for(npix)), dim3(kDevelopBlock), 0, stream, v, w, l, sl, stokes, s, t, mask, format, npix, out);
+        hipLaunchKernelGGL((k_develop_tonemap<kDev, C, false>), dim3(blocks_for(npix)), dim3(kDevelopBlock), 0, stream, v, w, l, sl, stokes, s, t, mask, format, npix, out);
 }
-int develop_tonemap_launch(const sensor_t& sn, hipStream_t stream, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
-                           const tonemap_args_t& t, uint32_t s, const float* d_mask, uint32_t format, uint32_t lds_table, void* d_out) {
+int develop_tonemap_launch(const sensor_t& sn, hipStream_t stream, const wtgpu_film_source& film, const tonemap_args_t& t, uint32_t s, const float* d_mask, uint32_t format, uint32_t lds_table, void* d_out) {
     const uint64_t npix = (uint64_t)sn.width * sn.height;
     if (npix == 0) return 0;
-    const double sl = develop_scale(spe);
     const uint32_t stokes = film_stokes(sn);
     const bool lds = lds_table != 0 && t.table_n <= kTableLdsEntries;
     // The table is read through the caches unless the knob says otherwise: with every pixel going through a 256-entry table (colourmap mode,
@@ -112,27 +114,32 @@ int develop_tonemap_launch(const sensor_t& sn, hipStream_t stream, const double*
     // it.  To RGBA8 in normal mode the kernel takes 0.040 ms on the cornell film and 0.086 ms on the room film back to back, 0.042 and 0.28 - 0.30 ms
     // when the GPU has idled for 100 ms before the launch.
     if (!film_dispatch(sn.channels, false, [&](auto c, auto) {
-            tonemap_launch_c<decltype(c)::value>(stream, d_value, d_weight, d_light, sl, stokes, s, t, d_mask, format, lds, npix, d_out);
+            film_source_dispatch(film, [&](auto src) {
+                tonemap_launch_c<decltype(src)::developed, decltype(c)::value>(stream, src.first(), src.weight, src.light, src.sl, stokes, s, t, d_mask, format, lds, npix, d_out);
+            });
         }))
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
 // ---- the host twin: the same wt/tonemap.h functions on host threads, one task per row -------------------------------------------------------
-void develop_tonemap_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, const tonemap_args_t& t, uint32_t s,
-                          const float* mask, uint32_t format, uint32_t n_threads, void* out) {
+template <class Src>
+static void develop_tonemap_host_of(const sensor_t& sn, const Src& film, const tonemap_args_t& t, uint32_t s, const float* mask, uint32_t format, uint32_t n_threads, void* out) {
     const uint32_t W = sn.width, H = sn.height, C = sn.channels, stokes = film_stokes(sn);
-    const double sl = develop_scale(spe);
     on_threads(H, n_threads, [&](auto claim) {
         for (uint64_t y = claim(); y < H; y = claim())
             for (uint32_t x = 0; x < W; ++x) {
                 const size_t p = (size_t)y * W + x;
                 float v[3] = {0.f, 0.f, 0.f}, rgb[3];
-                fs_planes(value, light, weight[p], sl, p, C, stokes, s, false, 0u, v);
+                fs_planes(film, p, C, stokes, s, false, 0u, v);
                 tm_pixel(t, v, C, rgb);
                 tm_store(out, p, format, mask ? 4u : 3u, rgb, mask ? mask[p] : 0.f);
             }
     });
+}
+void develop_tonemap_host(const sensor_t& sn, const wtgpu_film_source& film, const tonemap_args_t& t, uint32_t s, const float* mask, uint32_t format, uint32_t n_threads,
+                          void* out) {
+    film_source_dispatch(film, [&](auto src) { develop_tonemap_host_of(sn, src, t, s, mask, format, n_threads, out); });
 }
 
 }   // namespace wtk

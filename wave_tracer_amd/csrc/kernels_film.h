@@ -1,6 +1,6 @@
 // wave_tracer_amd — what the film kernels (kernels_develop.hip, kernels_stats.hip, kernels_compare.hip, kernels_polar.hip, kernels_denoise.hip) and their host twins share beyond the
 // arithmetic of wt/film_stats.h: the chunk geometry of the fixed summation order on a wavefront, the reduction of the chunk sums, the grid that
-// follows the film, the choice of a kernel by (channels, luminance), and the host threads of the twins (the sensor-element maps' too: kernels_maps.h).
+// follows the film, the choice of a kernel by (channels, luminance) and by the film's source (film_source_dispatch), and the host threads of the twins (the sensor-element maps' too: kernels_maps.h).
 //
 // Chunk geometry.  A block is kFilmBlock = 256 threads, four wavefronts; a wavefront owns whole chunks of kFsChunk = 256 elements.  Wavefront g
 // of the grid takes chunks g, g + waves, ... (film_first_chunk, film_waves); of chunk k lane l holds elements 256 k + 64 j + l, j = 0 .. 3 (four
@@ -197,7 +197,17 @@ bool film_dispatch(uint32_t channels, bool luminance, F&& fn) {
     return true;
 }
 
-// The host twins' threads: worker(claim) runs once on each of n_threads threads (0: one per hardware thread; never more than there are items;
+// The kernels and the twins are compiled for the source kind as well: fn(src) gets the film_src_t (wt/film_stats.h) of a wtgpu_film_source that
+// has passed the entry point's check — a developed film, or the accumulators with their develop_scale(spe).
+template <class F>
+void film_source_dispatch(const wtgpu_film_source& f, F&& fn) {
+    if (f.developed)
+        fn(film_dev_t{f.developed});
+    else
+        fn(film_acc_t{f.value, f.weight, f.light, develop_scale(f.spe)});
+}
+
+// The host twins' threads:worker(claim) runs once on each of n_threads threads (0: one per hardware thread; never more than there are items;
 // the caller's is one of them) and takes items with  for (i = claim(); i < n_items; i = claim()).  What a thread keeps to itself — a stack,
 // partial records — lives in the worker's own frame.
 template <class F>

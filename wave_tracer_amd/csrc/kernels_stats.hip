@@ -5,7 +5,8 @@
 // the extrema's keys into floats.  The arithmetic is wt/film_stats.h's, shared with the host twin at the end of the file: every counter, every
 // bin, the extrema and the sum are the same on both sides, bit for bit.  Measured on the MI355X (tools/bench_film_stats.py, docs/FEATURES.md): 0.39 ms
 // for the 418 MB of the polarimetric 1920 x 1088 film, 1.06 TB/s — a fifth of k_develop's rate on the same film: the per-element work, not the
-// memory system, sets the time.  No render kernel is compiled here.
+// memory system, sets the time.  The same kernel is compiled for a developed f32 film as its source (wt/film_stats.h: film_src_t).  No render kernel
+// is compiled here.
 #include <cstring>
 #include <mutex>
 
@@ -20,14 +21,19 @@ constexpr uint32_t kStatsSmallBins = 1024;
 // elements per plane.
 constexpr uint32_t kStatsBlocksPerCU = 4;
 
-// ---- k_film_stats: f64 films [H][W][P], [H][W] -> records, histogram, chunk sums ----------------------------------------------------------
+// ---- k_film_stats: f64 films [H][W][P], [H][W] (or a developed f32 film [H][W][P]) -> records, histogram, chunk sums ----------------------------------------------------------
 // One lane per pixel, its C = 1 or 3 developed values of Stokes component s (and their luminance) in registers, in the chunk geometry of
 // kernels_film.h.  The loads are conditional: an excluded pixel's films are not read.
 // Bins: LDS atomics on the block's u32 histogram, flushed with 64-bit global atomics at the end (non-zero bins only).  The five classes
 // outside the bins and n are wavefront-uniform counts (ballots): zeros of an unlit background would otherwise all hit one LDS word.
 // Extrema: per lane as keys (fs_key) over all its chunks, one wavefront reduction and one global atomic each at the end.
-template <uint32_t C, bool kLum, uint32_t kBinCap>
-__global__ void __launch_bounds__(kFilmBlock) k_film_stats(const double* __restrict__ value, const double* __restrict__ weight, const double* __restrict__ light,
+// kDev (a developed film, in `value`; wt/film_stats.h: film_src): the same lane per pixel, which takes its C floats with 4-byte loads, `stokes`
+// floats apart.  A monochromatic or RGB film's 4 C bytes per lane are contiguous across the wavefront (an RGB wavefront's three load instructions
+// cover the same 768 bytes, every line of them used); of a polarimetric film the pass wants one component in four, so three quarters of each
+// line are fetched for nothing — 48 bytes per pixel at most against the accumulators' 200, and a vector load per lane would fetch the same
+// lines to throw the same bytes away in registers.  No vector load, so no alignment is asked of the film.
+template <bool kDev, uint32_t C, bool kLum, uint32_t kBinCap>
+__global__ void __launch_bounds__(kFilmBlock) k_film_stats(const film_elem_t<kDev>* __restrict__ value, const double* __restrict__ weight, const double* __restrict__ light,
                                                            double sl, uint32_t stokes, uint32_t s, uint32_t flags, const float* __restrict__ mask, uint64_t npix,
                                                            const float* __restrict__ edges, uint32_t bins, film_stats_rec_t* __restrict__ rec,
                                                            unsigned long long* __restrict__ hist, double* __restrict__ sums, uint64_t sums_stride) {
@@ -40,6 +46,7 @@ __global__ void __launch_bounds__(kFilmBlock) k_film_stats(const double* __restr
 
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t n_chunks = fs_chunks(npix), n_waves = film_waves();
+    const film_src_t<kDev> film = film_src(value, weight, light, sl);
     uint32_t min_inv[NP], max_key[NP], minpos_inv[NP], count[NP][FS_BIN];   // count: the same in every lane
     uint32_t n_included = 0;
 #pragma unroll
@@ -57,7 +64,7 @@ __global__ void __launch_bounds__(kFilmBlock) k_film_stats(const double* __restr
             float x[NP];
 #pragma unroll
             for (uint32_t c = 0; c < NP; ++c) x[c] = 0.f;
-            if (included) fs_planes(value, light, weight[p], sl, p, C, stokes, s, kLum, flags, x);
+            if (included) fs_planes(film, p, C, stokes, s, kLum, flags, x);
             n_included += (uint32_t)__popcll(__ballot(included));
 #pragma unroll
             for (uint32_t c = 0; c < NP; ++c) {
@@ -117,22 +124,20 @@ __global__ void __launch_bounds__(kFilmBlock) k_film_stats_finish(film_stats_rec
     }
 }
 
-template <uint32_t C, bool kLum>
-static void film_stats_launch_c(hipStream_t stream, uint32_t blocks, const double* v, const double* w, const double* l, double sl, uint32_t stokes, uint32_t s, uint32_t flags,
+template <bool kDev, uint32_t C, bool kLum>
+static void film_stats_launch_c(hipStream_t stream, uint32_t blocks, const film_elem_t<kDev>* v, const double* w, const double* l, double sl, uint32_t stokes, uint32_t s, uint32_t flags,
                                 const float* mask, uint64_t npix, const float* edges, uint32_t bins, film_stats_rec_t* rec, unsigned long long* hist, double* sums,
                                 uint64_t stride) {
     if (bins <= kStatsSmallBins)
-        hipLaunchKernelGGL((k_film_stats<C, kLum, kStatsSmallBins>), dim3(blocks), dim3(kFilmBlock), 0, stream, v, w, l, sl, stokes, s, flags, mask, npix, edges, bins, rec,
+        hipLaunchKernelGGL((k_film_stats<kDev, C, kLum, kStatsSmallBins>), dim3(blocks), dim3(kFilmBlock), 0, stream, v, w, l, sl, stokes, s, flags, mask, npix, edges, bins, rec,
                            hist, sums, stride);
     else
-        hipLaunchKernelGGL((k_film_stats<C, kLum, kFsMaxBins>), dim3(blocks), dim3(kFilmBlock), 0, stream, v, w, l, sl, stokes, s, flags, mask, npix, edges, bins, rec, hist,
+        hipLaunchKernelGGL((k_film_stats<kDev, C, kLum, kFsMaxBins>), dim3(blocks), dim3(kFilmBlock), 0, stream, v, w, l, sl, stokes, s, flags, mask, npix, edges, bins, rec, hist,
                            sums, stride);
 }
-int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe, uint32_t s,
-                      uint32_t flags, const float* d_mask, const float* d_edges, uint32_t bins, void* d_rec, unsigned long long* d_hist, double* d_sums) {
+int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const wtgpu_film_source& film, uint32_t s, uint32_t flags, const float* d_mask, const float* d_edges, uint32_t bins, void* d_rec, unsigned long long* d_hist, double* d_sums) {
     const uint64_t npix = (uint64_t)sn.width * sn.height;
     if (npix == 0 || bins > kFsMaxBins) return (int)hipErrorInvalidValue;
-    const double sl = develop_scale(spe);
     const bool lum = (flags & FS_LUMINANCE) != 0;
     const uint64_t n_chunks = fs_chunks(npix), stride = fs_scratch_len(npix);
     // kStatsBlocksPerCU blocks per CU at most (1920 x 1088: 8160 chunks on 1024 blocks, two per wavefront): each block flushes its histogram once,
@@ -140,8 +145,10 @@ int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, co
     const uint32_t blocks = film_grid_blocks(npix, n_cus, kStatsBlocksPerCU);
     film_stats_rec_t* rec = static_cast<film_stats_rec_t*>(d_rec);
     if (!film_dispatch(sn.channels, lum, [&](auto c, auto l) {
-            film_stats_launch_c<decltype(c)::value, decltype(l)::value>(stream, blocks, d_value, d_weight, d_light, sl, film_stokes(sn), s, flags, d_mask, npix, d_edges, bins,
-                                                                        rec, d_hist, d_sums, stride);
+            film_source_dispatch(film, [&](auto src) {
+                film_stats_launch_c<decltype(src)::developed, decltype(c)::value, decltype(l)::value>(stream, blocks, src.first(), src.weight, src.light, src.sl, film_stokes(sn), s,
+                                                                                                      flags, d_mask, npix, d_edges, bins, rec, d_hist, d_sums, stride);
+            });
         }))
         return (int)hipErrorInvalidValue;
     if (const hipError_t e = hipGetLastError()) return (int)e;
@@ -151,11 +158,11 @@ int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, co
 
 // ---- the host twin: the same wt/film_stats.h functions on host threads, one task per chunk; the counts are integers and a chunk's sum is one
 // thread's, so the result does not depend on the number of threads -----------------------------------------------------------------------------
-void film_stats_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, uint32_t s, uint32_t flags, const float* mask,
-                     const float* edges, uint32_t bins, uint32_t n_threads, void* out_rec, unsigned long long* out_hist) {
+template <class Src>
+static void film_stats_host_of(const sensor_t& sn, const Src& film, uint32_t s, uint32_t flags, const float* mask, const float* edges, uint32_t bins, uint32_t n_threads,
+                               void* out_rec, unsigned long long* out_hist) {
     const uint32_t C = sn.channels, stokes = film_stokes(sn), NP = C + ((flags & FS_LUMINANCE) ? 1u : 0u);
     const uint64_t npix = (uint64_t)sn.width * sn.height, n_chunks = fs_chunks(npix), stride = fs_scratch_len(npix);
-    const double sl = develop_scale(spe);
     film_stats_rec_t* rec = static_cast<film_stats_rec_t*>(out_rec);
     std::memset(rec, 0, NP * sizeof(film_stats_rec_t));
     if (out_hist) std::memset(out_hist, 0, (size_t)NP * bins * sizeof(unsigned long long));
@@ -170,7 +177,7 @@ void film_stats_host(const sensor_t& sn, const double* value, const double* weig
                 const uint64_t p = chunk * kFsChunk + i;
                 const bool included = p < npix && (!mask || mask[p] > 0.f);
                 float x[kFsMaxPlanes] = {0.f, 0.f, 0.f, 0.f};
-                if (included) fs_planes(value, light, weight[p], sl, p, C, stokes, s, NP > C, flags, x);
+                if (included) fs_planes(film, p, C, stokes, s, NP > C, flags, x);
                 for (uint32_t c = 0; c < NP; ++c) {
                     a[c][i] = fs_addend(x[c], included);
                     if (!included) continue;
@@ -208,6 +215,10 @@ void film_stats_host(const sensor_t& sn, const double* value, const double* weig
         std::memcpy(&r.max_key, &mx, 4);
         std::memcpy(&r.minpos_inv, &mp, 4);
     }
+}
+void film_stats_host(const sensor_t& sn, const wtgpu_film_source& film, uint32_t s, uint32_t flags, const float* mask, const float* edges, uint32_t bins, uint32_t n_threads,
+                     void* out_rec, unsigned long long* out_hist) {
+    film_source_dispatch(film, [&](auto src) { film_stats_host_of(sn, src, s, flags, mask, edges, bins, n_threads, out_rec, out_hist); });
 }
 
 }   // namespace wtk

@@ -2,7 +2,8 @@
 // What a pixel's planes are (fs_planes), the flags and the summation order are also the film comparison's (wt/film_compare.h) and, for the
 // developed values, the tonemapper's (kernels_develop.hip).
 //
-// Element value.  x = develop_plane(...) of wt/tonemap.h, the f32 wtgpu_develop writes, of plane  channel * stokes + stokes_component;  with
+// Element value.  x = develop_plane(...) of wt/tonemap.h, the f32 wtgpu_develop writes, of plane  channel * stokes + stokes_component — or, from a
+// developed film, that f32 as it lies there (film_src_t: the one statement of the two sources, for all the film passes);  with
 // FS_LUMINANCE a 3-channel film has a fourth plane, tm_luminance of the three developed values (taken before FS_ABS).  FS_ABS: fabsf(x), for the
 // signed Stokes components Q / U / V (a NaN stays a NaN).
 // Membership.  A pixel's elements are included iff no mask is given or mask[pixel] > 0 (a NaN mask value excludes).
@@ -16,6 +17,8 @@
 // reduced by the butterfly pairing a[i] += a[i + d] (i < d) for d = 128, 64, ... 1 with +0.0 for excluded, NaN and missing elements; the
 // chunk sums reduced by the same rule, level after level, until one number is left (fs_level_count).  Only additions: nothing to contract.
 #pragma once
+#include <type_traits>
+
 #include "core.h"
 #include "tonemap.h"
 
@@ -74,12 +77,53 @@ WT_HD uint32_t fs_classify(float x, const float* edge, uint32_t bins, uint32_t& 
     return FS_BIN;
 }
 
-// A pixel's planes: the developed values of planes  c * stokes + s  of its `channels` channels, behind them — with `luminance`, 3-channel films
+// What a film pass reads its elements from (wtgpu_film_source), in two forms; THE place that knows them — fs_planes, the polarisation view's
+// loaders (kernels_polar.hip) and the host twins read a film through it and nothing else does.  An element is plane  c * stokes + s  of a pixel,
+// element index  pixel * planes + c * stokes + s;  what it needs of its pixel (the accumulators' weight word) is fetched once per pixel.
+//   film_src_t<false>  the accumulators as wtgpu_render fills them: develop_plane of value / weight / light with sl = develop_scale(spe);
+//   film_src_t<true>   a developed film [height][width][channels][stokes] f32 (wtgpu_develop's, a denoiser's): the element as it is, any f32.
+template <bool kDeveloped>
+struct film_src_t;
+typedef float film_quad_t __attribute__((vector_size(16), aligned(4)));   // four consecutive elements of a developed film, wherever they lie
+typedef float film_quad_aligned_t __attribute__((vector_size(16)));
+template <>
+struct film_src_t<false> {
+    static constexpr bool developed = false;
+    const double *value, *weight, *light;
+    double sl;
+    WT_HD const double* first() const { return value; }
+    WT_HD double pixel_word(uint64_t pixel) const { return weight[pixel]; }
+    WT_HD float element(uint64_t e, double w) const { return develop_plane(value[e], w, light[e], sl); }
+    WT_HD float element_of(uint64_t e, uint32_t planes) const { return develop_plane(value[e], weight[e / planes], light[e], sl); }   // (a lane per element: k_develop's mapping)
+};
+template <>
+struct film_src_t<true> {
+    static constexpr bool developed = true;
+    const float* film;
+    static constexpr const double *weight = nullptr, *light = nullptr;   // (what a launch passes in the unused arguments)
+    static constexpr double sl = 0.0;
+    WT_HD const float* first() const { return film; }
+    WT_HD double pixel_word(uint64_t) const { return 0.0; }
+    WT_HD float element(uint64_t e, double) const { return film[e]; }
+    WT_HD float element_of(uint64_t e, uint32_t) const { return film[e]; }
+    WT_HD film_quad_t element4(uint64_t quad) const { return reinterpret_cast<const film_quad_t*>(film)[quad]; }   // elements 4 quad .. 4 quad + 3
+};
+using film_acc_t = film_src_t<false>;
+using film_dev_t = film_src_t<true>;
+// The kernels take a source as the four arguments they always took (the pointers __restrict__, which a struct's members cannot say): the first is
+// the developed film where the kernel is compiled for one, and the other three are then null and not read.
+template <bool kDeveloped>
+using film_elem_t = std::conditional_t<kDeveloped, float, double>;
+WT_HD film_acc_t film_src(const double* value, const double* weight, const double* light, double sl) { return film_acc_t{value, weight, light, sl}; }
+WT_HD film_dev_t film_src(const float* developed, const double*, const double*, double) { return film_dev_t{developed}; }
+
+// A pixel's planes: the element values of planes  c * stokes + s  of its `channels` channels, behind them — with `luminance`, 3-channel films
 // only — the luminance of the three, taken before FS_ABS; then FS_ABS of all.  x: channels + luminance floats.
-WT_HD void fs_planes(const double* value, const double* light, double w, double sl, uint64_t pixel, uint32_t channels, uint32_t stokes, uint32_t s, bool luminance,
-                     uint32_t flags, float* x) {
+template <bool kDeveloped>
+WT_HD void fs_planes(const film_src_t<kDeveloped>& f, uint64_t pixel, uint32_t channels, uint32_t stokes, uint32_t s, bool luminance, uint32_t flags, float* x) {
+    const double w = f.pixel_word(pixel);
     const uint64_t base = pixel * (channels * stokes) + s;
-    for (uint32_t c = 0; c < channels; ++c) x[c] = develop_plane(value[base + c * stokes], w, light[base + c * stokes], sl);
+    for (uint32_t c = 0; c < channels; ++c) x[c] = f.element(base + c * stokes, w);
     if (luminance) x[channels] = tm_luminance(x[0], x[1], x[2]);
     for (uint32_t c = 0; c < channels + (luminance ? 1u : 0u); ++c) x[c] = (flags & FS_ABS) ? fabsf(x[c]) : x[c];
 }

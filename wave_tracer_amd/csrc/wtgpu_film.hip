@@ -1,6 +1,7 @@
 // wave_tracer_amd — the entry points that read films: develop, the tonemap spec / device / host calls (kernels_develop.hip), film statistics
 // (kernels_stats.hip), film comparison (kernels_compare.hip), the polarisation view (kernels_polar.hip) and the denoiser of two half-films (kernels_denoise.hip); what they check of a film
-// and keep with the scene between calls.
+// and keep with the scene between calls.  The four passes that read a film take a wtgpu_film_source — the accumulators or a developed f32 film — and
+// the accumulator-taking entry points are those calls with an accumulator source.
 #include <cstddef>
 
 #include "wtgpu_host.h"
@@ -21,6 +22,20 @@ static int film_planes_for(const wtgpu_scene* s, const char* what, uint32_t stok
     if ((flags & FS_LUMINANCE) && sn.channels != 3) return fail(WTGPU_ERR_INVALID, w + "LUMINANCE needs a 3-channel film (this one has " + std::to_string(sn.channels) + ")");
     planes = sn.channels + ((flags & FS_LUMINANCE) ? 1u : 0u);
     return WTGPU_OK;
+}
+
+// A film source (wtgpu_film_source) is exactly one of its two forms.  `what` opens the message, `which` names the operand where there are two.
+static int film_source_check(const char* what, const char* which, const wtgpu_film_source* f) {
+    const std::string w = std::string(what) + ": " + which;
+    const int n_acc = (f->value ? 1 : 0) + (f->weight ? 1 : 0) + (f->light ? 1 : 0);
+    if (f->developed && n_acc) return fail(WTGPU_ERR_INVALID, w + "film source: both forms are set (the accumulators value / weight / light, or a developed film: one of them)");
+    if (!f->developed && n_acc == 0) return fail(WTGPU_ERR_INVALID, w + "film source: neither form is set (the accumulators value / weight / light, or a developed film)");
+    if (n_acc != 0 && n_acc != 3) return fail(WTGPU_ERR_INVALID, w + "film source: the accumulators are value, weight and light together (" + std::to_string(n_acc) + " of the 3 set)");
+    return WTGPU_OK;
+}
+// the source an accumulator-taking entry point stands for
+static wtgpu_film_source accumulators(const double* value, const double* weight, const double* light, uint64_t spe) {
+    return wtgpu_film_source{value, weight, light, spe, nullptr};
 }
 
 // A feature's scratch is allocated at its first call: d_bytes on the device, the first h_bytes of them pinned on the host, n_sums chunk sums.
@@ -181,42 +196,57 @@ int wtgpu_develop_device(wtgpu_scene* s, void* stream_, const double* d_value, c
     if (e) return fail(WTGPU_ERR_HIP, std::string("k_develop: ") + hipGetErrorString((hipError_t)e));
     return WTGPU_OK;
 }
-int wtgpu_tonemap_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe, const wtgpu_tonemap* tm,
-                         uint32_t stokes_component, const float* d_mask, uint32_t format, void* d_out) {
-    if (!s || !d_value || !d_weight || !d_light || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+int wtgpu_tonemap_source_device(wtgpu_scene* s, void* stream_, const wtgpu_film_source* film, const wtgpu_tonemap* tm, uint32_t stokes_component, const float* d_mask,
+                                uint32_t format, void* d_out) {
+    if (!s || !film || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (const int rc = film_source_check("tonemap", "", film)) return rc;
     tonemap_args_t args{};
     std::vector<float> own;
     if (const int rc = tonemap_args_for(s, tm, stokes_component, format, args, own)) return rc;
-    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "scene not uploaded");
-    if ((uintptr_t)d_out % 16) return fail(WTGPU_ERR_INVALID, "tonemap: d_out must be aligned to 16 bytes");
-    device_guard_t guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (args.table) {   // the table goes to the device behind everything already on `stream`, through a pinned copy made before the call returns
-        const size_t bytes = (size_t)kMaxTonemapTable * 3 * sizeof(float);
-        if (!s->ev_tm) {
-            float* d = nullptr;
-            if (const int rc = dmalloc(s, &d, (size_t)kMaxTonemapTable * 3)) return rc;
-            HIP_CHECK(hipHostMalloc((void**)&s->h_tm_table, bytes, hipHostMallocDefault));
-            HIP_CHECK(hipEventCreateWithFlags(&s->ev_tm, hipEventDisableTiming));
-            s->d_tm_table = d;
-        } else
-            HIP_CHECK(hipEventSynchronize(s->ev_tm));   // the previous call's kernel has read the buffers
-        std::memcpy(s->h_tm_table, args.table, (size_t)args.table_n * 3 * sizeof(float));
-        HIP_CHECK(hipMemcpyAsync(s->d_tm_table, s->h_tm_table, (size_t)args.table_n * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
-        args.table = s->d_tm_table;
-    }
-    const int e = develop_tonemap_launch(s->host.sensor, stream, d_value, d_weight, d_light, spe, args, stokes_component, d_mask, format, s->knobs.tonemap_lds_table, d_out);
-    if (e) return fail(WTGPU_ERR_HIP, std::string("k_develop_tonemap: ") + hipGetErrorString((hipError_t)e));
-    if (args.table) HIP_CHECK(hipEventRecord(s->ev_tm, stream));
-    return WTGPU_OK;
+    // (a scene that is not uploaded is refused first, as it always was: film_on_device says so)
+    if (s->uploaded && (uintptr_t)d_out % 16) return fail(WTGPU_ERR_INVALID, "tonemap: d_out must be aligned to 16 bytes");
+    return film_on_device(s, stream_, "tonemap", [&](hipStream_t stream, uint64_t) -> int {
+        if (args.table) {   // the table goes to the device behind everything already on `stream`, through a pinned copy made before the call returns
+            const size_t bytes = (size_t)kMaxTonemapTable * 3 * sizeof(float);
+            if (!s->ev_tm) {
+                float* d = nullptr;
+                if (const int rc = dmalloc(s, &d, (size_t)kMaxTonemapTable * 3)) return rc;
+                HIP_CHECK(hipHostMalloc((void**)&s->h_tm_table, bytes, hipHostMallocDefault));
+                HIP_CHECK(hipEventCreateWithFlags(&s->ev_tm, hipEventDisableTiming));
+                s->d_tm_table = d;
+            } else
+                HIP_CHECK(hipEventSynchronize(s->ev_tm));   // the previous call's kernel has read the buffers
+            std::memcpy(s->h_tm_table, args.table, (size_t)args.table_n * 3 * sizeof(float));
+            HIP_CHECK(hipMemcpyAsync(s->d_tm_table, s->h_tm_table, (size_t)args.table_n * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+            args.table = s->d_tm_table;
+        }
+        const int e = develop_tonemap_launch(s->host.sensor, stream, *film, args, stokes_component, d_mask, format, s->knobs.tonemap_lds_table, d_out);
+        if (e) return fail(WTGPU_ERR_HIP, std::string("k_develop_tonemap: ") + hipGetErrorString((hipError_t)e));
+        if (args.table) HIP_CHECK(hipEventRecord(s->ev_tm, stream));
+        return WTGPU_OK;
+    });
+}
+int wtgpu_tonemap_source_host(const wtgpu_scene* s, const wtgpu_film_source* film, const wtgpu_tonemap* tm, uint32_t stokes_component, const float* mask, uint32_t format,
+                              uint32_t n_threads, void* out) {
+    if (!s || !film || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (const int rc = film_source_check("tonemap", "", film)) return rc;
+    tonemap_args_t args{};
+    std::vector<float> own;
+    if (const int rc = tonemap_args_for(s, tm, stokes_component, format, args, own)) return rc;
+    return film_on_host([&] { develop_tonemap_host(s->host.sensor, *film, args, stokes_component, mask, format, n_threads, out); });
+}
+// the accumulators' entry points: the same calls with an accumulator source
+int wtgpu_tonemap_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe, const wtgpu_tonemap* tm,
+                         uint32_t stokes_component, const float* d_mask, uint32_t format, void* d_out) {
+    if (!s || !d_value || !d_weight || !d_light || !d_out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const wtgpu_film_source film = accumulators(d_value, d_weight, d_light, spe);
+    return wtgpu_tonemap_source_device(s, stream_, &film, tm, stokes_component, d_mask, format, d_out);
 }
 int wtgpu_tonemap_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_tonemap* tm,
                        uint32_t stokes_component, const float* mask, uint32_t format, uint32_t n_threads, void* out) {
     if (!s || !value || !weight || !light || !out) return fail(WTGPU_ERR_INVALID, "null argument");
-    tonemap_args_t args{};
-    std::vector<float> own;
-    if (const int rc = tonemap_args_for(s, tm, stokes_component, format, args, own)) return rc;
-    return film_on_host([&] { develop_tonemap_host(s->host.sensor, value, weight, light, spe, args, stokes_component, mask, format, n_threads, out); });
+    const wtgpu_film_source film = accumulators(value, weight, light, spe);
+    return wtgpu_tonemap_source_host(s, &film, tm, stokes_component, mask, format, n_threads, out);
 }
 
 // ---- film statistics (kernels_stats.hip; wt/film_stats.h) -----------------------------------------------------------------------------------
@@ -246,9 +276,10 @@ int wtgpu_film_stats_edges(const wtgpu_film_stats_spec* spec, float* edges) {
 constexpr size_t kFsRecBytes = kFsMaxPlanes * sizeof(film_stats_rec_t), kFsHistBytes = (size_t)kFsMaxPlanes * kFsMaxBins * sizeof(uint64_t);
 constexpr size_t kFsEdgeOffset = kFsRecBytes + kFsHistBytes, kFsBlockBytes = kFsEdgeOffset + (kFsMaxBins + 1) * sizeof(float);
 
-int wtgpu_film_stats_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
-                            const wtgpu_film_stats_spec* spec, const float* d_mask, wtgpu_film_stats* out, uint64_t* hist) {
-    if (!s || !d_value || !d_weight || !d_light || !spec || !out || (!hist && spec->bins > 0)) return fail(WTGPU_ERR_INVALID, "null argument");
+int wtgpu_film_stats_source_device(wtgpu_scene* s, void* stream_, const wtgpu_film_source* film, const wtgpu_film_stats_spec* spec, const float* d_mask, wtgpu_film_stats* out,
+                                   uint64_t* hist) {
+    if (!s || !film || !spec || !out || (!hist && spec->bins > 0)) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (const int rc = film_source_check("film_stats", "", film)) return rc;
     uint32_t planes = 0;
     float edges[kFsMaxBins + 1];
     if (const int rc = film_stats_edges_for(spec, edges)) return rc;
@@ -261,7 +292,7 @@ int wtgpu_film_stats_device(wtgpu_scene* s, void* stream_, const double* d_value
         std::memcpy(f.h_block + kFsEdgeOffset, edges, edge_bytes);
         HIP_CHECK(hipMemcpyAsync(f.d_block + kFsEdgeOffset, f.h_block + kFsEdgeOffset, edge_bytes, hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipMemsetAsync(f.d_block, 0, kFsRecBytes + hist_bytes, stream));
-        const int e = film_stats_launch(s->host.sensor, stream, s->n_cus, d_value, d_weight, d_light, spe, spec->stokes_component, spec->flags, d_mask,
+        const int e = film_stats_launch(s->host.sensor, stream, s->n_cus, *film, spec->stokes_component, spec->flags, d_mask,
                                         reinterpret_cast<const float*>(f.d_block + kFsEdgeOffset), spec->bins, f.d_block,
                                         reinterpret_cast<unsigned long long*>(f.d_block + kFsRecBytes), f.d_sums);
         if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_stats: ") + hipGetErrorString((hipError_t)e));
@@ -270,17 +301,29 @@ int wtgpu_film_stats_device(wtgpu_scene* s, void* stream_, const double* d_value
         return WTGPU_OK;
     });
 }
-int wtgpu_film_stats_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_film_stats_spec* spec,
-                          const float* mask, uint32_t n_threads, wtgpu_film_stats* out, uint64_t* hist) {
-    if (!s || !value || !weight || !light || !spec || !out || (!hist && spec->bins > 0)) return fail(WTGPU_ERR_INVALID, "null argument");
+int wtgpu_film_stats_source_host(const wtgpu_scene* s, const wtgpu_film_source* film, const wtgpu_film_stats_spec* spec, const float* mask, uint32_t n_threads,
+                                 wtgpu_film_stats* out, uint64_t* hist) {
+    if (!s || !film || !spec || !out || (!hist && spec->bins > 0)) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (const int rc = film_source_check("film_stats", "", film)) return rc;
     uint32_t planes = 0;
     float edges[kFsMaxBins + 1];
     if (const int rc = film_stats_edges_for(spec, edges)) return rc;
     if (const int rc = film_planes_for(s, "film_stats", spec->stokes_component, spec->flags, planes)) return rc;
     return film_on_host([&] {
-        film_stats_host(s->host.sensor, value, weight, light, spe, spec->stokes_component, spec->flags, mask, edges, spec->bins, n_threads, out,
-                        reinterpret_cast<unsigned long long*>(hist));
+        film_stats_host(s->host.sensor, *film, spec->stokes_component, spec->flags, mask, edges, spec->bins, n_threads, out, reinterpret_cast<unsigned long long*>(hist));
     });
+}
+int wtgpu_film_stats_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                            const wtgpu_film_stats_spec* spec, const float* d_mask, wtgpu_film_stats* out, uint64_t* hist) {
+    if (!s || !d_value || !d_weight || !d_light || !spec || !out || (!hist && spec->bins > 0)) return fail(WTGPU_ERR_INVALID, "null argument");
+    const wtgpu_film_source film = accumulators(d_value, d_weight, d_light, spe);
+    return wtgpu_film_stats_source_device(s, stream_, &film, spec, d_mask, out, hist);
+}
+int wtgpu_film_stats_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_film_stats_spec* spec,
+                          const float* mask, uint32_t n_threads, wtgpu_film_stats* out, uint64_t* hist) {
+    if (!s || !value || !weight || !light || !spec || !out || (!hist && spec->bins > 0)) return fail(WTGPU_ERR_INVALID, "null argument");
+    const wtgpu_film_source film = accumulators(value, weight, light, spe);
+    return wtgpu_film_stats_source_host(s, &film, spec, mask, n_threads, out, hist);
 }
 
 // ---- film comparison (kernels_compare.hip; wt/film_compare.h) -------------------------------------------------------------------------------
@@ -299,31 +342,43 @@ static int film_compare_check(const wtgpu_scene* s, const wtgpu_film_compare_spe
     return film_planes_for(s, "film_compare", spec->stokes_component, spec->flags, planes);
 }
 
-int wtgpu_film_compare_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
-                              const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec, const float* d_mask,
-                              wtgpu_film_compare* out, float* d_diff) {
-    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+int wtgpu_film_compare_source_device(wtgpu_scene* s, void* stream_, const wtgpu_film_source* a, const wtgpu_film_source* b, const wtgpu_film_compare_spec* spec,
+                                     const float* d_mask, wtgpu_film_compare* out, float* d_diff) {
+    if (!s || !a || !b || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (const int rc = film_source_check("film_compare", "A: ", a)) return rc;
+    if (const int rc = film_source_check("film_compare", "B: ", b)) return rc;
     uint32_t planes = 0;
     if (const int rc = film_compare_check(s, spec, planes)) return rc;
     return film_on_device(s, stream_, "film_compare", [&](hipStream_t stream, uint64_t npix) -> int {
         film_scratch_t& f = s->fc;
         if (const int rc = film_rec_scratch<kFcSums>(s, f, npix)) return rc;
-        const int e = film_compare_launch(s->host.sensor, stream, s->n_cus, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec->stokes_component,
-                                          spec->flags, spec->eps, d_mask, f.d_block, f.d_sums, f.d_block + kFilmRecBytes<kFcSums>, d_diff);
+        const int e = film_compare_launch(s->host.sensor, stream, s->n_cus, *a, *b, spec->stokes_component, spec->flags, spec->eps, d_mask, f.d_block, f.d_sums, f.d_block + kFilmRecBytes<kFcSums>, d_diff);
         if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_compare: ") + hipGetErrorString((hipError_t)e));
         return film_records_back(f, stream, out, planes * sizeof(wtgpu_film_compare));
     });
+}
+int wtgpu_film_compare_source_host(const wtgpu_scene* s, const wtgpu_film_source* a, const wtgpu_film_source* b, const wtgpu_film_compare_spec* spec, const float* mask,
+                                   uint32_t n_threads, wtgpu_film_compare* out, float* diff) {
+    if (!s || !a || !b || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (const int rc = film_source_check("film_compare", "A: ", a)) return rc;
+    if (const int rc = film_source_check("film_compare", "B: ", b)) return rc;
+    uint32_t planes = 0;
+    if (const int rc = film_compare_check(s, spec, planes)) return rc;
+    return film_on_host([&] { film_compare_host(s->host.sensor, *a, *b, spec->stokes_component, spec->flags, spec->eps, mask, n_threads, out, diff); });
+}
+int wtgpu_film_compare_device(wtgpu_scene* s, void* stream_, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
+                              const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec, const float* d_mask,
+                              wtgpu_film_compare* out, float* d_diff) {
+    if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const wtgpu_film_source a = accumulators(a_value, a_weight, a_light, spe_a), b = accumulators(b_value, b_weight, b_light, spe_b);
+    return wtgpu_film_compare_source_device(s, stream_, &a, &b, spec, d_mask, out, d_diff);
 }
 int wtgpu_film_compare_host(const wtgpu_scene* s, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
                             const double* b_weight, const double* b_light, uint64_t spe_b, const wtgpu_film_compare_spec* spec, const float* mask, uint32_t n_threads,
                             wtgpu_film_compare* out, float* diff) {
     if (!s || !a_value || !a_weight || !a_light || !b_value || !b_weight || !b_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
-    uint32_t planes = 0;
-    if (const int rc = film_compare_check(s, spec, planes)) return rc;
-    return film_on_host([&] {
-        film_compare_host(s->host.sensor, a_value, a_weight, a_light, spe_a, b_value, b_weight, b_light, spe_b, spec->stokes_component, spec->flags, spec->eps, mask, n_threads,
-                          out, diff);
-    });
+    const wtgpu_film_source a = accumulators(a_value, a_weight, a_light, spe_a), b = accumulators(b_value, b_weight, b_light, spe_b);
+    return wtgpu_film_compare_source_host(s, &a, &b, spec, mask, n_threads, out, diff);
 }
 
 // ---- the polarisation view of a Stokes film (kernels_polar.hip; wt/film_polar.h) ------------------------------------------------------------
@@ -357,9 +412,10 @@ static int film_polar_check(const wtgpu_scene* s, const wtgpu_film_polar_spec* s
     return WTGPU_OK;
 }
 
-int wtgpu_film_polar_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
-                            const wtgpu_film_polar_spec* spec, const float* d_mask, wtgpu_film_polar* out, float* d_maps, void* d_picture) {
-    if (!s || !d_value || !d_weight || !d_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+int wtgpu_film_polar_source_device(wtgpu_scene* s, void* stream_, const wtgpu_film_source* film, const wtgpu_film_polar_spec* spec, const float* d_mask, wtgpu_film_polar* out,
+                                   float* d_maps, void* d_picture) {
+    if (!s || !film || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (const int rc = film_source_check("film_polar", "", film)) return rc;
     uint32_t planes = 0;
     film_polar_args_t a{};
     if (const int rc = film_polar_check(s, spec, planes, a)) return rc;
@@ -367,20 +423,33 @@ int wtgpu_film_polar_device(wtgpu_scene* s, void* stream_, const double* d_value
     return film_on_device(s, stream_, "film_polar", [&](hipStream_t stream, uint64_t npix) -> int {
         film_scratch_t& f = s->fp;
         if (const int rc = film_rec_scratch<kFpSums>(s, f, npix)) return rc;
-        const int e = film_polar_launch(s->host.sensor, stream, s->n_cus, d_value, d_weight, d_light, spe, spec->flags, a, s->knobs.film_polar_staged, d_mask, f.d_block,
+        const int e = film_polar_launch(s->host.sensor, stream, s->n_cus, *film, spec->flags, a, s->knobs.film_polar_staged, d_mask, f.d_block,
                                         f.d_sums, f.d_block + kFilmRecBytes<kFpSums>, d_maps, d_picture);
         if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_polar: ") + hipGetErrorString((hipError_t)e));
         return film_records_back(f, stream, out, planes * sizeof(wtgpu_film_polar));
     });
 }
-int wtgpu_film_polar_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_film_polar_spec* spec,
-                          const float* mask, uint32_t n_threads, wtgpu_film_polar* out, float* maps, void* picture) {
-    if (!s || !value || !weight || !light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+int wtgpu_film_polar_source_host(const wtgpu_scene* s, const wtgpu_film_source* film, const wtgpu_film_polar_spec* spec, const float* mask, uint32_t n_threads,
+                                 wtgpu_film_polar* out, float* maps, void* picture) {
+    if (!s || !film || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (const int rc = film_source_check("film_polar", "", film)) return rc;
     uint32_t planes = 0;
     film_polar_args_t a{};
     if (const int rc = film_polar_check(s, spec, planes, a)) return rc;
     if (maps && a.n_maps == 0) return fail(WTGPU_ERR_INVALID, "film_polar: maps without a map bit");
-    return film_on_host([&] { film_polar_host(s->host.sensor, value, weight, light, spe, spec->flags, a, mask, n_threads, out, maps, picture); });
+    return film_on_host([&] { film_polar_host(s->host.sensor, *film, spec->flags, a, mask, n_threads, out, maps, picture); });
+}
+int wtgpu_film_polar_device(wtgpu_scene* s, void* stream_, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
+                            const wtgpu_film_polar_spec* spec, const float* d_mask, wtgpu_film_polar* out, float* d_maps, void* d_picture) {
+    if (!s || !d_value || !d_weight || !d_light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const wtgpu_film_source film = accumulators(d_value, d_weight, d_light, spe);
+    return wtgpu_film_polar_source_device(s, stream_, &film, spec, d_mask, out, d_maps, d_picture);
+}
+int wtgpu_film_polar_host(const wtgpu_scene* s, const double* value, const double* weight, const double* light, uint64_t spe, const wtgpu_film_polar_spec* spec,
+                          const float* mask, uint32_t n_threads, wtgpu_film_polar* out, float* maps, void* picture) {
+    if (!s || !value || !weight || !light || !spec || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    const wtgpu_film_source film = accumulators(value, weight, light, spe);
+    return wtgpu_film_polar_source_host(s, &film, spec, mask, n_threads, out, maps, picture);
 }
 
 // ---- denoising a film from its two half-films (kernels_denoise.hip; wt/film_denoise.h) -------------------------------------------------------

@@ -635,44 +635,40 @@ void first_hit_material_host(const scene_t& sc, const fhm_query_t& q, uint32_t n
 int los_launch(const scene_t& sc, hipStream_t stream, const los_query_t& q, uint32_t per_sample, float* d_maps, float* d_elem, uint32_t* d_ids);
 void los_host(const scene_t& sc, const los_query_t& q, uint32_t n_threads, float* out_maps, float* out_elem, uint32_t* out_ids);
 // kernels_develop.hip: film development and tonemapping (wtgpu_develop_device / wtgpu_tonemap_device / wtgpu_tonemap_host).  Films as wtgpu_render
-// fills them; `t.table` is a DEVICE pointer for the launch and a host pointer for the host twin; s: the Stokes component; d_mask: null, or one
-// f32 per pixel that becomes the fourth component.  per_pixel / lds_table: the measured alternatives (WTGPU_DEVELOP_PER_PIXEL, WTGPU_TONEMAP_LDS_TABLE).
+// fills them, or — the passes that take a wtgpu_film_source, here and below — a developed f32 film, one of the two after the entry point's check
+// (film_source_check; device memory for a launch, host memory for a twin); `t.table` is a DEVICE pointer for the launch and a host pointer for the
+// host twin; s: the Stokes component; d_mask: null, or one f32 per pixel that becomes the fourth component.  per_pixel / lds_table: the measured alternatives (WTGPU_DEVELOP_PER_PIXEL, WTGPU_TONEMAP_LDS_TABLE).
 // The launches return a hipError_t.
 constexpr uint32_t kMaxTonemapTable = 1024;   // entries of a colour table
 int develop_launch(const sensor_t& sn, hipStream_t stream, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
                    uint32_t per_pixel, float* d_out);
-int develop_tonemap_launch(const sensor_t& sn, hipStream_t stream, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
-                           const tonemap_args_t& t, uint32_t s, const float* d_mask, uint32_t format, uint32_t lds_table, void* d_out);
-void develop_tonemap_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, const tonemap_args_t& t, uint32_t s,
+int develop_tonemap_launch(const sensor_t& sn, hipStream_t stream, const wtgpu_film_source& film, const tonemap_args_t& t, uint32_t s, const float* d_mask, uint32_t format, uint32_t lds_table, void* d_out);
+void develop_tonemap_host(const sensor_t& sn, const wtgpu_film_source& film, const tonemap_args_t& t, uint32_t s,
                           const float* mask, uint32_t format, uint32_t n_threads, void* out);
 // kernels_stats.hip: film statistics (wtgpu_film_stats_device / wtgpu_film_stats_host; wt/film_stats.h).  Films as wtgpu_render fills them; s: the Stokes
 // component; flags: FS_ABS | FS_LUMINANCE; edges: bins + 1 thresholds (DEVICE for the launch); rec: film_stats_rec_t per plane and hist: [planes][bins],
 // both ZEROED by the caller of the launch (the host twin clears its own); d_sums: kFsMaxPlanes x fs_scratch_len(pixels) doubles.  Two kernels on
 // `stream`; the launch returns a hipError_t.
-int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe, uint32_t s,
-                      uint32_t flags, const float* d_mask, const float* d_edges, uint32_t bins, void* d_rec, unsigned long long* d_hist, double* d_sums);
-void film_stats_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, uint32_t s, uint32_t flags, const float* mask,
+int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const wtgpu_film_source& film, uint32_t s, uint32_t flags, const float* d_mask, const float* d_edges, uint32_t bins, void* d_rec, unsigned long long* d_hist, double* d_sums);
+void film_stats_host(const sensor_t& sn, const wtgpu_film_source& film, uint32_t s, uint32_t flags, const float* mask,
                      const float* edges, uint32_t bins, uint32_t n_threads, void* out_rec, unsigned long long* out_hist);
 // kernels_compare.hip: comparison of two films (wtgpu_film_compare_device / wtgpu_film_compare_host; wt/film_compare.h).  Two sets of films as wtgpu_render fills
 // them (the same pointers twice are fine); s: the Stokes component; flags: FS_ABS | FS_LUMINANCE; eps: finite, > 0.  d_rec: film_compare_rec_t per plane;
 // d_sums: kFsMaxPlanes x kFcSums x fs_scratch_len(pixels) doubles; d_wave: film_rec_wave_bytes(pixels, n_cus) bytes (the polarisation view's too) — none of them has to be
 // cleared; d_diff: null or [height][width][planes] f32.  Two kernels on `stream`; the launch returns a hipError_t.
 size_t film_rec_wave_bytes(uint64_t npix, uint32_t n_cus);
-int film_compare_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a,
-                        const double* b_value, const double* b_weight, const double* b_light, uint64_t spe_b, uint32_t s, uint32_t flags, double eps, const float* d_mask,
+int film_compare_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const wtgpu_film_source& a, const wtgpu_film_source& b, uint32_t s, uint32_t flags, double eps, const float* d_mask,
                         void* d_rec, double* d_sums, void* d_wave, float* d_diff);
-void film_compare_host(const sensor_t& sn, const double* a_value, const double* a_weight, const double* a_light, uint64_t spe_a, const double* b_value,
-                       const double* b_weight, const double* b_light, uint64_t spe_b, uint32_t s, uint32_t flags, double eps, const float* mask, uint32_t n_threads,
+void film_compare_host(const sensor_t& sn, const wtgpu_film_source& a, const wtgpu_film_source& b, uint32_t s, uint32_t flags, double eps, const float* mask, uint32_t n_threads,
                        void* out_rec, float* diff);
 // kernels_polar.hip: the polarisation view of a Stokes film (wtgpu_film_polar_device / wtgpu_film_polar_host; wt/film_polar.h).  Films of a polarimetric
 // sensor as wtgpu_render fills them; flags: FP_LUMINANCE; a: the analyser, the maps' bits and the picture's plane, format and operator.  d_rec:
 // film_polar_rec_t per plane; d_sums: kFsMaxPlanes x kFpSums x fs_scratch_len(pixels) doubles; d_wave: film_rec_wave_bytes(pixels, n_cus) bytes — none of
 // them has to be cleared; d_maps: null or [height][width][planes][a.n_maps] f32; d_picture: null or [height][width][3, or 4 with a mask] in a.format.
 // staged: the measured alternative (WTGPU_FILM_POLAR_STAGED).  Two kernels on `stream`; the launch returns a hipError_t.
-int film_polar_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const double* d_value, const double* d_weight, const double* d_light, uint64_t spe,
-                      uint32_t flags, const film_polar_args_t& a, uint32_t staged, const float* d_mask, void* d_rec, double* d_sums, void* d_wave, float* d_maps,
+int film_polar_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const wtgpu_film_source& film, uint32_t flags, const film_polar_args_t& a, uint32_t staged, const float* d_mask, void* d_rec, double* d_sums, void* d_wave, float* d_maps,
                       void* d_picture);
-void film_polar_host(const sensor_t& sn, const double* value, const double* weight, const double* light, uint64_t spe, uint32_t flags, const film_polar_args_t& a,
+void film_polar_host(const sensor_t& sn, const wtgpu_film_source& film, uint32_t flags, const film_polar_args_t& a,
                      const float* mask, uint32_t n_threads, void* out_rec, float* maps, void* picture);
 // kernels_denoise.hip: the dual-buffer non-local-means filter of two half-films (wtgpu_film_denoise_device / wtgpu_film_denoise_host; wt/film_denoise.h).
 // Two film sets as wtgpu_render fills them (they may be the same memory); a: the radii, k x k, alpha, eps and the patch norm.  d_scratch:

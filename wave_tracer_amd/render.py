@@ -42,14 +42,44 @@ def auto_db_range(scene, films, spe, *, percentiles=(1, 99), mask=None):
     """A dB range for the films as they are: the two percentiles of 10 log10 x over the positive elements (of the pixels where mask > 0), from a
     256-bin histogram between the smallest positive and the largest element — Scene.film_stats_device on torch films on the scene's device
     (nothing but counts crosses to the host), Scene.film_stats_host on numpy films.  An RGB film is judged by its luminance, a polarimetric
-    one by its intensity (Stokes component 0).  Returns (db_min, db_max): tonemap_device's {"op": "dB", "db_range": ...}."""
+    one by its intensity (Stokes component 0).  Returns (db_min, db_max): tonemap_device's {"op": "dB", "db_range": ...}.
+    films may also be ONE developed f32 film (a torch tensor on the scene's device: Scene.film_stats_developed_device, or a numpy array:
+    Scene.film_stats_developed_host) — a denoised film, say; spe is then not read."""
     from . import imageio
-    value, weight, light = films
-    stats_of = scene.film_stats_host if isinstance(value, np.ndarray) else scene.film_stats_device
     lum = scene.spectral_channels == 3
-    stats = stats_of(value, weight, light, spe, scale="dB", range=None, bins=256, luminance=lum, mask=mask)
+    if isinstance(films, (tuple, list)):
+        value, weight, light = films
+        stats_of = scene.film_stats_host if isinstance(value, np.ndarray) else scene.film_stats_device
+        stats = stats_of(value, weight, light, spe, scale="dB", range=None, bins=256, luminance=lum, mask=mask)
+    else:
+        stats_of = scene.film_stats_developed_host if isinstance(films, np.ndarray) else scene.film_stats_developed_device
+        stats = stats_of(films, scale="dB", range=None, bins=256, luminance=lum, mask=mask)
     lo, hi = imageio.percentiles(stats, percentiles)[-1 if lum else 0]
     return float(lo), float(hi)
+
+
+def view(scene, film, tm=None, fmt="u8", mask=None, stokes_component=0):
+    """A picture of a DEVELOPED film where it is: film is a torch f32 tensor [H, W, channels, stokes] on the scene's device (Scene.develop_device's
+    result, a denoiser's "film" or "residual": Scene.tonemap_developed_device, the picture stays there) or a numpy float32 array
+    (Scene.tonemap_developed_host).  tm: None = the scene's own tonemap_spec, else {op, mode, gamma, db_range, table}; a dB operator without a
+    "db_range" takes auto_db_range's of this film (and this mask).  Returns tonemap_device's picture: H x W x 3 (x 4 with a mask) in `fmt`."""
+    if tm is not None and tm.get("op") == "dB" and tm.get("db_range") is None:
+        tm = dict(tm, db_range=auto_db_range(scene, film, None, mask=mask))
+    tonemap = scene.tonemap_developed_host if isinstance(film, np.ndarray) else scene.tonemap_developed_device
+    return tonemap(film, tm=tm, stokes_component=stokes_component, mask=mask, fmt=fmt)
+
+
+_view = view    # (denoise has a keyword of the name)
+
+
+def quality(scene, film, reference_films, reference_spe, **compare_kw):
+    """How far is a DEVELOPED film — a denoised one — from a reference render?  film: a torch f32 tensor on the scene's device or a numpy float32
+    array; reference_films = (value, weight, light), the accumulators of the reference (a long render) where the film is, developed with
+    reference_spe samples per element.  compare_kw: Scene.film_compare_device's (stokes_component, abs, luminance, mask, eps, diff).  Returns that
+    call's dict, film as A and the reference as B: the counts, max_abs / argmax, the sums, and rmse, mean_abs, rel_l2 = ||film - ref|| / ||ref||
+    and rel_mse per plane.  Only the records cross to the host."""
+    compare = scene.film_compare_host if isinstance(film, np.ndarray) else scene.film_compare_device
+    return compare(film, None, reference_films, reference_spe, **compare_kw)
 
 
 def noise_estimate(scene, films_a, films_b, spe, *, mask=None):
@@ -194,14 +224,16 @@ def join_guides(*triples):
     return torch.cat(planes, dim=-1).contiguous(), scales, ids
 
 
-def denoise(scene, films_a, films_b, spe, guides=None, **kw):
+def denoise(scene, films_a, films_b, spe, guides=None, view=None, **kw):
     """Denoises the film that the half-films A and B add up to (render_to_noise(..., halves=True); `spe` samples per element each): films_a / films_b
     are (value, weight, light), torch tensors on the scene's device (Scene.film_denoise_device: everything stays there) or numpy arrays
     (Scene.film_denoise_host).  kw: window, patch, k, alpha, eps, mask, residual (default here: True).  Returns that call's dict — "film", "residual" —
     and "residual_rel" = ||residual|| / ||film|| over the guide planes (Stokes component 0 of each channel) of the pixels where both are finite: an
     ESTIMATE of the relative error that is left, from the difference of the two filtered halves (None with residual=False; 0 for an all-zero film).
     guides: None (the colour-only filter, as before), a (guide, scales, ids) triple as first_hit_guides returns it — arrays where the films are; ids or
-    guide may be None — or True: first_hit_guides(scene) with its untuned defaults, on the host for numpy films."""
+    guide may be None — or True: first_hit_guides(scene) with its untuned defaults, on the host for numpy films.
+    view: None (the dict is as above), True or a dict of view()'s keywords (tm, fmt, mask, stokes_component): adds "picture", view() of the
+    denoised film where it is."""
     on_host = isinstance(films_a[0], np.ndarray)
     if guides is not None and guides is not False:
         guide, scales, ids = first_hit_guides(scene, host=on_host) if guides is True else guides
@@ -218,6 +250,8 @@ def denoise(scene, films_a, films_b, spe, guides=None, **kw):
             ok = torch.isfinite(film).all(dim=-1) & torch.isfinite(res).all(dim=-1)
             num, den = float((res[ok].double() ** 2).sum()), float((film[ok].double() ** 2).sum())
         out["residual_rel"] = float(np.sqrt(num / den)) if den > 0 else 0.0
+    if view is not None and view is not False:
+        out["picture"] = _view(scene, out["film"], **({} if view is True else view))
     return out
 
 
