@@ -566,6 +566,42 @@ int wtgpu_film_polar_source_device(wtgpu_scene* scene, void* stream, const wtgpu
 int wtgpu_film_polar_source_host(const wtgpu_scene* scene, const wtgpu_film_source* film, const wtgpu_film_polar_spec* spec, const float* mask, uint32_t n_threads,
                                  wtgpu_film_polar* out, float* maps, void* picture);
 
+/* Zonal film statistics: ONE pass over a film under a u32 label plane that keeps a statistics record per (zone, plane) — received power under line
+ * of sight against without it, per best-server cell (line_of_sight's NEAREST), per distance ring, per shape or material under a camera pixel
+ * (first_hit's ids), per block of cells — where a masked wtgpu_film_stats call per class would take one pass each.
+ *   elements, planes, members   the film statistics' on either kind of source: the film's channels (+ 1 with flag 2 LUMINANCE), flag 1 ABS, mask > 0.
+ *   zone      zones[height][width] u32: a member pixel with zones[p] < n_zones belongs to that zone; any other member pixel (0xFFFFFFFF, the id
+ *             maps' "no hit", included) to none and is counted once in *n_outside.  1 <= n_zones <= 65536.
+ *   record    out[n_zones][planes]: n members; the film statistics' classes against the same edge table (wtgpu_film_stats_edges of the spec's
+ *             scale, bins, lo, hi); n_inf counts the infinite elements (also counted as negative or above); min / max over the elements that are
+ *             not NaN (NaN if there is none; -0 sorts below +0).  hist[n_zones][planes][bins]; n_zones x bins <= 2^20.
+ *   sum       over the zone's FINITE elements: the exact real sum rounded once to the nearest f64 (ties to even; +0.0 where it is zero) — not the
+ *             film statistics' pairwise sum.  It does not depend on the order of the additions, so device and host agree on every field bit for
+ *             bit, and it is what Python's math.fsum gives.
+ *   paint     optional: [height][width][planes] f32, every pixel painted with (float)(sum / (double)(n - n_nan - n_inf)) of its zone — the zone means
+ *             as a developed film, which the tonemap calls show; 0 for a pixel the mask excludes, one outside every zone, or a zone without a
+ *             finite element.
+ * Errors (WTGPU_ERR_INVALID with a message): everything the film statistics refuse, in their words; n_zones of 0 or above 65536; n_zones x bins
+ * above 2^20; zones, out or n_outside NULL; hist NULL with bins > 0; a film of 2^31 pixels or more. */
+typedef struct wtgpu_film_zonal_spec {
+    uint32_t stokes_component, scale /* 0 linear, 1 dB */, bins /* 0 .. 4096 */, flags /* 1 ABS, 2 LUMINANCE */, n_zones /* 1 .. 65536 */;
+    float lo, hi;
+} wtgpu_film_zonal_spec;
+typedef struct wtgpu_film_zonal {
+    uint64_t n, n_nan, n_inf, n_negative, n_zero, n_below, n_above;
+    float min, max;
+    double sum;
+} wtgpu_film_zonal;
+/* On the device, on `stream`: one pass over the film and d_zones (DEVICE; d_mask and d_paint: DEVICE, each may be NULL), two small kernels and the
+ * copy of the result, for which the call waits: out, hist (may be NULL if bins == 0) and n_outside are HOST memory.  Needs an uploaded scene
+ * (WTGPU_ERR_INVALID otherwise); its scratch memory is sized by the call, grown when a later call needs more and freed with the scene; touches
+ * neither films nor counters. */
+int wtgpu_film_zonal_device(wtgpu_scene* scene, void* stream, const wtgpu_film_source* film, const wtgpu_film_zonal_spec* spec, const uint32_t* d_zones,
+                            const float* d_mask, wtgpu_film_zonal* out, uint64_t* hist, uint64_t* n_outside, float* d_paint);
+/* The same on `n_threads` host threads (0: all cores) from HOST memory; the result does not depend on n_threads.  No device needed. */
+int wtgpu_film_zonal_host(const wtgpu_scene* scene, const wtgpu_film_source* film, const wtgpu_film_zonal_spec* spec, const uint32_t* zones, const float* mask,
+                          uint32_t n_threads, wtgpu_film_zonal* out, uint64_t* hist, uint64_t* n_outside, float* paint);
+
 /* Denoising a film from its two half-films A and B (two renders of disjoint sample ranges, as render_to_noise keeps them) without the films leaving
  * the device: the dual-buffer non-local-means filter of Rousselle, Knaus and Zwicker 2012 — the weights that filter one half are computed from the
  * other, the per-pixel variance comes from (a - b)^2, and the difference of the two filtered halves estimates the error that is left.

@@ -73,6 +73,18 @@ class FilmStats(C.Structure):        # wtgpu_film_stats
                 ("min", C.c_float), ("max", C.c_float), ("min_positive", C.c_float), ("pad", C.c_float), ("sum", C.c_double)]
 
 
+class FilmZonalSpec(C.Structure):    # wtgpu_film_zonal_spec
+    _fields_ = [("stokes_component", C.c_uint32), ("scale", C.c_uint32), ("bins", C.c_uint32), ("flags", C.c_uint32), ("n_zones", C.c_uint32), ("lo", C.c_float),
+                ("hi", C.c_float)]
+
+
+# wtgpu_film_zonal as a numpy record (72 bytes, no padding)
+FILM_ZONAL_FIELDS = [("n", "<u8"), ("n_nan", "<u8"), ("n_inf", "<u8"), ("n_negative", "<u8"), ("n_zero", "<u8"), ("n_below", "<u8"), ("n_above", "<u8"),
+                     ("min", "<f4"), ("max", "<f4"), ("sum", "<f8")]
+FILM_ZONAL_MAX_ZONES = 65536
+FILM_ZONAL_NO_ZONE = 0xFFFFFFFF
+
+
 class FilmCompareSpec(C.Structure):  # wtgpu_film_compare_spec
     _fields_ = [("stokes_component", C.c_uint32), ("flags", C.c_uint32), ("eps", C.c_double)]
 
@@ -167,6 +179,7 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host",
            "wtgpu_tonemap_source_device", "wtgpu_tonemap_source_host", "wtgpu_film_stats_source_device", "wtgpu_film_stats_source_host",
            "wtgpu_film_compare_source_device", "wtgpu_film_compare_source_host", "wtgpu_film_polar_source_device", "wtgpu_film_polar_source_host",
+           "wtgpu_film_zonal_device", "wtgpu_film_zonal_host",
            "wtgpu_film_denoise_device", "wtgpu_film_denoise_host",
            "wtgpu_film_denoise_guided_device", "wtgpu_film_denoise_guided_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
@@ -195,6 +208,25 @@ def dn_exp2_neg(t):
     out = np.zeros(t.shape, dtype=np.float32)
     _check(load_library().wtgpu_test_dn_exp2_neg(t.ctypes.data, t.size, out.ctypes.data))
     return out
+
+
+def fz_sum(x=(), words=None):
+    """Test hook (wtgpu_test_hooks.h): the zonal statistics' exact sum by itself (wt/film_zonal.h) on the host — fz_add of the finite ones of the f32
+    x onto `words` (nine uint64, two's complement; None: zeros), then fz_round -> (the f64, the words as they then are)."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    w = np.zeros(9, np.uint64) if words is None else np.array(words, dtype=np.uint64).reshape(9).copy()
+    out = C.c_double(0.0)
+    _check(load_library().wtgpu_test_fz_sum(w.ctypes.data, x.ctypes.data if x.size else None, x.size, C.byref(out)))
+    return out.value, w
+
+
+def film_zonal_form(scene):
+    """Test hook (wtgpu_test_hooks.h): the form of k_film_zonal the scene's last film_zonal_device call launched — "lds", "global", or None before
+    the first call.  Both forms give the same bits, so only this tells which one ran."""
+    lds = C.c_uint32(0)
+    _check(load_library().wtgpu_test_film_zonal_form(scene.handle, C.byref(lds)))
+    return {0: "global", 1: "lds"}.get(lds.value)
 
 
 def load_library():
@@ -277,6 +309,10 @@ def load_library():
     lib.wtgpu_tonemap_source_host.argtypes = [vp, src, C.POINTER(Tonemap), u32, vp, u32, u32, vp]
     lib.wtgpu_film_stats_source_device.argtypes = [vp, vp, src, C.POINTER(FilmStatsSpec), vp, vp, vp]
     lib.wtgpu_film_stats_source_host.argtypes = [vp, src, C.POINTER(FilmStatsSpec), vp, u32, vp, vp]
+    lib.wtgpu_film_zonal_device.argtypes = [vp, vp, src, C.POINTER(FilmZonalSpec), vp, vp, vp, vp, C.POINTER(u64), vp]
+    lib.wtgpu_film_zonal_host.argtypes = [vp, src, C.POINTER(FilmZonalSpec), vp, vp, u32, vp, vp, C.POINTER(u64), vp]
+    lib.wtgpu_test_fz_sum.argtypes = [vp, vp, u64, C.POINTER(C.c_double)]
+    lib.wtgpu_test_film_zonal_form.argtypes = [vp, C.POINTER(u32)]
     lib.wtgpu_film_compare_source_device.argtypes = [vp, vp, src, src, C.POINTER(FilmCompareSpec), vp, vp, vp]
     lib.wtgpu_film_compare_source_host.argtypes = [vp, src, src, C.POINTER(FilmCompareSpec), vp, u32, vp, vp]
     lib.wtgpu_film_polar_source_device.argtypes = [vp, vp, src, C.POINTER(FilmPolarSpec), vp, vp, vp, vp]
@@ -1053,6 +1089,99 @@ class Scene:
     def film_stats_developed_host(self, film, *, stokes_component=0, scale="dB", range=None, bins=256, abs=False, luminance=False, mask=None, threads=0):
         """film_stats_developed_device's twin on host threads (wtgpu_film_stats_source_host): film a contiguous numpy float32 array of the scene's planes."""
         return self._film_stats_host("film_stats_developed_host", film, 0, stokes_component, scale, range, bins, abs, luminance, mask, threads)
+
+    # ---- zonal film statistics (wtgpu_film_zonal_*; csrc/wt/film_zonal.h) ----
+    def _film_zonal(self, what, xp_zones, call, n_zones, stokes_component, scale, range, bins, abs, luminance, paint):
+        """What film_zonal_device / film_zonal_host share: the spec, the records as a dict.  xp_zones: the zone plane's ids below 0xFFFFFFFF as a
+        callable giving their maximum (or None where there is none); call(spec, rec, hist_or_None, n_outside, planes) runs the pass."""
+        import numpy as np
+        if scale not in FILM_STATS_SCALES:
+            raise ValueError(f"{what}: scale 'dB' or 'linear' expected, got {scale!r}")
+        if n_zones is None:
+            top = xp_zones()
+            n_zones = 1 if top is None else top + 1
+            if n_zones > FILM_ZONAL_MAX_ZONES:
+                raise ValueError(f"{what}: the zone plane holds id {top}: more than {FILM_ZONAL_MAX_ZONES} zones (pass n_zones, or relabel)")
+        planes = self.spectral_channels + (1 if luminance else 0)
+        flags = (FILM_STATS_ABS if abs else 0) | (FILM_STATS_LUMINANCE if luminance else 0)
+        lo, hi = (0.0, 0.0) if range is None else range
+        if range is None and bins:
+            raise ValueError(f"{what}: bins > 0 needs a range (lo, hi) in the scale's units")
+        spec = FilmZonalSpec(int(stokes_component), FILM_STATS_SCALES.index(scale), int(bins), flags, int(n_zones), float(lo), float(hi))
+        zones_ok = 0 < spec.n_zones <= FILM_ZONAL_MAX_ZONES and spec.bins <= FILM_STATS_MAX_BINS and spec.n_zones * spec.bins <= 1 << 20   # (the library says why not)
+        rec = np.zeros((spec.n_zones if zones_ok else 1, max(planes, 1)), dtype=np.dtype(FILM_ZONAL_FIELDS))
+        hist = np.zeros((spec.n_zones, planes, spec.bins) if zones_ok else (0, planes, 0), dtype=np.uint64)
+        n_outside = C.c_uint64(0)
+        extra = call(spec, rec, hist.ctypes.data if hist.size else None, n_outside, planes)
+        out = {name: np.ascontiguousarray(rec[name]) for name, _ in FILM_ZONAL_FIELDS}
+        n_finite = (out["n"] - out["n_nan"] - out["n_inf"]).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["mean"] = out["sum"] / n_finite
+        edges = np.zeros(spec.bins + 1, dtype=np.float32)
+        fs = FilmStatsSpec(spec.stokes_component, spec.scale, spec.bins, spec.flags, spec.lo, spec.hi)
+        _check(load_library().wtgpu_film_stats_edges(C.byref(fs), edges.ctypes.data))
+        out.update(hist=hist, edges=edges, n_outside=int(n_outside.value), n_zones=int(spec.n_zones), scale=scale, range=(float(spec.lo), float(spec.hi)), bins=int(spec.bins))
+        if paint:
+            out["paint"] = extra
+        return out
+
+    def film_zonal_device(self, film, spe, zones, n_zones=None, *, stokes_component=0, abs=False, luminance=False, mask=None, scale="linear", range=None, bins=0,
+                          paint=False, stream=None):
+        """Statistics per zone of a label plane in ONE pass where the films are (wtgpu_film_zonal_device): film is the (value, weight, light) triple of
+        torch f64 tensors on the scene's device, developed with spe samples per element, or one developed f32 film there (spe is then not read), as
+        film_compare_device takes its operands; zones a contiguous torch int32 tensor [H, W] there holding the u32 ids (first_hit's shape /
+        triangle, first_hit_material's, line_of_sight's n_visible / nearest, render.zones_from_edges, render.cell_zones; torch.uint32 is taken too).
+        A pixel with mask > 0 (or any, without a mask) and an id below n_zones belongs to that zone, any other to none (counted in n_outside);
+        n_zones=None: the largest id below 0xFFFFFFFF plus one.  stokes_component / abs / luminance / scale / range / bins: film_stats_device's
+        (range is needed only with bins > 0; without bins, range[0] — default 0 — splits the positive elements into below and above).
+        Returns a dict of numpy arrays [n_zones, planes]: n, n_nan, n_inf, n_negative, n_zero, n_below, n_above (uint64), min, max (float32), sum
+        (float64: the EXACT sum of the zone's finite elements rounded once, math.fsum's) and mean = sum / (n - n_nan - n_inf); hist [n_zones,
+        planes, bins] uint64; edges, n_outside, n_zones, scale, range, bins.  paint=True adds "paint": a torch f32 tensor [H, W, planes] on the
+        device, every pixel holding its zone's mean (0 outside the mask and the zones) — a developed film that render.view shows."""
+        import torch
+        src, dev = self._device_source("film_zonal_device", film, spe or 0, mask)
+        n = self.width * self.height
+        if not (isinstance(zones, torch.Tensor) and zones.is_cuda and zones.device.index == self.device and zones.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
+                and tuple(zones.shape) == (self.height, self.width) and zones.is_contiguous()):
+            raise ValueError(f"film_zonal_device: zones: a contiguous torch.int32 (or uint32) tensor [{self.height}, {self.width}] ({n} ids) on cuda:{self.device} expected")
+        st = self._stream_arg(stream, dev)
+
+        def top():
+            z = zones.view(torch.int32).reshape(-1)
+            z = z[z != -1]
+            if z.numel() == 0:
+                return None
+            return int(z.to(torch.int64).remainder(1 << 32).max().item())
+
+        def call(spec, rec, hist, n_outside, planes):
+            d_paint = torch.empty((self.height, self.width, planes), dtype=torch.float32, device=dev) if paint else None
+            _check(load_library().wtgpu_film_zonal_device(self._h, st, C.byref(src), C.byref(spec), zones.data_ptr(), None if mask is None else mask.data_ptr(),
+                                                          rec.ctypes.data, hist, C.byref(n_outside), None if d_paint is None else d_paint.data_ptr()))
+            return d_paint
+        return self._film_zonal("film_zonal_device", top, call, n_zones, stokes_component, scale, range, bins, abs, luminance, paint)
+
+    def film_zonal_host(self, film, spe, zones, n_zones=None, *, stokes_component=0, abs=False, luminance=False, mask=None, scale="linear", range=None, bins=0,
+                        paint=False, threads=0):
+        """film_zonal_device's twin on host threads from numpy arrays (wtgpu_film_zonal_host; threads 0 = all cores): the same dict, every field bit for
+        bit the device's, "paint" a numpy array.  zones: a contiguous int32 or uint32 array [H, W].  No device needed."""
+        import numpy as np
+        src, m, keep = self._host_source("film_zonal_host", film, spe or 0, mask)
+        if not (isinstance(zones, np.ndarray) and zones.dtype in (np.int32, np.uint32) and zones.shape == (self.height, self.width) and zones.flags.c_contiguous):
+            raise ValueError(f"film_zonal_host: zones: a contiguous int32 or uint32 array [{self.height}, {self.width}] expected")
+
+        def top():
+            z = zones.view(np.uint32)
+            z = z[z != FILM_ZONAL_NO_ZONE]
+            return int(z.max()) if z.size else None
+
+        def call(spec, rec, hist, n_outside, planes):
+            out = np.zeros((self.height, self.width, planes), dtype=np.float32) if paint else None
+            _check(load_library().wtgpu_film_zonal_host(self._h, C.byref(src), C.byref(spec), zones.ctypes.data, None if m is None else m.ctypes.data, int(threads),
+                                                        rec.ctypes.data, hist, C.byref(n_outside), None if out is None else out.ctypes.data))
+            return out
+        out = self._film_zonal("film_zonal_host", top, call, n_zones, stokes_component, scale, range, bins, abs, luminance, paint)
+        del keep
+        return out
 
     # ---- film comparison (wtgpu_film_compare_*; csrc/wt/film_compare.h) ----
     def _film_compare(self, call, stokes_component, abs, luminance, eps):

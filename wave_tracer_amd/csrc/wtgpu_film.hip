@@ -1,5 +1,5 @@
 // wave_tracer_amd — the entry points that read films: develop, the tonemap spec / device / host calls (kernels_develop.hip), film statistics
-// (kernels_stats.hip), film comparison (kernels_compare.hip), the polarisation view (kernels_polar.hip) and the denoiser of two half-films (kernels_denoise.hip); what they check of a film
+// (kernels_stats.hip), zonal film statistics (kernels_zonal.hip), film comparison (kernels_compare.hip), the polarisation view (kernels_polar.hip) and the denoiser of two half-films (kernels_denoise.hip); what they check of a film
 // and keep with the scene between calls.  The four passes that read a film take a wtgpu_film_source — the accumulators or a developed f32 film — and
 // the accumulator-taking entry points are those calls with an accumulator source.
 #include <cstddef>
@@ -7,6 +7,7 @@
 #include "wtgpu_host.h"
 #include "wt/tonemap.h"
 #include "wt/film_stats.h"
+#include "wt/film_zonal.h"
 #include "wt/film_compare.h"
 #include "wt/film_polar.h"
 #include "wt/film_denoise.h"
@@ -252,16 +253,16 @@ int wtgpu_tonemap_host(const wtgpu_scene* s, const double* value, const double* 
 // ---- film statistics (kernels_stats.hip; wt/film_stats.h) -----------------------------------------------------------------------------------
 static_assert(sizeof(wtgpu_film_stats) == sizeof(film_stats_rec_t), "the kernels' record is wtgpu_film_stats");
 // what a spec says by itself, and its edge table
-static int film_stats_edges_for(const wtgpu_film_stats_spec* spec, float* edges) {
-    if (spec->scale > FS_DB) return fail(WTGPU_ERR_INVALID, "film_stats: scale 0 (linear) or 1 (dB) expected");
-    if (spec->flags & ~(FS_ABS | FS_LUMINANCE)) return fail(WTGPU_ERR_INVALID, "film_stats: flags 1 (ABS) and 2 (LUMINANCE) expected");
-    if (spec->bins > kFsMaxBins) return fail(WTGPU_ERR_INVALID, "film_stats: bins " + std::to_string(spec->bins) + " above the " + std::to_string(kFsMaxBins) + " the histogram holds");
-    if (!std::isfinite(spec->lo) || (spec->bins > 0 && !std::isfinite(spec->hi))) return fail(WTGPU_ERR_INVALID, "film_stats: a finite range expected");
-    if (spec->bins > 0 && !(spec->lo < spec->hi)) return fail(WTGPU_ERR_INVALID, "film_stats: lo < hi expected with bins > 0");
+static int film_stats_edges_for(const wtgpu_film_stats_spec* spec, float* edges, const std::string& what = "film_stats") {
+    if (spec->scale > FS_DB) return fail(WTGPU_ERR_INVALID, what + ": scale 0 (linear) or 1 (dB) expected");
+    if (spec->flags & ~(FS_ABS | FS_LUMINANCE)) return fail(WTGPU_ERR_INVALID, what + ": flags 1 (ABS) and 2 (LUMINANCE) expected");
+    if (spec->bins > kFsMaxBins) return fail(WTGPU_ERR_INVALID, what + ": bins " + std::to_string(spec->bins) + " above the " + std::to_string(kFsMaxBins) + " the histogram holds");
+    if (!std::isfinite(spec->lo) || (spec->bins > 0 && !std::isfinite(spec->hi))) return fail(WTGPU_ERR_INVALID, what + ": a finite range expected");
+    if (spec->bins > 0 && !(spec->lo < spec->hi)) return fail(WTGPU_ERR_INVALID, what + ": lo < hi expected with bins > 0");
     for (uint32_t i = 0; i <= spec->bins; ++i) {
         edges[i] = fs_edge(spec->scale, spec->lo, spec->hi, spec->bins, i);
         if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i - 1] < edges[i])))
-            return fail(WTGPU_ERR_INVALID, "film_stats: degenerate edges: edge " + std::to_string(i) + " of " + std::to_string(spec->bins) + " is not above edge " +
+            return fail(WTGPU_ERR_INVALID, what + ": degenerate edges: edge " + std::to_string(i) + " of " + std::to_string(spec->bins) + " is not above edge " +
                                                std::to_string(i ? i - 1 : 0) + " after rounding to f32 (fewer bins or a wider range)");
     }
     return WTGPU_OK;
@@ -324,6 +325,105 @@ int wtgpu_film_stats_host(const wtgpu_scene* s, const double* value, const doubl
     if (!s || !value || !weight || !light || !spec || !out || (!hist && spec->bins > 0)) return fail(WTGPU_ERR_INVALID, "null argument");
     const wtgpu_film_source film = accumulators(value, weight, light, spe);
     return wtgpu_film_stats_source_host(s, &film, spec, mask, n_threads, out, hist);
+}
+
+// ---- zonal film statistics (kernels_zonal.hip; wt/film_zonal.h) ---------------------------------------------------------------------------------
+static_assert(sizeof(wtgpu_film_zonal) == sizeof(film_zonal_rec_t) && offsetof(wtgpu_film_zonal, n_above) == offsetof(film_zonal_rec_t, count) + FZ_ABOVE * 8 &&
+                  offsetof(wtgpu_film_zonal, n_inf) == offsetof(film_zonal_rec_t, count) + FZ_INF * 8 && offsetof(wtgpu_film_zonal, min) == offsetof(film_zonal_rec_t, min) &&
+                  offsetof(wtgpu_film_zonal, sum) == offsetof(film_zonal_rec_t, sum),
+              "the kernels' record is wtgpu_film_zonal");
+// What both entry points check: the film statistics' refusals in their words, then the zones'.  planes: records per zone; edges: the spec's table.
+static int film_zonal_check(const wtgpu_scene* s, const wtgpu_film_source* film, const wtgpu_film_zonal_spec* spec, const uint32_t* zones, const wtgpu_film_zonal* out,
+                            const uint64_t* hist, const uint64_t* n_outside, uint32_t& planes, float* edges) {
+    if (!s || !film || !spec) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (!zones) return fail(WTGPU_ERR_INVALID, "film_zonal: a zone plane expected (zones is NULL)");
+    if (!out || !n_outside) return fail(WTGPU_ERR_INVALID, "film_zonal: out and n_outside expected (one of them is NULL)");
+    if (const int rc = film_source_check("film_zonal", "", film)) return rc;
+    const wtgpu_film_stats_spec fs{spec->stokes_component, spec->scale, spec->bins, spec->flags, spec->lo, spec->hi};
+    if (const int rc = film_stats_edges_for(&fs, edges, "film_zonal")) return rc;
+    if (const int rc = film_planes_for(s, "film_zonal", spec->stokes_component, spec->flags, planes)) return rc;
+    if (spec->n_zones == 0 || spec->n_zones > kFzMaxZones)
+        return fail(WTGPU_ERR_INVALID, "film_zonal: n_zones " + std::to_string(spec->n_zones) + " out of range (1 .. " + std::to_string(kFzMaxZones) + ")");
+    if ((uint64_t)spec->n_zones * spec->bins > kFzMaxZoneBins)
+        return fail(WTGPU_ERR_INVALID, "film_zonal: n_zones x bins = " + std::to_string((uint64_t)spec->n_zones * spec->bins) + " above the " + std::to_string(kFzMaxZoneBins) +
+                                           " the histogram holds");
+    if ((uint64_t)s->host.sensor.width * s->host.sensor.height >= kFzMaxPixels)
+        return fail(WTGPU_ERR_INVALID, "film_zonal: a film of 2^31 pixels or more (a word of the exact sum could overflow)");
+    if (!hist && spec->bins > 0) return fail(WTGPU_ERR_INVALID, "film_zonal: bins > 0 without a histogram (hist is NULL)");
+    return WTGPU_OK;
+}
+
+int wtgpu_film_zonal_device(wtgpu_scene* s, void* stream_, const wtgpu_film_source* film, const wtgpu_film_zonal_spec* spec, const uint32_t* d_zones, const float* d_mask,
+                            wtgpu_film_zonal* out, uint64_t* hist, uint64_t* n_outside, float* d_paint) {
+    uint32_t planes = 0;
+    float edges[kFsMaxBins + 1];
+    if (const int rc = film_zonal_check(s, film, spec, d_zones, out, hist, n_outside, planes, edges)) return rc;
+    return film_on_device(s, stream_, "film_zonal", [&](hipStream_t stream, uint64_t) -> int {
+        // the block: records | edge table | histogram | n_outside | slots.  The first four come back through the pinned copy (which also carries the
+        // edge table to the device); everything behind the edge table is cleared.  The call waits for its result, so the block is free again when
+        // it returns.
+        const size_t n_slots = (size_t)spec->n_zones * planes, rec_bytes = n_slots * sizeof(film_zonal_rec_t), edge_bytes = (((size_t)spec->bins + 2) & ~(size_t)1) * sizeof(float);
+        const size_t hist_bytes = n_slots * spec->bins * sizeof(uint64_t), off_edge = rec_bytes, off_hist = off_edge + edge_bytes, off_outside = off_hist + hist_bytes;
+        const size_t off_slots = off_outside + sizeof(uint64_t), total = off_slots + n_slots * sizeof(film_zonal_slot_t);
+        if (s->d_zonal_bytes < total) {
+            unsigned char* old = s->d_zonal;
+            s->d_zonal = nullptr, s->d_zonal_bytes = 0;   // (reset first: a failed free leaves nothing behind for the next call)
+            if (old) HIP_CHECK(hipFree(old));
+            void* p = nullptr;
+            if (const hipError_t e = hipMalloc(&p, total)) return fail(WTGPU_ERR_OOM, std::string("hipMalloc of ") + std::to_string(total) + " bytes: " + hipGetErrorString(e));
+            s->d_zonal = static_cast<unsigned char*>(p), s->d_zonal_bytes = total;
+        }
+        if (s->h_zonal_bytes < off_slots) {
+            unsigned char* old = s->h_zonal;
+            s->h_zonal = nullptr, s->h_zonal_bytes = 0;
+            if (old) HIP_CHECK(hipHostFree(old));
+            HIP_CHECK(hipHostMalloc((void**)&s->h_zonal, off_slots, hipHostMallocDefault));
+            s->h_zonal_bytes = off_slots;
+        }
+        unsigned char* d = s->d_zonal;
+        std::memcpy(s->h_zonal + off_edge, edges, (spec->bins + 1) * sizeof(float));
+        HIP_CHECK(hipMemcpyAsync(d + off_edge, s->h_zonal + off_edge, edge_bytes, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemsetAsync(d + off_hist, 0, total - off_hist, stream));
+        // the LDS form wherever its table fits a launch, unless WTGPU_FILM_ZONAL_LDS=0
+        const uint32_t lds = s->knobs.film_zonal_lds && film_zonal_lds_fits(spec->n_zones, planes, spec->bins) ? 1u : 0u;
+        s->zonal_last_lds = lds;
+        const int e = film_zonal_launch(s->host.sensor, stream, s->n_cus, *film, spec->stokes_component, spec->flags, d_zones, d_mask, reinterpret_cast<const float*>(d + off_edge),
+                                        spec->bins, spec->n_zones, lds, s->knobs.film_zonal_blocks, d + off_slots,
+                                        reinterpret_cast<unsigned long long*>(d + off_hist), reinterpret_cast<unsigned long long*>(d + off_outside), d, d_paint);
+        if (e) return fail(WTGPU_ERR_HIP, std::string("k_film_zonal: ") + hipGetErrorString((hipError_t)e));
+        HIP_CHECK(hipMemcpyAsync(s->h_zonal, d, off_slots, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        std::memcpy(out, s->h_zonal, rec_bytes);
+        if (spec->bins) std::memcpy(hist, s->h_zonal + off_hist, hist_bytes);
+        std::memcpy(n_outside, s->h_zonal + off_outside, sizeof(uint64_t));
+        return WTGPU_OK;
+    });
+}
+int wtgpu_film_zonal_host(const wtgpu_scene* s, const wtgpu_film_source* film, const wtgpu_film_zonal_spec* spec, const uint32_t* zones, const float* mask, uint32_t n_threads,
+                          wtgpu_film_zonal* out, uint64_t* hist, uint64_t* n_outside, float* paint) {
+    uint32_t planes = 0;
+    float edges[kFsMaxBins + 1];
+    if (const int rc = film_zonal_check(s, film, spec, zones, out, hist, n_outside, planes, edges)) return rc;
+    return film_on_host([&] {
+        film_zonal_host(s->host.sensor, *film, spec->stokes_component, spec->flags, zones, mask, edges, spec->bins, spec->n_zones, n_threads, out,
+                        reinterpret_cast<unsigned long long*>(hist), reinterpret_cast<unsigned long long*>(n_outside), paint);
+    });
+}
+int wtgpu_test_film_zonal_form(const wtgpu_scene* s, uint32_t* lds) {
+    if (!s || !lds) return fail(WTGPU_ERR_INVALID, "null argument");
+    *lds = s->zonal_last_lds;
+    return WTGPU_OK;
+}
+// the exact sum by itself (tests): words[9] += the addends of x[n], finite elements only; *out = fz_round(words)
+int wtgpu_test_fz_sum(uint64_t* words, const float* x, uint64_t n, double* out) {
+    if (!words || (!x && n) || !out) return fail(WTGPU_ERR_INVALID, "null argument");
+    unsigned long long w[kFzWords];
+    for (uint32_t k = 0; k < kFzWords; ++k) w[k] = words[k];
+    for (uint64_t i = 0; i < n; ++i)
+        if (fz_finite(x[i])) fz_add(w, x[i]);
+    for (uint32_t k = 0; k < kFzWords; ++k) words[k] = w[k];
+    *out = fz_round(w);
+    return WTGPU_OK;
 }
 
 // ---- film comparison (kernels_compare.hip; wt/film_compare.h) -------------------------------------------------------------------------------

@@ -119,6 +119,12 @@ struct wtgpu_scene {
     float* h_tm_table = nullptr;
     hipEvent_t ev_tm = nullptr;
     film_scratch_t fs, fc, fp;           // wtgpu_film_stats_device, wtgpu_film_compare_device, wtgpu_film_polar_device
+    // wtgpu_film_zonal_device: records, edge table, histogram, n_outside and the accumulating slots on the device, all but the slots pinned on the host;
+    // sized by the call and grown when a later call needs more
+    unsigned char* d_zonal = nullptr;
+    unsigned char* h_zonal = nullptr;
+    size_t d_zonal_bytes = 0, h_zonal_bytes = 0;
+    uint32_t zonal_last_lds = 0xFFFFFFFFu;   // the form the last wtgpu_film_zonal_device call took: 1 LDS, 0 global (wtgpu_test_film_zonal_form)
     float* d_denoise = nullptr;          // wtgpu_film_denoise_device: the developed half-films, their variance and what one direction leaves for the other
     // WTGPU_TRACE_AB (diagnostic, tests/test_gpu_traversal.py): accumulated over the replayed rounds — milliseconds of k_trace_refill / k_trace_sm on the
     // same queue, words of their outputs that differ (traversal records + triangle lists + heavy-queue checksums), walks replayed

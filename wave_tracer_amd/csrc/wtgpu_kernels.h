@@ -18,6 +18,7 @@
 //                       their grids, a group's share of a ballot, the exchange through the LDS of the stacks and its sums in sample order, the host twins' loop
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
+//   kernels_zonal.hip   k_film_zonal / k_film_zonal_finish / k_film_zonal_paint: a statistics record per (zone, plane) of a film under a label plane (not part of a render)
 //   kernels_compare.hip k_film_compare (+ k_film_finish): difference statistics of two films (not part of a render)
 //   kernels_polar.hip   k_film_polar (+ k_film_finish): polarisation maps, Stokes sums and false-colour picture of a Stokes film (not part of a render)
 //   kernels_denoise.hip k_denoise_prepare / _variance / k_denoise_filter: the dual-buffer non-local-means filter of two half-films (not part of a render)
@@ -652,6 +653,17 @@ void develop_tonemap_host(const sensor_t& sn, const wtgpu_film_source& film, con
 int film_stats_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const wtgpu_film_source& film, uint32_t s, uint32_t flags, const float* d_mask, const float* d_edges, uint32_t bins, void* d_rec, unsigned long long* d_hist, double* d_sums);
 void film_stats_host(const sensor_t& sn, const wtgpu_film_source& film, uint32_t s, uint32_t flags, const float* mask,
                      const float* edges, uint32_t bins, uint32_t n_threads, void* out_rec, unsigned long long* out_hist);
+// kernels_zonal.hip: zonal film statistics (wtgpu_film_zonal_device / wtgpu_film_zonal_host; wt/film_zonal.h).  A film source as above; d_zones: [height][width]
+// u32; edges as for the statistics; n_zones: 1 .. 65536.  lds_form: 1 the LDS form (only where film_zonal_lds_fits), 0 the global form; max_blocks: WTGPU_FILM_ZONAL_BLOCKS.  d_slots: film_zonal_slot_t per
+// (zone, plane), d_hist: [n_zones][planes][bins] and d_outside: one count, all three ZEROED by the caller of the launch; d_rec: film_zonal_rec_t per
+// (zone, plane), every field written; d_paint: null or [height][width][planes] f32.  Two or three kernels on `stream`; the launch returns a hipError_t.
+// film_zonal_lds_fits: whether the LDS form's table of a call fits the 64 KB a launch may ask for.
+bool film_zonal_lds_fits(uint32_t n_zones, uint32_t planes, uint32_t bins);
+int film_zonal_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, const wtgpu_film_source& film, uint32_t s, uint32_t flags, const uint32_t* d_zones, const float* d_mask,
+                      const float* d_edges, uint32_t bins, uint32_t n_zones, uint32_t lds_form, uint32_t max_blocks, void* d_slots, unsigned long long* d_hist,
+                      unsigned long long* d_outside, void* d_rec, float* d_paint);
+void film_zonal_host(const sensor_t& sn, const wtgpu_film_source& film, uint32_t s, uint32_t flags, const uint32_t* zones, const float* mask, const float* edges, uint32_t bins,
+                     uint32_t n_zones, uint32_t n_threads, void* out_rec, unsigned long long* out_hist, unsigned long long* out_outside, float* paint);
 // kernels_compare.hip: comparison of two films (wtgpu_film_compare_device / wtgpu_film_compare_host; wt/film_compare.h).  Two sets of films as wtgpu_render fills
 // them (the same pointers twice are fine); s: the Stokes component; flags: FS_ABS | FS_LUMINANCE; eps: finite, > 0.  d_rec: film_compare_rec_t per plane;
 // d_sums: kFsMaxPlanes x kFcSums x fs_scratch_len(pixels) doubles; d_wave: film_rec_wave_bytes(pixels, n_cus) bytes (the polarisation view's too) — none of them has to be

@@ -75,6 +75,8 @@ const knob_t kKnobs[] = {
     {"WTGPU_FILM_DENOISE_GUIDE_LDS", K(film_denoise_guide_lds), KNOB_U32, 0, 0, 1, "k_denoise_filter, guided: 1 the guide planes of the candidate square go into LDS beside the halo where the sum fits 64 KB (from global memory where it does not); 0 every lane reads g(q) from global memory where it reads x(q) (A/B: tools/bench_film_denoise_guided.py; the results do not depend on it)"},
     {"WTGPU_FIRST_HIT_PER_SAMPLE", K(first_hit_per_sample), KNOB_U32, 1, 0, 1, "k_first_hit: 1 one lane per sample where a pixel's samples fit a wavefront (k_first_hit_wave: the lanes of a pixel exchange their samples through LDS, lane j sums float j in sample order); 0 one lane per pixel always (A/B: tools/bench_first_hit.py; the results do not depend on it); k_first_hit_material / k_first_hit_material_wave follow it too (tools/bench_first_hit_material.py)"},
     {"WTGPU_LOS_PER_SAMPLE", K(los_per_sample), KNOB_U32, 1, 0, 1, "wtgpu_line_of_sight: 1 one lane per (element, sample) where the sensor's own elements are sampled and an element's samples fit a wavefront (k_los_sample: the lanes walk the emitters together and exchange their samples through LDS, lane j sums float j in sample order); 0 one lane per (element, emitter) always (k_los_pair) (A/B: tools/bench_los.py; the results do not depend on it)"},
+    {"WTGPU_FILM_ZONAL_LDS", K(film_zonal_lds), KNOB_U32, 1, 0, 1, "k_film_zonal: 1 every block accumulates in a table in LDS wherever the table of n_zones x planes entries fits the 64 KB a launch may ask for, and flushes it once (measured 7 to 165 times faster wherever it fits); 0 the atomics go straight to global memory always (A/B: tools/bench_film_zonal.py; both forms are exact, the results do not depend on it)"},
+    {"WTGPU_FILM_ZONAL_BLOCKS", K(film_zonal_blocks), KNOB_U32, 0, 0, kU32, "k_film_zonal: n > 0 caps the grid at n blocks (the tests: one wavefront takes many chunks of a small film); 0 the film statistics' rule (kernels_film.h: film_grid_blocks); the results do not depend on it"},
     // ---- diagnostics and bring-up aids
     {"WTGPU_DEBUG_STAGE", K(dbg_stage), KNOB_INT, 1 << 30, INT_MIN, INT_MAX, "bring-up aid: stops launching the round kernels after stage n (INVALID RESULTS)"},
     {"WTGPU_HOST_PROF", K(host_prof), KNOB_PRESENT, 0, 0, 1, "set: host time spent inside each kind of launch call, printed per render call"},

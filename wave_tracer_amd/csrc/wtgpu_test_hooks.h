@@ -60,6 +60,12 @@ int wtgpu_test_connect_class_order(uint32_t* keys, uint32_t cap, uint32_t* n_key
 int wtgpu_test_connect_class_items(wtgpu_scene* s, uint32_t slice, uint32_t* table, uint32_t* items, uint32_t items_cap, uint32_t* n_items);
 /* out[i] = dn_exp2_neg(t[i]) of wt/film_denoise.h (2^-t for t >= 0, the film denoiser's weight function), on the host: for the test of its bound. */
 int wtgpu_test_dn_exp2_neg(const float* t, uint64_t n, float* out);
+/* The zonal statistics' exact sum by itself (wt/film_zonal.h), on the host: fz_add of the finite ones of x[n] onto words[9] (left as they then are),
+ * *out = fz_round(words).  n = 0 rounds hand-made words. */
+int wtgpu_test_fz_sum(uint64_t* words, const float* x, uint64_t n, double* out);
+/* The form of k_film_zonal that the scene's last wtgpu_film_zonal_device call launched: *lds = 1 the LDS form, 0 the global form, 0xFFFFFFFF no call
+ * yet.  Both forms give the same bits, so only this tells a test which one ran. */
+int wtgpu_test_film_zonal_form(const wtgpu_scene* s, uint32_t* lds);
 #ifdef __cplusplus
 }
 #endif

@@ -322,6 +322,11 @@ void release_device(wtgpu_scene* s) {
     film_scratch_free(s->fc);
     film_scratch_free(s->fp);
     s->d_denoise = nullptr;      // (freed with dev_allocs)
+    if (s->d_zonal) (void)hipFree(s->d_zonal);   // (its own allocation: it grows with the calls)
+    if (s->h_zonal) (void)hipHostFree(s->h_zonal);
+    s->d_zonal = s->h_zonal = nullptr;
+    s->d_zonal_bytes = s->h_zonal_bytes = 0;
+    s->zonal_last_lds = 0xFFFFFFFFu;
     s->uploaded = false;
 }
 

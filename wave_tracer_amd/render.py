@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from .api import Scene, load_library, _check
+from .api import FILM_ZONAL_NO_ZONE, Scene, load_library, _check
 
 
 def alloc_films(scene, device):
@@ -152,6 +152,79 @@ def los_masks(scene, emitter=None, samples=0, seed=1, host=False):
         return los, np.float32(1) - los
     los = seen.float().contiguous()
     return los, (1.0 - los).contiguous()
+
+
+NO_ZONE = FILM_ZONAL_NO_ZONE    # the id of a pixel that belongs to no zone (the id maps' "no hit")
+
+
+def zones_from_edges(plane, edges):
+    """A zone plane from a plane of values: zone i where edges[i] <= x < edges[i + 1] (edges: strictly increasing, compared in the plane's own
+    f32), 0xFFFFFFFF elsewhere — below the first edge, from the last edge on, NaN.  plane: a torch tensor [H, W] (the zones stay on its device, as
+    int32 holding the u32 bits) or a numpy array (uint32).  Distance rings for the path-loss exponent come from line_of_sight's DISTANCE of one
+    emitter or first_hit's DEPTH."""
+    e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1)
+    if e.size < 2 or not (np.diff(e.astype(np.float64)) > 0).all():
+        raise ValueError("zones_from_edges: at least two strictly increasing edges (as float32) expected")
+    if isinstance(plane, np.ndarray):
+        x = plane.astype(np.float32, copy=False)
+        inside = (x >= e[0]) & (x < e[-1])       # (False for a NaN)
+        z = np.searchsorted(e, np.where(inside, x, e[0]), side="right") - 1
+        return np.ascontiguousarray(np.where(inside, z, NO_ZONE).astype(np.uint32))
+    import torch
+    x = plane.float()
+    te = torch.from_numpy(e).to(x.device)
+    inside = (x >= te[0]) & (x < te[-1])
+    z = torch.searchsorted(te, torch.where(inside, x, te[0]).contiguous(), right=True) - 1
+    return torch.where(inside, z, torch.full_like(z, -1)).to(torch.int32).contiguous()
+
+
+def cell_zones(height, width, cell):
+    """Block cells as a zone plane (numpy uint32 [height, width]): cells of `cell` x `cell` pixels (the last of a row or column may be cut), numbered
+    row-major — zone (y // cell) * ceil(width / cell) + x // cell — and their number."""
+    cell = int(cell)
+    if cell < 1 or height < 1 or width < 1:
+        raise ValueError("cell_zones: positive sizes expected")
+    per_row = -(-width // cell)
+    yy, xx = np.mgrid[0:height, 0:width]
+    return np.ascontiguousarray(((yy // cell) * per_row + xx // cell).astype(np.uint32)), per_row * -(-height // cell)
+
+
+class ZonalStats(dict):
+    """film_zonal_device's dict with percentiles(q) per zone."""
+
+    def percentiles(self, q):
+        """imageio.percentiles of every zone's histogram, in the histogram's own scale: [n_zones, planes] for one q, [n_zones, planes, len(q)] else."""
+        from . import imageio
+        if not self["bins"]:
+            raise ValueError("zonal: percentiles need a histogram (bins > 0 and a range)")
+        return np.stack([imageio.percentiles({"hist": self["hist"][z], "range": self["range"], "n_below": self["n_below"][z], "n_above": self["n_above"][z]}, q)
+                         for z in range(self["n_zones"])])
+
+
+def zonal(scene, films, spe, zones, n_zones=None, **kw):
+    """Statistics per zone of a label plane in one pass over the films where they are: films = (value, weight, light) or one developed f32 film, torch
+    tensors on the scene's device with zones there (Scene.film_zonal_device; a scene that is not uploaded yet is uploaded to the films' device) or
+    numpy arrays (Scene.film_zonal_host).  kw: stokes_component, abs, luminance, mask, scale, range, bins, paint.  Returns that call's dict, which
+    also answers percentiles(q) per zone from the histograms."""
+    first = films[0] if isinstance(films, (tuple, list)) else films
+    if isinstance(first, np.ndarray):
+        return ZonalStats(scene.film_zonal_host(films, spe, zones, n_zones, **kw))
+    if scene.device is None:
+        scene.upload(first.device.index or 0)
+    return ZonalStats(scene.film_zonal_device(films, spe, zones, n_zones, **kw))
+
+
+def coverage_by_los(scene, films, spe, emitter=None, samples=0, seed=1, **kw):
+    """Received power without and under line of sight in ONE pass: zonal() over two zones, 0 = no line of sight and 1 = line of sight, from
+    Scene.line_of_sight's n_visible > 0 (emitter=None: any emitter that is not an area emitter) or one emitter's visible > 0, computed where the
+    films are (numpy films: the host twins).  kw: zonal()'s."""
+    first = films[0] if isinstance(films, (tuple, list)) else films
+    host = isinstance(first, np.ndarray)
+    if not host and scene.device is None:
+        scene.upload(first.device.index or 0)
+    los, _ = los_masks(scene, emitter, samples, seed, host=host)
+    zones = np.ascontiguousarray(los > 0, dtype=np.uint32) if host else (los > 0).int().contiguous()
+    return zonal(scene, films, spe, zones, 2, **kw)
 
 
 SHADOW_GUIDE_SCALE = 1.0 / FIRST_HIT_GUIDE_KF ** 2   # shadow_guides' default scale for every plane: first_hit_guides' 2.78.  UNTUNED.
