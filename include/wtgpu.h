@@ -602,6 +602,42 @@ int wtgpu_film_zonal_device(wtgpu_scene* scene, void* stream, const wtgpu_film_s
 int wtgpu_film_zonal_host(const wtgpu_scene* scene, const wtgpu_film_source* film, const wtgpu_film_zonal_spec* spec, const uint32_t* zones, const float* mask,
                           uint32_t n_threads, wtgpu_film_zonal* out, uint64_t* hist, uint64_t* n_outside, float* paint);
 
+/* Connected segments of a label plane: which REGION a pixel lies in, where the id maps and zone planes say which class — the coverage holes below
+ * a threshold, the shadow behind one building (line_of_sight's n_visible == 0), one visible fragment of a shape.  The result is canonical: it
+ * depends on no order of execution and holds no floating-point number, so device and host agree bit for bit.
+ *   inputs    classes[height][width] u32 or NULL (every pixel has class 0); mask[height][width] f32 or NULL.
+ *   member    pixel p is a member iff (mask == NULL or mask[p] > 0 — a NaN is not) and classes[p] != 0xFFFFFFFF (the id maps' "no hit").
+ *   link      two members are linked iff they have the same class and are neighbours: the 4 edge neighbours, with flag 1 DIAGONAL the 4 corner
+ *             neighbours as well.  Rows do not wrap.
+ *   segment   a connected component of the link graph.  first: its smallest row-major pixel index; area: its pixel count; klass: its class;
+ *             x0, y0, x1, y1: its inclusive bounding box; sum_x, sum_y: the sums of its pixels' coordinates (the centroid is sum / area).
+ *   kept      a segment is kept iff area >= max(min_area, 1); kept segments are numbered 0 .. K - 1 in ascending `first`.
+ *   segments  [height][width] u32: the number of the pixel's segment; 0xFFFFFFFF for a pixel that is no member or whose segment was dropped.
+ *             wtgpu_film_zonal_* takes this plane as `zones` as it is.
+ *   info      n_segments = K, n_dropped (segments), n_members (pixels), n_dropped_pixels (members of dropped segments).
+ *   records   optional, HOST memory: the first min(K, max_records) kept segments; max_records may be 0 with records == NULL.
+ * Errors (WTGPU_ERR_INVALID with a message opened by "film_segments:"): segments or info NULL; records NULL with max_records > 0; flags other than
+ * 0 / 1; a sensor of 2^31 pixels or more; the device call without an upload. */
+typedef struct wtgpu_film_segments_spec {
+    uint32_t flags /* 1 DIAGONAL */, min_area, max_records, pad;
+} wtgpu_film_segments_spec;
+typedef struct wtgpu_film_segments_info {
+    uint64_t n_segments, n_dropped, n_members, n_dropped_pixels;
+} wtgpu_film_segments_info;
+typedef struct wtgpu_film_segment {
+    uint32_t klass, area, first, x0, y0, x1, y1, pad;
+    uint64_t sum_x, sum_y;
+} wtgpu_film_segment;
+/* On the device, on `stream`: d_classes, d_mask (each may be NULL) and d_segments are DEVICE memory; info and records are HOST memory, and the call
+ * waits for them.  A union-find in global memory (csrc/kernels_segments.hip); every one of its loops carries a step bound, and a call in which one
+ * was hit returns WTGPU_ERR_HIP with a message, d_segments then holding nothing to be read.  Needs an uploaded scene; its scratch memory is
+ * sized by the call, grown when a later call needs more and freed with the scene; touches neither films nor counters. */
+int wtgpu_film_segments_device(wtgpu_scene* scene, void* stream, const wtgpu_film_segments_spec* spec, const uint32_t* d_classes, const float* d_mask,
+                               uint32_t* d_segments, wtgpu_film_segments_info* info, wtgpu_film_segment* records);
+/* The same from HOST memory; n_threads is accepted (0: all cores) and the result does not depend on it.  No device needed. */
+int wtgpu_film_segments_host(const wtgpu_scene* scene, const wtgpu_film_segments_spec* spec, const uint32_t* classes, const float* mask, uint32_t n_threads,
+                             uint32_t* segments, wtgpu_film_segments_info* info, wtgpu_film_segment* records);
+
 /* Denoising a film from its two half-films A and B (two renders of disjoint sample ranges, as render_to_noise keeps them) without the films leaving
  * the device: the dual-buffer non-local-means filter of Rousselle, Knaus and Zwicker 2012 — the weights that filter one half are computed from the
  * other, the per-pixel variance comes from (a - b)^2, and the difference of the two filtered halves estimates the error that is left.

@@ -85,6 +85,20 @@ FILM_ZONAL_MAX_ZONES = 65536
 FILM_ZONAL_NO_ZONE = 0xFFFFFFFF
 
 
+class FilmSegmentsSpec(C.Structure):  # wtgpu_film_segments_spec
+    _fields_ = [("flags", C.c_uint32), ("min_area", C.c_uint32), ("max_records", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class FilmSegmentsInfo(C.Structure):  # wtgpu_film_segments_info
+    _fields_ = [("n_segments", C.c_uint64), ("n_dropped", C.c_uint64), ("n_members", C.c_uint64), ("n_dropped_pixels", C.c_uint64)]
+
+
+# wtgpu_film_segment as a numpy record (48 bytes, no padding)
+FILM_SEGMENT_FIELDS = [("klass", "<u4"), ("area", "<u4"), ("first", "<u4"), ("x0", "<u4"), ("y0", "<u4"), ("x1", "<u4"), ("y1", "<u4"), ("pad", "<u4"),
+                       ("sum_x", "<u8"), ("sum_y", "<u8")]
+FILM_SEGMENTS_DIAGONAL = 1
+
+
 class FilmCompareSpec(C.Structure):  # wtgpu_film_compare_spec
     _fields_ = [("stokes_component", C.c_uint32), ("flags", C.c_uint32), ("eps", C.c_double)]
 
@@ -179,7 +193,7 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_film_compare_device", "wtgpu_film_compare_host", "wtgpu_film_polar_device", "wtgpu_film_polar_host",
            "wtgpu_tonemap_source_device", "wtgpu_tonemap_source_host", "wtgpu_film_stats_source_device", "wtgpu_film_stats_source_host",
            "wtgpu_film_compare_source_device", "wtgpu_film_compare_source_host", "wtgpu_film_polar_source_device", "wtgpu_film_polar_source_host",
-           "wtgpu_film_zonal_device", "wtgpu_film_zonal_host",
+           "wtgpu_film_zonal_device", "wtgpu_film_zonal_host", "wtgpu_film_segments_device", "wtgpu_film_segments_host",
            "wtgpu_film_denoise_device", "wtgpu_film_denoise_host",
            "wtgpu_film_denoise_guided_device", "wtgpu_film_denoise_guided_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
@@ -227,6 +241,25 @@ def film_zonal_form(scene):
     lds = C.c_uint32(0)
     _check(load_library().wtgpu_test_film_zonal_form(scene.handle, C.byref(lds)))
     return {0: "global", 1: "lds"}.get(lds.value)
+
+
+def film_segments_form(scene):
+    """Test hook (wtgpu_test_hooks.h): (form, overflow) of the scene's last film_segments_device call — form "tiled" or "global" (the form of its first two
+    phases, WTGPU_FILM_SEGMENTS_TILED; both give the same bits, so only this tells which one ran),
+    overflow the union-find's overflow word (0: no loop hit its step bound); (None, None) before the first call."""
+    form, over = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().wtgpu_test_film_segments_form(scene.handle, C.byref(form), C.byref(over)))
+    return (None, None) if form.value == 0xFFFFFFFF else ({0: "global", 1: "tiled"}[form.value], int(over.value))
+
+
+def film_segments_find(parent, x, bound):
+    """Test hook (wtgpu_test_hooks.h): the segments' union-find walk by itself on the host (csrc/kernels_segments.hip: seg_find) — up the uint32
+    `parent` array from x with at most `bound` loads -> (where it ended, whether the bound was hit or a parent lies above its child)."""
+    import numpy as np
+    parent = np.ascontiguousarray(parent, dtype=np.uint32).reshape(-1)
+    root, over = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().wtgpu_test_film_segments_find(parent.ctypes.data, parent.size, int(x), int(bound), C.byref(root), C.byref(over)))
+    return int(root.value), bool(over.value)
 
 
 def load_library():
@@ -311,6 +344,10 @@ def load_library():
     lib.wtgpu_film_stats_source_host.argtypes = [vp, src, C.POINTER(FilmStatsSpec), vp, u32, vp, vp]
     lib.wtgpu_film_zonal_device.argtypes = [vp, vp, src, C.POINTER(FilmZonalSpec), vp, vp, vp, vp, C.POINTER(u64), vp]
     lib.wtgpu_film_zonal_host.argtypes = [vp, src, C.POINTER(FilmZonalSpec), vp, vp, u32, vp, vp, C.POINTER(u64), vp]
+    lib.wtgpu_film_segments_device.argtypes = [vp, vp, C.POINTER(FilmSegmentsSpec), vp, vp, vp, C.POINTER(FilmSegmentsInfo), vp]
+    lib.wtgpu_film_segments_host.argtypes = [vp, C.POINTER(FilmSegmentsSpec), vp, vp, u32, vp, C.POINTER(FilmSegmentsInfo), vp]
+    lib.wtgpu_test_film_segments_form.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    lib.wtgpu_test_film_segments_find.argtypes = [vp, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.wtgpu_test_fz_sum.argtypes = [vp, vp, u64, C.POINTER(C.c_double)]
     lib.wtgpu_test_film_zonal_form.argtypes = [vp, C.POINTER(u32)]
     lib.wtgpu_film_compare_source_device.argtypes = [vp, vp, src, src, C.POINTER(FilmCompareSpec), vp, vp, vp]
@@ -1182,6 +1219,74 @@ class Scene:
         out = self._film_zonal("film_zonal_host", top, call, n_zones, stokes_component, scale, range, bins, abs, luminance, paint)
         del keep
         return out
+
+    # ---- connected segments of a label plane (wtgpu_film_segments_*; csrc/wt/film_segments.h) ----
+    def _film_segments(self, what, call, diagonal, min_area, max_records):
+        """What film_segments_device / film_segments_host share: the spec, the info and the records as a dict.  call(spec, info, rec) runs the pass and
+        returns the segment plane."""
+        import numpy as np
+        if int(min_area) < 0 or int(max_records) < 0:
+            raise ValueError(f"{what}: min_area and max_records must not be negative")
+        n_rec = min(int(max_records), self.width * self.height)       # (there are never more segments than pixels)
+        spec = FilmSegmentsSpec(FILM_SEGMENTS_DIAGONAL if diagonal else 0, int(min_area), n_rec, 0)
+        info = FilmSegmentsInfo()
+        rec = np.zeros(n_rec, dtype=np.dtype(FILM_SEGMENT_FIELDS))
+        segments = call(spec, info, rec.ctypes.data if n_rec else None)
+        rec = rec[:min(int(info.n_segments), n_rec)]
+        area = rec["area"].astype(np.float64)
+        return {"segments": segments, "n_segments": int(info.n_segments), "n_dropped": int(info.n_dropped), "n_members": int(info.n_members),
+                "n_dropped_pixels": int(info.n_dropped_pixels), "klass": np.ascontiguousarray(rec["klass"]), "area": np.ascontiguousarray(rec["area"]),
+                "first": np.ascontiguousarray(rec["first"]), "bbox": np.stack([rec["x0"], rec["y0"], rec["x1"], rec["y1"]], axis=1),
+                "centroid": np.stack([rec["sum_x"] / area, rec["sum_y"] / area], axis=1)}
+
+    def film_segments_device(self, classes=None, *, mask=None, diagonal=False, min_area=1, max_records=65536, stream=None):
+        """The connected segments of a label plane where it is (wtgpu_film_segments_device): which REGION a pixel lies in, where the id maps say which
+        class.  classes: a contiguous torch int32 tensor [H, W] on the scene's device holding the u32 ids (first_hit's, line_of_sight's, a zone
+        plane; torch.uint32 is taken too), or None: every pixel has class 0.  A pixel is a member iff mask > 0 (or any, without a mask: a torch f32
+        tensor [H, W] there) and its class is not 0xFFFFFFFF; members of one class that are edge neighbours — diagonal=True: or corner
+        neighbours — are linked, and a segment is a connected component.  Segments of at least max(min_area, 1) pixels are kept and numbered
+        from 0 in the order of their first (smallest row-major) pixel.  Returns a dict: "segments", a torch int32 tensor [H, W] there holding the
+        number of the pixel's segment, -1 (0xFFFFFFFF) for no member or a dropped segment — film_zonal_device takes it as zones as it is;
+        n_segments, n_dropped, n_members, n_dropped_pixels (int); and of the first min(n_segments, max_records) segments the numpy arrays klass, area,
+        first (uint32), bbox [K', 4] (x0, y0, x1, y1, inclusive) and centroid [K', 2] (x, y; float64)."""
+        import torch
+        if self.device is None:
+            raise WtgpuError("film_segments_device: upload(device) first")
+        dev = torch.device("cuda", self.device)
+
+        def plane(t, name, dtypes, words):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype in dtypes
+                                      and tuple(t.shape) == (self.height, self.width) and t.is_contiguous()):
+                raise ValueError(f"film_segments_device: {name}: a contiguous {words} tensor [{self.height}, {self.width}] on cuda:{self.device} expected")
+            return None if t is None else t.data_ptr()
+        d_classes = plane(classes, "classes", (torch.int32, getattr(torch, "uint32", torch.int32)), "torch.int32 (or uint32)")
+        d_mask = plane(mask, "mask", (torch.float32,), "torch.float32")
+        st = self._stream_arg(stream, dev)
+
+        def call(spec, info, rec):
+            out = torch.empty((self.height, self.width), dtype=torch.int32, device=dev)
+            _check(load_library().wtgpu_film_segments_device(self._h, st, C.byref(spec), d_classes, d_mask, out.data_ptr(), C.byref(info), rec))
+            return out
+        return self._film_segments("film_segments_device", call, diagonal, min_area, max_records)
+
+    def film_segments_host(self, classes=None, *, mask=None, diagonal=False, min_area=1, max_records=65536, threads=0):
+        """film_segments_device's twin on the host from numpy arrays (wtgpu_film_segments_host): the same dict, every field bit for bit the device's,
+        "segments" a numpy uint32 array.  classes: a contiguous int32 or uint32 array [H, W] or None; mask: a contiguous float32 array [H, W] or
+        None.  The result does not depend on threads.  No device needed."""
+        import numpy as np
+
+        def plane(t, name, dtypes, words):
+            if t is not None and not (isinstance(t, np.ndarray) and t.dtype in dtypes and t.shape == (self.height, self.width) and t.flags.c_contiguous):
+                raise ValueError(f"film_segments_host: {name}: a contiguous {words} array [{self.height}, {self.width}] expected")
+            return None if t is None else t.ctypes.data
+        p_classes = plane(classes, "classes", (np.int32, np.uint32), "int32 or uint32")
+        p_mask = plane(mask, "mask", (np.float32,), "float32")
+
+        def call(spec, info, rec):
+            out = np.zeros((self.height, self.width), dtype=np.uint32)
+            _check(load_library().wtgpu_film_segments_host(self._h, C.byref(spec), p_classes, p_mask, int(threads), out.ctypes.data, C.byref(info), rec))
+            return out
+        return self._film_segments("film_segments_host", call, diagonal, min_area, max_records)
 
     # ---- film comparison (wtgpu_film_compare_*; csrc/wt/film_compare.h) ----
     def _film_compare(self, call, stokes_component, abs, luminance, eps):

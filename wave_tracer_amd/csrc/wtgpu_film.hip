@@ -1,5 +1,5 @@
 // wave_tracer_amd — the entry points that read films: develop, the tonemap spec / device / host calls (kernels_develop.hip), film statistics
-// (kernels_stats.hip), zonal film statistics (kernels_zonal.hip), film comparison (kernels_compare.hip), the polarisation view (kernels_polar.hip) and the denoiser of two half-films (kernels_denoise.hip); what they check of a film
+// (kernels_stats.hip), zonal film statistics (kernels_zonal.hip), connected segments of a label plane (kernels_segments.hip), film comparison (kernels_compare.hip), the polarisation view (kernels_polar.hip) and the denoiser of two half-films (kernels_denoise.hip); what they check of a film
 // and keep with the scene between calls.  The four passes that read a film take a wtgpu_film_source — the accumulators or a developed f32 film — and
 // the accumulator-taking entry points are those calls with an accumulator source.
 #include <cstddef>
@@ -8,6 +8,7 @@
 #include "wt/tonemap.h"
 #include "wt/film_stats.h"
 #include "wt/film_zonal.h"
+#include "wt/film_segments.h"
 #include "wt/film_compare.h"
 #include "wt/film_polar.h"
 #include "wt/film_denoise.h"
@@ -423,6 +424,96 @@ int wtgpu_test_fz_sum(uint64_t* words, const float* x, uint64_t n, double* out) 
         if (fz_finite(x[i])) fz_add(w, x[i]);
     for (uint32_t k = 0; k < kFzWords; ++k) words[k] = w[k];
     *out = fz_round(w);
+    return WTGPU_OK;
+}
+
+// ---- connected segments of a label plane (kernels_segments.hip; wt/film_segments.h) -----------------------------------------------------------------
+static_assert(sizeof(wtgpu_film_segment) == sizeof(film_segment_t) && offsetof(wtgpu_film_segment, first) == offsetof(film_segment_t, first) &&
+                  offsetof(wtgpu_film_segment, y1) == offsetof(film_segment_t, y1) && offsetof(wtgpu_film_segment, sum_y) == offsetof(film_segment_t, sum_y),
+              "the kernels' record is wtgpu_film_segment");
+static_assert(sizeof(wtgpu_film_segments_info) == 4 * sizeof(unsigned long long) && sizeof(wtgpu_film_segments_info) <= kSegHeadBytes, "the head opens with wtgpu_film_segments_info");
+// what both entry points check
+static int film_segments_check(const wtgpu_scene* s, const wtgpu_film_segments_spec* spec, const uint32_t* segments, const wtgpu_film_segments_info* info,
+                               const wtgpu_film_segment* records) {
+    if (!s || !spec) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (!segments || !info) return fail(WTGPU_ERR_INVALID, "film_segments: segments and info expected (one of them is NULL)");
+    if (!records && spec->max_records > 0) return fail(WTGPU_ERR_INVALID, "film_segments: max_records " + std::to_string(spec->max_records) + " without records (records is NULL)");
+    if (spec->flags & ~(uint32_t)SEG_DIAGONAL) return fail(WTGPU_ERR_INVALID, "film_segments: flags 0 or 1 (DIAGONAL) expected, got " + std::to_string(spec->flags));
+    if ((uint64_t)s->host.sensor.width * s->host.sensor.height >= kSegMaxPixels)
+        return fail(WTGPU_ERR_INVALID, "film_segments: a sensor of 2^31 pixels or more (pixel indices and areas are 32-bit)");
+    return WTGPU_OK;
+}
+
+int wtgpu_film_segments_device(wtgpu_scene* s, void* stream_, const wtgpu_film_segments_spec* spec, const uint32_t* d_classes, const float* d_mask, uint32_t* d_segments,
+                               wtgpu_film_segments_info* info, wtgpu_film_segment* records) {
+    if (const int rc = film_segments_check(s, spec, d_segments, info, records)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "film_segments: scene not uploaded");
+    return film_on_device(s, stream_, "film_segments", [&](hipStream_t stream, uint64_t npix) -> int {
+        // the block: head | records | the union-find's arrays.  Head and records come back through the pinned copy; there are never more
+        // segments than pixels.  The call waits for its result, so the block is free again when it returns.
+        const uint32_t max_records = (uint32_t)std::min<uint64_t>(spec->max_records, npix);
+        const size_t off_work = kSegHeadBytes + (size_t)max_records * sizeof(film_segment_t), total = off_work + (size_t)film_segments_scratch_words(npix) * sizeof(uint32_t);
+        if (s->d_segments_bytes < total) {
+            unsigned char* old = s->d_segments;
+            s->d_segments = nullptr, s->d_segments_bytes = 0;   // (reset first: a failed free leaves nothing behind for the next call)
+            if (old) HIP_CHECK(hipFree(old));
+            void* p = nullptr;
+            if (const hipError_t e = hipMalloc(&p, total)) return fail(WTGPU_ERR_OOM, std::string("hipMalloc of ") + std::to_string(total) + " bytes: " + hipGetErrorString(e));
+            s->d_segments = static_cast<unsigned char*>(p), s->d_segments_bytes = total;
+        }
+        if (s->h_segments_bytes < off_work) {
+            unsigned char* old = s->h_segments;
+            s->h_segments = nullptr, s->h_segments_bytes = 0;
+            if (old) HIP_CHECK(hipHostFree(old));
+            HIP_CHECK(hipHostMalloc((void**)&s->h_segments, off_work, hipHostMallocDefault));
+            s->h_segments_bytes = off_work;
+        }
+        unsigned char* d = s->d_segments;
+        s->segments_last_overflow = 0xFFFFFFFFu;
+        s->segments_last_tiled = s->knobs.film_segments_tiled ? 1u : 0u;
+        const int e = film_segments_launch(s->host.sensor, stream, s->n_cus, s->segments_last_tiled, spec->flags, spec->min_area, max_records, d_classes, d_mask, d_segments, d, d + kSegHeadBytes,
+                                           reinterpret_cast<uint32_t*>(d + off_work));
+        if (e) return fail(WTGPU_ERR_HIP, std::string("k_seg: ") + hipGetErrorString((hipError_t)e));
+        // the head first: it says how many records there are
+        HIP_CHECK(hipMemcpyAsync(s->h_segments, d, kSegHeadBytes, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        uint32_t overflow = 0;
+        std::memcpy(&overflow, s->h_segments + sizeof(wtgpu_film_segments_info), sizeof overflow);
+        s->segments_last_overflow = overflow;
+        if (overflow)
+            return fail(WTGPU_ERR_HIP, "film_segments: a union-find loop hit its step bound (the pixel count): the library's fault, not the planes'; the segment plane holds nothing to be read");
+        std::memcpy(info, s->h_segments, sizeof *info);
+        const size_t n_rec = (size_t)std::min<uint64_t>(info->n_segments, max_records);
+        if (n_rec) {
+            HIP_CHECK(hipMemcpyAsync(s->h_segments + kSegHeadBytes, d + kSegHeadBytes, n_rec * sizeof(film_segment_t), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            std::memcpy(records, s->h_segments + kSegHeadBytes, n_rec * sizeof(film_segment_t));
+        }
+        return WTGPU_OK;
+    });
+}
+int wtgpu_film_segments_host(const wtgpu_scene* s, const wtgpu_film_segments_spec* spec, const uint32_t* classes, const float* mask, uint32_t n_threads, uint32_t* segments,
+                             wtgpu_film_segments_info* info, wtgpu_film_segment* records) {
+    if (const int rc = film_segments_check(s, spec, segments, info, records)) return rc;
+    return film_on_host([&] {
+        unsigned long long counts[4];
+        film_segments_host(s->host.sensor, spec->flags, spec->min_area, spec->max_records, classes, mask, n_threads, segments, counts, records);
+        *info = wtgpu_film_segments_info{counts[0], counts[1], counts[2], counts[3]};
+    });
+}
+int wtgpu_test_film_segments_form(const wtgpu_scene* s, uint32_t* form, uint32_t* overflow) {
+    if (!s || !form || !overflow) return fail(WTGPU_ERR_INVALID, "null argument");
+    *form = s->segments_last_tiled;
+    *overflow = s->segments_last_overflow;
+    return WTGPU_OK;
+}
+int wtgpu_test_film_segments_find(const uint32_t* parent, uint32_t n, uint32_t x, uint32_t bound, uint32_t* root, uint32_t* overflow) {
+    if (!parent || !root || !overflow || x >= n) return fail(WTGPU_ERR_INVALID, "film_segments_find: parent, root, overflow and x < n expected");
+    for (uint32_t i = 0; i < n; ++i)
+        if (parent[i] >= n) return fail(WTGPU_ERR_INVALID, "film_segments_find: parent[" + std::to_string(i) + "] is not below n");
+    bool over = false;
+    *root = film_segments_find_host(parent, x, bound, over);
+    *overflow = over ? 1u : 0u;
     return WTGPU_OK;
 }
 

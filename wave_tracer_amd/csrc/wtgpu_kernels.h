@@ -19,6 +19,7 @@
 //   kernels_develop.hip k_develop / k_develop_tonemap: film development and tonemapping (not part of a render)
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
 //   kernels_zonal.hip   k_film_zonal / k_film_zonal_finish / k_film_zonal_paint: a statistics record per (zone, plane) of a film under a label plane (not part of a render)
+//   kernels_segments.hip k_seg_runs / _merge (or k_seg_tile / _border) / _roots / _count / _scan / _number / _relabel: connected segments of a label plane by union-find (not part of a render)
 //   kernels_compare.hip k_film_compare (+ k_film_finish): difference statistics of two films (not part of a render)
 //   kernels_polar.hip   k_film_polar (+ k_film_finish): polarisation maps, Stokes sums and false-colour picture of a Stokes film (not part of a render)
 //   kernels_denoise.hip k_denoise_prepare / _variance / k_denoise_filter: the dual-buffer non-local-means filter of two half-films (not part of a render)
@@ -664,6 +665,20 @@ int film_zonal_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, co
                       unsigned long long* d_outside, void* d_rec, float* d_paint);
 void film_zonal_host(const sensor_t& sn, const wtgpu_film_source& film, uint32_t s, uint32_t flags, const uint32_t* zones, const float* mask, const float* edges, uint32_t bins,
                      uint32_t n_zones, uint32_t n_threads, void* out_rec, unsigned long long* out_hist, unsigned long long* out_outside, float* paint);
+// kernels_segments.hip: connected segments of a label plane (wtgpu_film_segments_device / wtgpu_film_segments_host; wt/film_segments.h).  d_classes: null or
+// [height][width] u32; d_mask: null or [height][width] f32; flags: SEG_DIAGONAL; d_segments: [height][width] u32, every pixel written.  d_head: kSegHeadBytes
+// (n_segments, n_dropped, n_members, n_dropped_pixels as u64, then the overflow word: not zero where a union-find loop hit its step bound, and the plane
+// is then not to be read); d_records: max_records film_segment_t, of which the first min(n_segments, max_records) are written; d_work:
+// film_segments_scratch_words(pixels) u32.  tiled: the form of the first two phases, 1 k_seg_tile + k_seg_border, 0 k_seg_runs + k_seg_merge (WTGPU_FILM_SEGMENTS_TILED).  The launch clears what has to be cleared.  Two memsets and seven kernels on `stream`; returns a hipError_t.
+constexpr size_t kSegHeadBytes = 48;
+uint64_t film_segments_scratch_words(uint64_t npix);
+int film_segments_launch(const sensor_t& sn, hipStream_t stream, uint32_t n_cus, uint32_t tiled, uint32_t flags, uint32_t min_area, uint32_t max_records, const uint32_t* d_classes,
+                         const float* d_mask, uint32_t* d_segments, void* d_head, void* d_records, uint32_t* d_work);
+// info: the four u64 of wtgpu_film_segments_info; out_records: max_records film_segment_t (may be null with max_records == 0)
+void film_segments_host(const sensor_t& sn, uint32_t flags, uint32_t min_area, uint32_t max_records, const uint32_t* classes, const float* mask, uint32_t n_threads,
+                        uint32_t* segments, unsigned long long* info, void* out_records);
+// the kernels' find by itself on the host: up parent[] from x with at most `bound` loads; overflow is set where the bound is hit or a parent lies above its child
+uint32_t film_segments_find_host(const uint32_t* parent, uint32_t x, uint32_t bound, bool& overflow);
 // kernels_compare.hip: comparison of two films (wtgpu_film_compare_device / wtgpu_film_compare_host; wt/film_compare.h).  Two sets of films as wtgpu_render fills
 // them (the same pointers twice are fine); s: the Stokes component; flags: FS_ABS | FS_LUMINANCE; eps: finite, > 0.  d_rec: film_compare_rec_t per plane;
 // d_sums: kFsMaxPlanes x kFcSums x fs_scratch_len(pixels) doubles; d_wave: film_rec_wave_bytes(pixels, n_cus) bytes (the polarisation view's too) — none of them has to be

@@ -66,6 +66,12 @@ int wtgpu_test_fz_sum(uint64_t* words, const float* x, uint64_t n, double* out);
 /* The form of k_film_zonal that the scene's last wtgpu_film_zonal_device call launched: *lds = 1 the LDS form, 0 the global form, 0xFFFFFFFF no call
  * yet.  Both forms give the same bits, so only this tells a test which one ran. */
 int wtgpu_test_film_zonal_form(const wtgpu_scene* s, uint32_t* lds);
+/* The segments' union-find walk by itself (csrc/kernels_segments.hip: seg_find), on the host: up parent[n] from x with at most `bound` loads.  *root: where
+ * the walk ended; *overflow: 1 where the bound was hit or a parent lies above its child (the kernels then refuse), else 0. */
+int wtgpu_test_film_segments_find(const uint32_t* parent, uint32_t n, uint32_t x, uint32_t bound, uint32_t* root, uint32_t* overflow);
+/* The scene's last wtgpu_film_segments_device call: *form = 1 the tiled form of its first two phases, 0 the global form (both give the same
+ * bits, so only this tells a test which one ran), *overflow = its overflow word (0: no loop hit its step bound); both 0xFFFFFFFF before the first call. */
+int wtgpu_test_film_segments_form(const wtgpu_scene* s, uint32_t* form, uint32_t* overflow);
 #ifdef __cplusplus
 }
 #endif

@@ -327,6 +327,11 @@ void release_device(wtgpu_scene* s) {
     s->d_zonal = s->h_zonal = nullptr;
     s->d_zonal_bytes = s->h_zonal_bytes = 0;
     s->zonal_last_lds = 0xFFFFFFFFu;
+    if (s->d_segments) (void)hipFree(s->d_segments);
+    if (s->h_segments) (void)hipHostFree(s->h_segments);
+    s->d_segments = s->h_segments = nullptr;
+    s->d_segments_bytes = s->h_segments_bytes = 0;
+    s->segments_last_overflow = s->segments_last_tiled = 0xFFFFFFFFu;
     s->uploaded = false;
 }
 

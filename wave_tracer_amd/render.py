@@ -227,6 +227,72 @@ def coverage_by_los(scene, films, spe, emitter=None, samples=0, seed=1, **kw):
     return zonal(scene, films, spe, zones, 2, **kw)
 
 
+def segments(scene, classes=None, **kw):
+    """The connected segments of a label plane where it is: classes (or, with classes=None, kw["mask"]) a torch tensor on the scene's device
+    (Scene.film_segments_device; a scene that is not uploaded yet is uploaded to that device) or a numpy array (Scene.film_segments_host).
+    kw: mask, diagonal, min_area, max_records, and stream or threads.  Returns that call's dict."""
+    first = classes if classes is not None else kw.get("mask")
+    if first is None or isinstance(first, np.ndarray):
+        if first is None and scene.device is not None:
+            return scene.film_segments_device(classes, **kw)
+        return scene.film_segments_host(classes, **kw)
+    if scene.device is None:
+        scene.upload(first.device.index or 0)
+    return scene.film_segments_device(classes, **kw)
+
+
+COVERAGE_HOLES_MAX_ZONES = 65536   # the zonal statistics' limit
+
+
+def coverage_holes(scene, films, spe, threshold, *, scale="dB", below=True, stokes_component=0, channel=0, mask=None, min_area=1, diagonal=False, **zonal_kw):
+    """The coverage holes of a film — the connected areas where one plane of the developed film lies below a threshold (below=False: at or above
+    it) — and the film's statistics inside each, computed where the films are: films = (value, weight, light) or one developed f32 film, torch
+    tensors on the scene's device or numpy arrays (the host twins).  The plane is spectral channel `channel` of Stokes component
+    stokes_component; it is compared in its own f32 scale with the threshold as an f32 — for scale="dB" 10^(threshold / 10), converted once on the
+    host (wtgpu_film_stats_edges, as film_stats does).  A NaN is in no hole.  A hole is a segment (segments(): mask, min_area, diagonal) of the
+    class plane that holds 1 in the hole pixels and NO_ZONE elsewhere.  Returns segments()'s dict with "threshold" (the f32 compared against) and
+    "zonal": zonal() over the holes (in the same scale; zonal_kw: abs, luminance, range, bins, paint), so that zonal["n"][i] is the area of hole i.  zonal()
+    reports EVERY plane of the film's Stokes component, not only the thresholded one: the plane the holes were cut from is column `channel` of its
+    arrays (zonal["max"][:, channel] lies below the threshold for below=True) — or None,
+    with "zonal_skipped" saying why, where there is no hole or there are more than 65536 of them."""
+    import ctypes as C
+    from .api import FILM_STATS_SCALES, FilmStatsSpec
+    if scale not in FILM_STATS_SCALES:
+        raise ValueError(f"coverage_holes: scale 'dB' or 'linear' expected, got {scale!r}")
+    if not 0 <= int(channel) < scene.spectral_channels or not 0 <= int(stokes_component) < scene.stokes:
+        raise ValueError(f"coverage_holes: channel {channel} / stokes_component {stokes_component} out of range ({scene.spectral_channels} channels, {scene.stokes} Stokes components)")
+    edge = np.zeros(1, dtype=np.float32)
+    fs = FilmStatsSpec(0, FILM_STATS_SCALES.index(scale), 0, 0, float(threshold), 0.0)
+    _check(load_library().wtgpu_film_stats_edges(C.byref(fs), edge.ctypes.data))
+    first = films[0] if isinstance(films, (tuple, list)) else films
+    host = isinstance(first, np.ndarray)
+    shape = (scene.height, scene.width, scene.spectral_channels, scene.stokes)
+    if host:
+        developed = develop(scene, *films, spe) if isinstance(films, (tuple, list)) else films
+        x = developed.reshape(shape)[:, :, int(channel), int(stokes_component)]
+        inside = x < edge[0] if below else x >= edge[0]       # (False for a NaN either way)
+        classes = np.ascontiguousarray(np.where(inside, 1, NO_ZONE).astype(np.uint32))
+    else:
+        import torch
+        if scene.device is None:
+            scene.upload(first.device.index or 0)
+        developed = scene.develop_device(*films, spe) if isinstance(films, (tuple, list)) else films
+        x = developed.reshape(shape)[:, :, int(channel), int(stokes_component)]
+        thr = float(edge[0])                                    # (an f32's value: the comparison with the f32 plane is exact)
+        inside = x < thr if below else x >= thr
+        classes = torch.where(inside, 1, -1).to(torch.int32).contiguous()
+    out = segments(scene, classes, mask=mask, min_area=min_area, diagonal=diagonal)
+    out["threshold"] = edge[0]
+    out["zonal"] = None
+    if out["n_segments"] == 0:
+        out["zonal_skipped"] = "no segments"
+    elif out["n_segments"] > COVERAGE_HOLES_MAX_ZONES:
+        out["zonal_skipped"] = f"{out['n_segments']} segments: more than the {COVERAGE_HOLES_MAX_ZONES} zones the zonal statistics hold (raise min_area)"
+    else:
+        out["zonal"] = zonal(scene, films, spe, out["segments"], out["n_segments"], stokes_component=stokes_component, mask=mask, scale=scale, **zonal_kw)
+    return out
+
+
 SHADOW_GUIDE_SCALE = 1.0 / FIRST_HIT_GUIDE_KF ** 2   # shadow_guides' default scale for every plane: first_hit_guides' 2.78.  UNTUNED.
 SHADOW_GUIDE_T_MIN = 1e-4                            # shadow_guides' default t_min, in diagonals of the scene's bounding box
 
