@@ -638,6 +638,35 @@ int wtgpu_film_segments_device(wtgpu_scene* scene, void* stream, const wtgpu_fil
 int wtgpu_film_segments_host(const wtgpu_scene* scene, const wtgpu_film_segments_spec* spec, const uint32_t* classes, const float* mask, uint32_t n_threads,
                              uint32_t* segments, wtgpu_film_segments_info* info, wtgpu_film_segment* records);
 
+/* Distance transform of a label plane: how FAR a pixel lies from the nearest site, exactly, and which site that is — distance to coverage, depth
+ * inside a hole and its deepest point, the nearest region, rings around a region, erode / dilate by a radius.  The result holds no
+ * floating-point number and ties are broken by pixel index, so device and host agree bit for bit.
+ *   inputs    classes[height][width] u32 or NULL (every pixel has class 0); mask[height][width] f32 or NULL.
+ *   member    as for wtgpu_film_segments_*: (mask == NULL or mask[p] > 0 — a NaN is not) and classes[p] != 0xFFFFFFFF.
+ *   site      the members; with flag 1 INVERT the pixels that are no members.  The film's outside holds no site.
+ *   dist2     [height][width] u32: the minimum over the sites s of (x - xs)^2 + (y - ys)^2; 0 on a site; 0xFFFFFFFF everywhere where the plane has no site.
+ *   nearest   optional [height][width] u32: the row-major index of a site at that distance, of several the smallest index; 0xFFFFFFFF without a site.
+ *   info      n_sites: the number of sites; max_dist2: the maximum of dist2 over all pixels; argmax: the lowest pixel index that attains it.  No
+ *             special cases: an all-sites plane gives 0 / 0, a plane without a site 0xFFFFFFFF / 0.
+ * Errors (WTGPU_ERR_INVALID with a message opened by "film_distance:"): dist2 or info NULL; flags other than 0 / 1; a sensor wider or higher than
+ * 32768 pixels (so that every dist2 stays below 2^31 and a vertical offset fits 16 bits); the device call without an upload. */
+typedef struct wtgpu_film_distance_spec {
+    uint32_t flags /* 1 INVERT */, pad[3];
+} wtgpu_film_distance_spec;
+typedef struct wtgpu_film_distance_info {
+    uint64_t n_sites, argmax;
+    uint32_t max_dist2, pad;
+} wtgpu_film_distance_info;
+/* On the device, on `stream`: d_classes, d_mask (each may be NULL), d_dist2 and d_nearest (may be NULL) are DEVICE memory; info is HOST memory, and
+ * the call waits for it.  Two kernels (csrc/kernels_distance.hip): the columns, then the rows; their loops are counted by the height and the
+ * width and wait for nobody.  Needs an uploaded scene; its scratch memory (16 bits per pixel and a little more) is sized by the call, grown when
+ * a later call needs more and freed with the scene; touches neither films nor counters. */
+int wtgpu_film_distance_device(wtgpu_scene* scene, void* stream, const wtgpu_film_distance_spec* spec, const uint32_t* d_classes, const float* d_mask,
+                               uint32_t* d_dist2, uint32_t* d_nearest, wtgpu_film_distance_info* info);
+/* The same from HOST memory; n_threads: 0 all cores, and the result does not depend on it.  nearest may be NULL.  No device needed. */
+int wtgpu_film_distance_host(const wtgpu_scene* scene, const wtgpu_film_distance_spec* spec, const uint32_t* classes, const float* mask, uint32_t n_threads,
+                             uint32_t* dist2, uint32_t* nearest, wtgpu_film_distance_info* info);
+
 /* Denoising a film from its two half-films A and B (two renders of disjoint sample ranges, as render_to_noise keeps them) without the films leaving
  * the device: the dual-buffer non-local-means filter of Rousselle, Knaus and Zwicker 2012 — the weights that filter one half are computed from the
  * other, the per-pixel variance comes from (a - b)^2, and the difference of the two filtered halves estimates the error that is left.

@@ -99,6 +99,19 @@ FILM_SEGMENT_FIELDS = [("klass", "<u4"), ("area", "<u4"), ("first", "<u4"), ("x0
 FILM_SEGMENTS_DIAGONAL = 1
 
 
+class FilmDistanceSpec(C.Structure):  # wtgpu_film_distance_spec
+    _fields_ = [("flags", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
+class FilmDistanceInfo(C.Structure):  # wtgpu_film_distance_info
+    _fields_ = [("n_sites", C.c_uint64), ("argmax", C.c_uint64), ("max_dist2", C.c_uint32), ("pad", C.c_uint32)]
+
+
+FILM_DISTANCE_INVERT = 1
+FILM_DISTANCE_NONE = 0xFFFFFFFF   # dist2 and nearest where the plane holds no site
+FILM_DISTANCE_MAX_SIDE = 32768    # wider or higher sensors are refused
+
+
 class FilmCompareSpec(C.Structure):  # wtgpu_film_compare_spec
     _fields_ = [("stokes_component", C.c_uint32), ("flags", C.c_uint32), ("eps", C.c_double)]
 
@@ -194,6 +207,7 @@ SYMBOLS = ["wtgpu_scene_create_named", "wtgpu_scene_create_from_desc", "wtgpu_sc
            "wtgpu_tonemap_source_device", "wtgpu_tonemap_source_host", "wtgpu_film_stats_source_device", "wtgpu_film_stats_source_host",
            "wtgpu_film_compare_source_device", "wtgpu_film_compare_source_host", "wtgpu_film_polar_source_device", "wtgpu_film_polar_source_host",
            "wtgpu_film_zonal_device", "wtgpu_film_zonal_host", "wtgpu_film_segments_device", "wtgpu_film_segments_host",
+           "wtgpu_film_distance_device", "wtgpu_film_distance_host",
            "wtgpu_film_denoise_device", "wtgpu_film_denoise_host",
            "wtgpu_film_denoise_guided_device", "wtgpu_film_denoise_guided_host"]
 PROGRESS_CB = C.CFUNCTYPE(C.c_int, C.c_uint64, C.c_uint64, C.c_void_p)
@@ -250,6 +264,15 @@ def film_segments_form(scene):
     form, over = C.c_uint32(0), C.c_uint32(0)
     _check(load_library().wtgpu_test_film_segments_form(scene.handle, C.byref(form), C.byref(over)))
     return (None, None) if form.value == 0xFFFFFFFF else ({0: "global", 1: "tiled"}[form.value], int(over.value))
+
+
+def film_distance_form(scene):
+    """Test hook (wtgpu_test_hooks.h): the form of k_dist_rows that the scene's last film_distance_device call launched — "groups" (the outward search
+    ends at |dx| = 64 and goes on group by group, WTGPU_FILM_DISTANCE_GROUPS=1) or "plain" (the outward search alone); both give the same bits, so
+    only this tells which one ran; None before the first call."""
+    groups = C.c_uint32(0)
+    _check(load_library().wtgpu_test_film_distance_form(scene.handle, C.byref(groups)))
+    return {0: "plain", 1: "groups"}.get(groups.value)
 
 
 def film_segments_find(parent, x, bound):
@@ -346,6 +369,9 @@ def load_library():
     lib.wtgpu_film_zonal_host.argtypes = [vp, src, C.POINTER(FilmZonalSpec), vp, vp, u32, vp, vp, C.POINTER(u64), vp]
     lib.wtgpu_film_segments_device.argtypes = [vp, vp, C.POINTER(FilmSegmentsSpec), vp, vp, vp, C.POINTER(FilmSegmentsInfo), vp]
     lib.wtgpu_film_segments_host.argtypes = [vp, C.POINTER(FilmSegmentsSpec), vp, vp, u32, vp, C.POINTER(FilmSegmentsInfo), vp]
+    lib.wtgpu_film_distance_device.argtypes = [vp, vp, C.POINTER(FilmDistanceSpec), vp, vp, vp, vp, C.POINTER(FilmDistanceInfo)]
+    lib.wtgpu_film_distance_host.argtypes = [vp, C.POINTER(FilmDistanceSpec), vp, vp, u32, vp, vp, C.POINTER(FilmDistanceInfo)]
+    lib.wtgpu_test_film_distance_form.argtypes = [vp, C.POINTER(u32)]
     lib.wtgpu_test_film_segments_form.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     lib.wtgpu_test_film_segments_find.argtypes = [vp, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.wtgpu_test_fz_sum.argtypes = [vp, vp, u64, C.POINTER(C.c_double)]
@@ -1287,6 +1313,54 @@ class Scene:
             _check(load_library().wtgpu_film_segments_host(self._h, C.byref(spec), p_classes, p_mask, int(threads), out.ctypes.data, C.byref(info), rec))
             return out
         return self._film_segments("film_segments_host", call, diagonal, min_area, max_records)
+
+    # ---- distance transform of a label plane (wtgpu_film_distance_*; csrc/wt/film_distance.h) ----
+    def film_distance_device(self, classes=None, *, mask=None, invert=False, nearest=False, stream=None):
+        """The exact Euclidean distance transform of a label plane where it is (wtgpu_film_distance_device): how FAR each pixel lies from the nearest
+        site, and which site that is.  classes: a contiguous torch int32 tensor [H, W] on the scene's device holding the u32 ids (torch.uint32 is
+        taken too), or None: every pixel has class 0; mask: a torch f32 tensor [H, W] there or None.  A pixel is a member as for
+        film_segments_device (mask > 0, or any without a mask, and a class other than 0xFFFFFFFF); the sites are the members, with invert=True the
+        pixels that are none.  The film's outside holds no site.  Returns a dict: "dist2", a torch int32 tensor [H, W] there holding the u32 bits of
+        the squared pixel distance to the nearest site (0 on a site; -1, 0xFFFFFFFF, everywhere where there is no site); "nearest", with nearest=True
+        the same kind of tensor holding the row-major index of that site (of several equally far the smallest index; -1 without a site), else None;
+        n_sites, max_dist2 (the largest dist2) and argmax (the lowest pixel index that attains it) as int."""
+        import torch
+        if self.device is None:
+            raise WtgpuError("film_distance_device: upload(device) first")
+        dev = torch.device("cuda", self.device)
+
+        def plane(t, name, dtypes, words):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype in dtypes
+                                      and tuple(t.shape) == (self.height, self.width) and t.is_contiguous()):
+                raise ValueError(f"film_distance_device: {name}: a contiguous {words} tensor [{self.height}, {self.width}] on cuda:{self.device} expected")
+            return None if t is None else t.data_ptr()
+        d_classes = plane(classes, "classes", (torch.int32, getattr(torch, "uint32", torch.int32)), "torch.int32 (or uint32)")
+        d_mask = plane(mask, "mask", (torch.float32,), "torch.float32")
+        st = self._stream_arg(stream, dev)
+        spec, info = FilmDistanceSpec(FILM_DISTANCE_INVERT if invert else 0), FilmDistanceInfo()
+        dist2 = torch.empty((self.height, self.width), dtype=torch.int32, device=dev)
+        near = torch.empty((self.height, self.width), dtype=torch.int32, device=dev) if nearest else None
+        _check(load_library().wtgpu_film_distance_device(self._h, st, C.byref(spec), d_classes, d_mask, dist2.data_ptr(), near.data_ptr() if nearest else None, C.byref(info)))
+        return {"dist2": dist2, "nearest": near, "n_sites": int(info.n_sites), "max_dist2": int(info.max_dist2), "argmax": int(info.argmax)}
+
+    def film_distance_host(self, classes=None, *, mask=None, invert=False, nearest=False, threads=0):
+        """film_distance_device's twin on the host from numpy arrays (wtgpu_film_distance_host): the same dict, every field bit for bit the device's,
+        "dist2" and "nearest" numpy uint32 arrays.  classes: a contiguous int32 or uint32 array [H, W] or None; mask: a contiguous float32 array
+        [H, W] or None.  The result does not depend on threads.  No device needed."""
+        import numpy as np
+
+        def plane(t, name, dtypes, words):
+            if t is not None and not (isinstance(t, np.ndarray) and t.dtype in dtypes and t.shape == (self.height, self.width) and t.flags.c_contiguous):
+                raise ValueError(f"film_distance_host: {name}: a contiguous {words} array [{self.height}, {self.width}] expected")
+            return None if t is None else t.ctypes.data
+        p_classes = plane(classes, "classes", (np.int32, np.uint32), "int32 or uint32")
+        p_mask = plane(mask, "mask", (np.float32,), "float32")
+        spec, info = FilmDistanceSpec(FILM_DISTANCE_INVERT if invert else 0), FilmDistanceInfo()
+        dist2 = np.zeros((self.height, self.width), dtype=np.uint32)
+        near = np.zeros((self.height, self.width), dtype=np.uint32) if nearest else None
+        _check(load_library().wtgpu_film_distance_host(self._h, C.byref(spec), p_classes, p_mask, int(threads), dist2.ctypes.data, near.ctypes.data if nearest else None,
+                                                       C.byref(info)))
+        return {"dist2": dist2, "nearest": near, "n_sites": int(info.n_sites), "max_dist2": int(info.max_dist2), "argmax": int(info.argmax)}
 
     # ---- film comparison (wtgpu_film_compare_*; csrc/wt/film_compare.h) ----
     def _film_compare(self, call, stokes_component, abs, luminance, eps):

@@ -1,5 +1,5 @@
 // wave_tracer_amd — the entry points that read films: develop, the tonemap spec / device / host calls (kernels_develop.hip), film statistics
-// (kernels_stats.hip), zonal film statistics (kernels_zonal.hip), connected segments of a label plane (kernels_segments.hip), film comparison (kernels_compare.hip), the polarisation view (kernels_polar.hip) and the denoiser of two half-films (kernels_denoise.hip); what they check of a film
+// (kernels_stats.hip), zonal film statistics (kernels_zonal.hip), connected segments of a label plane (kernels_segments.hip), its distance transform (kernels_distance.hip), film comparison (kernels_compare.hip), the polarisation view (kernels_polar.hip) and the denoiser of two half-films (kernels_denoise.hip); what they check of a film
 // and keep with the scene between calls.  The four passes that read a film take a wtgpu_film_source — the accumulators or a developed f32 film — and
 // the accumulator-taking entry points are those calls with an accumulator source.
 #include <cstddef>
@@ -9,6 +9,7 @@
 #include "wt/film_stats.h"
 #include "wt/film_zonal.h"
 #include "wt/film_segments.h"
+#include "wt/film_distance.h"
 #include "wt/film_compare.h"
 #include "wt/film_polar.h"
 #include "wt/film_denoise.h"
@@ -514,6 +515,63 @@ int wtgpu_test_film_segments_find(const uint32_t* parent, uint32_t n, uint32_t x
     bool over = false;
     *root = film_segments_find_host(parent, x, bound, over);
     *overflow = over ? 1u : 0u;
+    return WTGPU_OK;
+}
+
+// ---- distance transform of a label plane (kernels_distance.hip; wt/film_distance.h) -------------------------------------------------------------------
+static_assert(sizeof(wtgpu_film_distance_info) == 24 && offsetof(wtgpu_film_distance_info, max_dist2) == 16, "wtgpu_film_distance_info");
+// what both entry points check
+static int film_distance_check(const wtgpu_scene* s, const wtgpu_film_distance_spec* spec, const uint32_t* dist2, const wtgpu_film_distance_info* info) {
+    if (!s || !spec) return fail(WTGPU_ERR_INVALID, "null argument");
+    if (!dist2 || !info) return fail(WTGPU_ERR_INVALID, "film_distance: dist2 and info expected (one of them is NULL)");
+    if (spec->flags & ~(uint32_t)DIST_INVERT) return fail(WTGPU_ERR_INVALID, "film_distance: flags 0 or 1 (INVERT) expected, got " + std::to_string(spec->flags));
+    if (s->host.sensor.width > kDistMaxSide || s->host.sensor.height > kDistMaxSide)
+        return fail(WTGPU_ERR_INVALID, "film_distance: a sensor wider or higher than 32768 pixels (squared distances stay below 2^31 and a vertical offset fits 16 bits)");
+    return WTGPU_OK;
+}
+
+int wtgpu_film_distance_device(wtgpu_scene* s, void* stream_, const wtgpu_film_distance_spec* spec, const uint32_t* d_classes, const float* d_mask, uint32_t* d_dist2,
+                               uint32_t* d_nearest, wtgpu_film_distance_info* info) {
+    if (const int rc = film_distance_check(s, spec, d_dist2, info)) return rc;
+    if (!s->uploaded) return fail(WTGPU_ERR_INVALID, "film_distance: scene not uploaded");
+    return film_on_device(s, stream_, "film_distance", [&](hipStream_t stream, uint64_t) -> int {
+        // the block: head | the column offsets and the groups' minima.  The head comes back through the pinned copy; the call waits for its result,
+        // so the block is free again when it returns.
+        const size_t total = kDistHeadBytes + (size_t)film_distance_scratch_bytes(s->host.sensor.width, s->host.sensor.height);
+        if (s->d_distance_bytes < total) {
+            unsigned char* old = s->d_distance;
+            s->d_distance = nullptr, s->d_distance_bytes = 0;   // (reset first: a failed free leaves nothing behind for the next call)
+            if (old) HIP_CHECK(hipFree(old));
+            void* p = nullptr;
+            if (const hipError_t e = hipMalloc(&p, total)) return fail(WTGPU_ERR_OOM, std::string("hipMalloc of ") + std::to_string(total) + " bytes: " + hipGetErrorString(e));
+            s->d_distance = static_cast<unsigned char*>(p), s->d_distance_bytes = total;
+        }
+        if (!s->h_distance) HIP_CHECK(hipHostMalloc((void**)&s->h_distance, kDistHeadBytes, hipHostMallocDefault));
+        unsigned char* d = s->d_distance;
+        s->distance_last_groups = s->knobs.film_distance_groups ? 1u : 0u;
+        const int e = film_distance_launch(s->host.sensor, stream, s->distance_last_groups, spec->flags, d_classes, d_mask, d_dist2, d_nearest, d, d + kDistHeadBytes);
+        if (e) return fail(WTGPU_ERR_HIP, std::string("k_dist: ") + hipGetErrorString((hipError_t)e));
+        HIP_CHECK(hipMemcpyAsync(s->h_distance, d, kDistHeadBytes, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        unsigned long long head[2];
+        std::memcpy(head, s->h_distance, sizeof head);
+        *info = wtgpu_film_distance_info{head[0], (uint32_t)~(uint32_t)head[1], (uint32_t)(head[1] >> 32), 0u};
+        return WTGPU_OK;
+    });
+}
+int wtgpu_film_distance_host(const wtgpu_scene* s, const wtgpu_film_distance_spec* spec, const uint32_t* classes, const float* mask, uint32_t n_threads, uint32_t* dist2,
+                             uint32_t* nearest, wtgpu_film_distance_info* info) {
+    if (const int rc = film_distance_check(s, spec, dist2, info)) return rc;
+    if ((uint64_t)s->host.sensor.width * s->host.sensor.height == 0) return fail(WTGPU_ERR_INVALID, "film_distance: the film has no pixels");
+    return film_on_host([&] {
+        unsigned long long out[3];
+        film_distance_host(s->host.sensor, spec->flags, classes, mask, n_threads, dist2, nearest, out);
+        *info = wtgpu_film_distance_info{out[0], out[1], (uint32_t)out[2], 0u};
+    });
+}
+int wtgpu_test_film_distance_form(const wtgpu_scene* s, uint32_t* groups) {
+    if (!s || !groups) return fail(WTGPU_ERR_INVALID, "null argument");
+    *groups = s->distance_last_groups;
     return WTGPU_OK;
 }
 

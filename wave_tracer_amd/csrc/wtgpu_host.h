@@ -132,6 +132,12 @@ struct wtgpu_scene {
     size_t d_segments_bytes = 0, h_segments_bytes = 0;
     uint32_t segments_last_overflow = 0xFFFFFFFFu;   // the overflow word of the last wtgpu_film_segments_device call (wtgpu_test_film_segments_form)
     uint32_t segments_last_tiled = 0xFFFFFFFFu;      // the form that call took: 1 tiled, 0 global
+    // wtgpu_film_distance_device: the head (site count, key of the maximum) on the device and pinned on the host, the column offsets and the groups'
+    // minima on the device; sized by the call and grown when a later call needs more
+    unsigned char* d_distance = nullptr;
+    unsigned char* h_distance = nullptr;
+    size_t d_distance_bytes = 0;
+    uint32_t distance_last_groups = 0xFFFFFFFFu;     // the form the last wtgpu_film_distance_device call took: 1 with the group level, 0 without (wtgpu_test_film_distance_form)
     float* d_denoise = nullptr;          // wtgpu_film_denoise_device: the developed half-films, their variance and what one direction leaves for the other
     // WTGPU_TRACE_AB (diagnostic, tests/test_gpu_traversal.py): accumulated over the replayed rounds — milliseconds of k_trace_refill / k_trace_sm on the
     // same queue, words of their outputs that differ (traversal records + triangle lists + heavy-queue checksums), walks replayed

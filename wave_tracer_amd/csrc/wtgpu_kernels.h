@@ -20,6 +20,7 @@
 //   kernels_stats.hip   k_film_stats / k_film_stats_finish: range, histogram and sum of a film (not part of a render)
 //   kernels_zonal.hip   k_film_zonal / k_film_zonal_finish / k_film_zonal_paint: a statistics record per (zone, plane) of a film under a label plane (not part of a render)
 //   kernels_segments.hip k_seg_runs / _merge (or k_seg_tile / _border) / _roots / _count / _scan / _number / _relabel: connected segments of a label plane by union-find (not part of a render)
+//   kernels_distance.hip k_dist_columns / k_dist_rows: exact Euclidean distance transform of a label plane with the nearest site (not part of a render)
 //   kernels_compare.hip k_film_compare (+ k_film_finish): difference statistics of two films (not part of a render)
 //   kernels_polar.hip   k_film_polar (+ k_film_finish): polarisation maps, Stokes sums and false-colour picture of a Stokes film (not part of a render)
 //   kernels_denoise.hip k_denoise_prepare / _variance / k_denoise_filter: the dual-buffer non-local-means filter of two half-films (not part of a render)
@@ -679,6 +680,18 @@ void film_segments_host(const sensor_t& sn, uint32_t flags, uint32_t min_area, u
                         uint32_t* segments, unsigned long long* info, void* out_records);
 // the kernels' find by itself on the host: up parent[] from x with at most `bound` loads; overflow is set where the bound is hit or a parent lies above its child
 uint32_t film_segments_find_host(const uint32_t* parent, uint32_t x, uint32_t bound, bool& overflow);
+// kernels_distance.hip: distance transform of a label plane (wtgpu_film_distance_device / wtgpu_film_distance_host; wt/film_distance.h).  d_classes: null or
+// [height][width] u32; d_mask: null or [height][width] f32; flags: DIST_INVERT; d_dist2: [height][width] u32, every pixel written; d_nearest: null or the
+// same.  d_head: kDistHeadBytes (n_sites u64, then the key of the maximum: max d² << 32 | ~argmax); d_work: film_distance_scratch_bytes(width, height)
+// bytes, aligned to 16.  groups: the form of k_dist_rows, 1 with the group level, 0 the outward search alone (WTGPU_FILM_DISTANCE_GROUPS).  The launch
+// clears what has to be cleared.  One memset and two kernels on `stream`; returns a hipError_t.
+constexpr size_t kDistHeadBytes = 32;
+uint64_t film_distance_scratch_bytes(uint32_t width, uint32_t height);
+int film_distance_launch(const sensor_t& sn, hipStream_t stream, uint32_t groups, uint32_t flags, const uint32_t* d_classes, const float* d_mask, uint32_t* d_dist2,
+                         uint32_t* d_nearest, void* d_head, void* d_work);
+// nearest may be null; info: n_sites, argmax, max_dist2
+void film_distance_host(const sensor_t& sn, uint32_t flags, const uint32_t* classes, const float* mask, uint32_t n_threads, uint32_t* dist2, uint32_t* nearest,
+                        unsigned long long* info);
 // kernels_compare.hip: comparison of two films (wtgpu_film_compare_device / wtgpu_film_compare_host; wt/film_compare.h).  Two sets of films as wtgpu_render fills
 // them (the same pointers twice are fine); s: the Stokes component; flags: FS_ABS | FS_LUMINANCE; eps: finite, > 0.  d_rec: film_compare_rec_t per plane;
 // d_sums: kFsMaxPlanes x kFcSums x fs_scratch_len(pixels) doubles; d_wave: film_rec_wave_bytes(pixels, n_cus) bytes (the polarisation view's too) — none of them has to be

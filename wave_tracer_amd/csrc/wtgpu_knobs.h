@@ -13,7 +13,7 @@ struct knobs_t {
     uint32_t heavy_waves_per_cu, round_blocks_per_cu, grid_div_b, grid_div_c, grid_div_hard, grid_mul_flux;
     uint32_t sorted_interact, coop_io, staged_connect, connect_class, tiled_splat, pass_c_tiers, pass_c_easy_tries, pass_c_thin;
     uint32_t trace_staged, trace_stages, trace_staged_rounds, trace_sm, trace_ab;
-    uint32_t develop_per_pixel, tonemap_lds_table, film_polar_staged, film_denoise_fused, film_denoise_guide_lds, first_hit_per_sample, los_per_sample, film_zonal_lds, film_zonal_blocks, film_segments_tiled;
+    uint32_t develop_per_pixel, tonemap_lds_table, film_polar_staged, film_denoise_fused, film_denoise_guide_lds, first_hit_per_sample, los_per_sample, film_zonal_lds, film_zonal_blocks, film_segments_tiled, film_distance_groups;
     uint32_t dbg_stage;   // an int (WTGPU_DEBUG_STAGE may be negative), kept in 32 bits like the rest: read it as (int)dbg_stage
     uint32_t host_prof, trace_launch, tail_diag, trace_ab_verbose;
     uint32_t grid_div_cls[4];   // WTGPU_GRID_CLS, beside the table

@@ -78,6 +78,7 @@ const knob_t kKnobs[] = {
     {"WTGPU_FILM_ZONAL_LDS", K(film_zonal_lds), KNOB_U32, 1, 0, 1, "k_film_zonal: 1 every block accumulates in a table in LDS wherever the table of n_zones x planes entries fits the 64 KB a launch may ask for, and flushes it once (measured 7 to 165 times faster wherever it fits); 0 the atomics go straight to global memory always (A/B: tools/bench_film_zonal.py; both forms are exact, the results do not depend on it)"},
     {"WTGPU_FILM_ZONAL_BLOCKS", K(film_zonal_blocks), KNOB_U32, 0, 0, kU32, "k_film_zonal: n > 0 caps the grid at n blocks (the tests: one wavefront takes many chunks of a small film); 0 the film statistics' rule (kernels_film.h: film_grid_blocks); the results do not depend on it"},
     {"WTGPU_FILM_SEGMENTS_TILED", K(film_segments_tiled), KNOB_U32, 0, 0, 1, "wtgpu_film_segments_device, the first two phases: 1 a block labels a tile of 64 x 32 pixels in LDS (k_seg_tile: the row runs and a union-find with ds_min_u32) and the global merge unions across tile borders only (k_seg_border); 0 the row runs of a wavefront's 64 pixels (k_seg_runs) and every remaining link in global memory (k_seg_merge), the default: measured level with the tiled form on percolation and spiral planes and 7 to 22 % faster on coherent ones; the tiled form is ahead on one plane of 28, critical percolation with 8 neighbours at 1920 x 1088, at 0.85 - 0.88 (docs/FEATURES.md; A/B: tools/bench_film_segments.py; the result is canonical and does not depend on it)"},
+    {"WTGPU_FILM_DISTANCE_GROUPS", K(film_distance_groups), KNOB_U32, 1, 0, 1, "wtgpu_film_distance_device, k_dist_rows: 1 a lane's outward search over the columns ends at |dx| = 64 and goes on group by group, a 64-column group being skipped where (distance to its nearer edge)^2 + (its min |dy|)^2 cannot reach or tie the best; 0 the outward search alone, column by column to the end (docs/FEATURES.md; A/B: tools/bench_film_distance.py; the result is canonical and does not depend on it)"},
     // ---- diagnostics and bring-up aids
     {"WTGPU_DEBUG_STAGE", K(dbg_stage), KNOB_INT, 1 << 30, INT_MIN, INT_MAX, "bring-up aid: stops launching the round kernels after stage n (INVALID RESULTS)"},
     {"WTGPU_HOST_PROF", K(host_prof), KNOB_PRESENT, 0, 0, 1, "set: host time spent inside each kind of launch call, printed per render call"},

@@ -72,6 +72,9 @@ int wtgpu_test_film_segments_find(const uint32_t* parent, uint32_t n, uint32_t x
 /* The scene's last wtgpu_film_segments_device call: *form = 1 the tiled form of its first two phases, 0 the global form (both give the same
  * bits, so only this tells a test which one ran), *overflow = its overflow word (0: no loop hit its step bound); both 0xFFFFFFFF before the first call. */
 int wtgpu_test_film_segments_form(const wtgpu_scene* s, uint32_t* form, uint32_t* overflow);
+/* The form of k_dist_rows that the scene's last wtgpu_film_distance_device call launched: *groups = 1 with the group level, 0 the outward search
+ * alone, 0xFFFFFFFF no call yet.  Both forms give the same bits, so only this tells a test which one ran. */
+int wtgpu_test_film_distance_form(const wtgpu_scene* s, uint32_t* groups);
 #ifdef __cplusplus
 }
 #endif

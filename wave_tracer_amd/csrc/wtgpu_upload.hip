@@ -332,6 +332,11 @@ void release_device(wtgpu_scene* s) {
     s->d_segments = s->h_segments = nullptr;
     s->d_segments_bytes = s->h_segments_bytes = 0;
     s->segments_last_overflow = s->segments_last_tiled = 0xFFFFFFFFu;
+    if (s->d_distance) (void)hipFree(s->d_distance);
+    if (s->h_distance) (void)hipHostFree(s->h_distance);
+    s->d_distance = s->h_distance = nullptr;
+    s->d_distance_bytes = 0;
+    s->distance_last_groups = 0xFFFFFFFFu;
     s->uploaded = false;
 }
 

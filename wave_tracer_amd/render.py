@@ -293,6 +293,114 @@ def coverage_holes(scene, films, spe, threshold, *, scale="dB", below=True, stok
     return out
 
 
+def distance(scene, classes=None, **kw):
+    """The exact Euclidean distance transform of a label plane where it is: classes (or, with classes=None, kw["mask"]) a torch tensor on the
+    scene's device (Scene.film_distance_device; a scene that is not uploaded yet is uploaded to that device) or a numpy array
+    (Scene.film_distance_host).  kw: mask, invert, nearest, and stream or threads.  Returns that call's dict."""
+    first = classes if classes is not None else kw.get("mask")
+    if first is None or isinstance(first, np.ndarray):
+        if first is None and scene.device is not None:
+            return scene.film_distance_device(classes, **kw)
+        return scene.film_distance_host(classes, **kw)
+    if scene.device is None:
+        scene.upload(first.device.index or 0)
+    return scene.film_distance_device(classes, **kw)
+
+
+def _radius2(what, radius):
+    """the integer floor(radius²) that a squared pixel distance is compared with (below 2^31, above every distance of a sensor the pass takes)"""
+    import math
+    from fractions import Fraction
+    if not (math.isfinite(radius) and radius >= 0):
+        raise ValueError(f"{what}: a finite radius >= 0 expected, got {radius!r}")
+    return min(math.floor(Fraction(radius) ** 2), 2 ** 31 - 1)
+
+
+def _bool_plane(what, plane):
+    """a bool plane as the f32 mask whose members (> 0) are its True pixels"""
+    if isinstance(plane, np.ndarray):
+        if plane.dtype != np.bool_:
+            raise ValueError(f"{what}: a bool plane expected, got {plane.dtype}")
+        return np.ascontiguousarray(plane, dtype=np.float32)
+    import torch
+    if not isinstance(plane, torch.Tensor) or plane.dtype != torch.bool:
+        raise ValueError(f"{what}: a bool plane (torch or numpy) expected")
+    return plane.float().contiguous()
+
+
+def _dist2_u32(dist2):
+    """dist2 as signed 64-bit numbers holding the u32 values (torch keeps the bits in int32)"""
+    if isinstance(dist2, np.ndarray):
+        return dist2.view(np.uint32).astype(np.int64)
+    return dist2.long() & 0xFFFFFFFF
+
+
+def dilate(scene, plane, radius):
+    """Dilation of a bool plane (torch on the scene's device, or numpy) by a disc: True where a True pixel lies within `radius` pixels, centre to
+    centre — dist2 <= floor(radius²), an integer comparison.  One distance() call.  The film's outside holds no site: nothing grows in from beyond
+    the border."""
+    r2 = _radius2("dilate", radius)
+    return _dist2_u32(distance(scene, mask=_bool_plane("dilate", plane))["dist2"]) <= r2
+
+
+def erode(scene, plane, radius):
+    """Erosion of a bool plane by a disc: True where no False pixel lies within `radius` pixels — the inverted transform's dist2 >
+    floor(radius²).  One distance() call.  The film's outside holds no site, so a region touching the border is not eroded from that side (scipy's
+    binary_erosion with border_value=1)."""
+    r2 = _radius2("erode", radius)
+    return _dist2_u32(distance(scene, mask=_bool_plane("erode", plane), invert=True)["dist2"]) > r2
+
+
+def opening(scene, plane, radius):
+    """erode, then dilate, by the same disc (two distance() calls): drops what is thinner than the disc — one-pixel bridges, specks.  The film's
+    outside holds no site, so a region touching the border is not eroded from that side."""
+    return dilate(scene, erode(scene, plane, radius), radius)
+
+
+def closing(scene, plane, radius):
+    """dilate, then erode, by the same disc (two distance() calls): fills what is thinner than the disc — pin-holes, one-pixel gaps.  The film's
+    outside holds no site, so a region touching the border is not eroded from that side."""
+    return erode(scene, dilate(scene, plane, radius), radius)
+
+
+def nearest_segment(scene, segments_plane):
+    """The Voronoi partition of a segments plane (segments()'s "segments", or any zone plane): every pixel gets the number of the segment whose
+    nearest pixel is nearest to it — segments.flatten()[nearest], of several equally far pixels the one with the smallest index — and NO_ZONE
+    where the plane holds no segment at all.  A zone plane that zonal() takes as it is (torch int32 holding the u32 bits, or numpy uint32)."""
+    near = distance(scene, segments_plane, nearest=True)["nearest"]
+    if isinstance(near, np.ndarray):
+        none = near == NO_ZONE
+        out = segments_plane.reshape(-1).view(np.uint32)[np.where(none, 0, near)]
+        return np.ascontiguousarray(np.where(none, NO_ZONE, out).astype(np.uint32))
+    import torch
+    none = near < 0
+    out = segments_plane.reshape(-1)[torch.where(none, torch.zeros_like(near), near).long()]
+    return torch.where(none, torch.full_like(out, -1), out).to(torch.int32).contiguous()
+
+
+def zones_from_distance(dist2, edges_px):
+    """Distance rings around the sites of a distance transform as a zone plane: zone i where edges_px[i]² <= d² < edges_px[i + 1]² (edges_px: at
+    least two, not negative, strictly increasing, in pixels), compared in integers against ceil(edge²); NO_ZONE elsewhere and where d² is
+    0xFFFFFFFF, no site.  dist2: distance()'s "dist2", a torch tensor (the zones stay on its device, as int32 holding the u32 bits) or a numpy
+    array (uint32)."""
+    import math
+    from fractions import Fraction
+    e = [float(v) for v in np.ravel(edges_px)]
+    if len(e) < 2 or not all(math.isfinite(v) and v >= 0 for v in e) or not all(a < b for a, b in zip(e, e[1:])):
+        raise ValueError("zones_from_distance: at least two finite, not negative, strictly increasing edges expected")
+    t = np.array([min(math.ceil(Fraction(v) ** 2), 2 ** 32 - 1) for v in e], dtype=np.int64)   # (d² < 2^32 - 1 always holds for a site's d²)
+    d = _dist2_u32(dist2)
+    if isinstance(d, np.ndarray):
+        inside = (d >= t[0]) & (d < t[-1])
+        z = np.searchsorted(t, d, side="right") - 1
+        return np.ascontiguousarray(np.where(inside, z, NO_ZONE).astype(np.uint32))
+    import torch
+    tt = torch.from_numpy(t).to(d.device)
+    inside = (d >= tt[0]) & (d < tt[-1])
+    z = torch.searchsorted(tt, d.contiguous(), right=True) - 1
+    return torch.where(inside, z, torch.full_like(z, -1)).to(torch.int32).contiguous()
+
+
 SHADOW_GUIDE_SCALE = 1.0 / FIRST_HIT_GUIDE_KF ** 2   # shadow_guides' default scale for every plane: first_hit_guides' 2.78.  UNTUNED.
 SHADOW_GUIDE_T_MIN = 1e-4                            # shadow_guides' default t_min, in diagonals of the scene's bounding box
 
